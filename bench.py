@@ -23,9 +23,15 @@ caller-created streams, one work_dev call per step.
 Multi-GPU (weak scaling): snapshots are independent, so every rank owns its own batch and there is
 no data-path collective; value = (steps * batch * world) / max-over-ranks time.  Timing: barrier + synchronize, clock
 on, K steps, synchronize, clock off, barrier, MAX over ranks of the per-rank times (the closing collective's own latency is
-not charged to the steps; the slowest rank decides).  After the timed region the
-ranks also run the product's sharded driver (doa.distributed.run_sharded: one stream cut into per-rank
-shards with their overlap halo, results gathered over RCCL) and rank 0 reports it as "sharded_run".
+not charged to the steps; the slowest rank decides).
+
+A plain run sets up, warms up, times the K steps, checks the last batch's angles against the directions they were
+generated with, and prints the headline.  --dump-outputs DIR also writes what the last timed step computed (rank 0's
+covariance, spectrum and peak ports) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for
+output.  --full adds every secondary measurement after the timed region: the same steps without the spectrum output,
+stand-alone per-kernel timings and the K1 roofline, the scan-kernel roofline, the other BASELINE configs, the CPU
+baseline, and with N > 1 the product's sharded driver (doa.distributed.run_sharded: one stream cut into per-rank
+shards with their overlap halo, results gathered over RCCL), reported by rank 0 as "sharded_run".
 """
 import argparse
 import ctypes
@@ -517,6 +523,12 @@ def main():
     ap.add_argument("--mode", choices=("batches", "streams"), default="batches",
                     help="batches: the K steps as ONE doa_music_pipeline_work_dev_batches call on one handle (the library owns the "
                          "overlap); streams: one work_dev call per step on caller-created streams, one handle each (rounds 1-2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run the secondary measurements (angles-only steps, per-kernel "
+                         "timings and rooflines, other configs, CPU baseline, sharded run); the --no-* switches below "
+                         "trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the driver-timed secondary configs (cfg3, cfg4, flowgraph shape)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-scan-roofline", action="store_true",
@@ -567,6 +579,8 @@ def main():
     if batched:
         pipes[0].set_lanes(n_streams)
     hip_streams = [torch.cuda.Stream() for _ in range(n_streams)]
+    # the stand-alone blocks are timed only with --full, but every run creates them (and their streams) here, so that the
+    # timed region meets the same streams and hardware queues with or without --full
     cov_blk = doa.autocorrelate(N_ANT, K_SNAP, 0, 0)
     music_blk = doa.MUSIC_lin_array(NORM_SPACING, M_SRC, N_ANT, P_SPEC)
     peak_blk = doa.find_local_max(M_SRC, P_SPEC, 0.0, 180.0)
@@ -630,8 +644,10 @@ def main():
 
     # host-side marshalling of every call below, before anything is launched
     n_setup = max(n_streams, nbuf)
-    for call in ((0, n_setup, True), (0, args.warmup, True), (0, args.steps, True), (0, 8, False), (0, args.steps, False),
-                 (max(0, args.steps - n_streams), min(n_streams, args.steps), True)):
+    calls = [(0, n_setup, True), (0, args.warmup, True), (0, args.steps, True)]
+    if args.full:
+        calls += [(0, 8, False), (0, args.steps, False), (max(0, args.steps - n_streams), min(n_streams, args.steps), True)]
+    for call in calls:
         prepare(*call)
     # setup, not warm-up: touch every lane / stream / buffer set once, so that first-launch code loading and lazy
     # workspace allocation never fall into a short timed region whatever --warmup says -- and the process group's first
@@ -655,53 +671,62 @@ def main():
     if dist is not None:
         elapsed = doa.distributed.max_over_ranks(elapsed, device="cuda", dist=dist)
 
-    # Secondary figure, never `value`: the same steps with no spectrum pointer (the fused block with only its angle port
-    # connected: the 4 KiB row per snapshot is neither converted to dB nor written).
-    run_steps(0, 8, with_spectrum=False)
-    torch.cuda.synchronize()
-    ta = time.perf_counter()
-    run_steps(0, args.steps, with_spectrum=False)
-    torch.cuda.synchronize()
-    angles_elapsed = time.perf_counter() - ta
-    run_steps(max(0, args.steps - n_streams), min(n_streams, args.steps))    # leave full results (spectra included) behind
-    torch.cuda.synchronize()
-
-    # Not part of the timed region (snapshots are independent: the path has no data-path collective): the sharded
-    # run itself, product code (doa.distributed.run_sharded), as a measurement of its own (sharded_run's docstring).
-    sharded = None
-    if dist is not None:
-        torch.cuda.synchronize()
-        try:
-            sharded = sharded_run(doa, torch, dist, world, rank, local_rank)
-        except Exception as e:                      # never lose the throughput number to the check
-            sharded = {"error": repr(e)}
-
-    # sanity: the estimates of the last batch must sit on the directions they were generated with
+    # what the last timed step handed its caller (buffer set = step index mod nbuf), before anything else runs
     import numpy as np
     last = (args.steps - 1) % nbuf
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("covariance", torch.view_as_real(cov[last])), ("spectrum", spec[last]),
+                        ("peak_values", mx[last]), ("peak_angles", am[last])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+    angles_elapsed, sharded = None, None
+    if args.full:
+        # Secondary figure, never `value`: the same steps with no spectrum pointer (the fused block with only its angle port
+        # connected: the 4 KiB row per snapshot is neither converted to dB nor written).
+        run_steps(0, 8, with_spectrum=False)
+        torch.cuda.synchronize()
+        ta = time.perf_counter()
+        run_steps(0, args.steps, with_spectrum=False)
+        torch.cuda.synchronize()
+        angles_elapsed = time.perf_counter() - ta
+        run_steps(max(0, args.steps - n_streams), min(n_streams, args.steps))    # leave full results (spectra included) behind
+        torch.cuda.synchronize()
+
+        # Not part of the timed region (snapshots are independent: the path has no data-path collective): the sharded
+        # run itself, product code (doa.distributed.run_sharded), as a measurement of its own (sharded_run's docstring).
+        if dist is not None:
+            torch.cuda.synchronize()
+            try:
+                sharded = sharded_run(doa, torch, dist, world, rank, local_rank)
+            except Exception as e:                      # never lose the throughput number to the check
+                sharded = {"error": repr(e)}
+
+    # sanity: the estimates of the last batch must sit on the directions they were generated with
     est = am[last].cpu().numpy()[:, 0]
     ang_err = float(np.abs(est - thetas[last][:, 0]).max())
     if not ang_err <= 1.0:
         raise SystemExit(f"bench sanity check failed: max angle error {ang_err} deg")
 
-    # ---- per-kernel timing with HIP events on the launch stream (after the timed region) -----------
-    def time_stage(fn, reps):
-        for i in range(5):
-            fn(i)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record(st)
-        for i in range(reps):
-            fn(i)
-        e1.record(st)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps           # us per launch (includes the ~1.5 us launch gap)
+    if args.full:
+        # ---- per-kernel timing with HIP events on the launch stream (after the timed region) -----------
+        def time_stage(fn, reps):
+            for i in range(5):
+                fn(i)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(st)
+            for i in range(reps):
+                fn(i)
+            e1.record(st)
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e3 / reps           # us per launch (includes the ~1.5 us launch gap)
 
-    reps = max(20, min(args.steps, 200))
-    t_cov = time_stage(lambda i: cov_blk.work_dev(BATCH, in_ptrs[i % nbuf], cov[i % nbuf].data_ptr(), st), reps)
-    t_music = time_stage(lambda i: music_blk.work_dev(BATCH, cov[i % nbuf].data_ptr(), spec[i % nbuf].data_ptr(), st), reps)
-    t_peak = time_stage(lambda i: peak_blk.work_dev(BATCH, spec[i % nbuf].data_ptr(), mx[i % nbuf].data_ptr(),
-                                                    am[i % nbuf].data_ptr(), st), reps)
+        reps = max(20, min(args.steps, 200))
+        t_cov = time_stage(lambda i: cov_blk.work_dev(BATCH, in_ptrs[i % nbuf], cov[i % nbuf].data_ptr(), st), reps)
+        t_music = time_stage(lambda i: music_blk.work_dev(BATCH, cov[i % nbuf].data_ptr(), spec[i % nbuf].data_ptr(), st), reps)
+        t_peak = time_stage(lambda i: peak_blk.work_dev(BATCH, spec[i % nbuf].data_ptr(), mx[i % nbuf].data_ptr(),
+                                                        am[i % nbuf].data_ptr(), st), reps)
 
     if rank != 0:
         if dist is not None:
@@ -711,8 +736,6 @@ def main():
     ab = algorithmic_bytes()
     total_snap = args.steps * BATCH * world
     value = total_snap / elapsed
-    cov_gbs = ab["cov"] * BATCH / (t_cov * 1e-6) / 1e9
-    traffic = pmc_traffic(COV_KERNEL, BATCH)
     out = {
         "metric": "DoA snapshots/sec (autocorr+MUSIC+peak) @ N=4, 1024 samp, 1024 angles",
         "value": value,
@@ -721,9 +744,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
-        "angles_only_mode": {"value": args.steps * BATCH / angles_elapsed, "unit": "snapshots/s (this rank)",
-                             "ms_per_step": angles_elapsed / args.steps * 1e3,
-                             "note": "secondary: same steps with no spectrum output requested (spectrum neither converted to dB nor written); not the headline"},
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -739,6 +759,22 @@ def main():
                    "parallelism": f"snapshot-sharded x{world}, no data-path collective"},
         "pipeline_gbs": ab["fused_total"] * value / world / 1e9,      # fused algorithmic bytes x rate, per GPU
         "pipeline_gbs_unfused_accounting": ab["total"] * value / world / 1e9,   # SURVEY 8(d)'s 41 KB/snapshot
+        "max_angle_error_deg": ang_err,
+    }
+    if dist is not None:
+        out["world_size_seen_by_rccl"] = int(dist.get_world_size())
+    if not args.full:
+        print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    cov_gbs = ab["cov"] * BATCH / (t_cov * 1e-6) / 1e9
+    traffic = pmc_traffic(COV_KERNEL, BATCH)
+    out.update({
+        "angles_only_mode": {"value": args.steps * BATCH / angles_elapsed, "unit": "snapshots/s (this rank)",
+                             "ms_per_step": angles_elapsed / args.steps * 1e3,
+                             "note": "secondary: same steps with no spectrum output requested (spectrum neither converted to dB nor written); not the headline"},
         # the dominant kernel (88 % of the step's bytes): K1, stand-alone launches on one stream
         "roofline": {"bound": "hbm", "kernel": COV_KERNEL + " (K1 covariance)",
                      "achieved": cov_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": cov_gbs / HBM_PEAK_GBS,
@@ -752,10 +788,8 @@ def main():
             "K5_peak": {"us": t_peak, "GBs": ab["peak"] * BATCH / (t_peak * 1e-6) / 1e9},
         },
         "kernels_note": "stand-alone block launches on one stream, HIP events; the timed pipeline fuses K5 into K4",
-        "max_angle_error_deg": ang_err,
-    }
+    })
     if dist is not None:
-        out["world_size_seen_by_rccl"] = int(dist.get_world_size())
         out["sharded_run"] = sharded
     if world == 1 and args.precision == 64 and not args.no_scan_roofline:
         # the kernel the north star grades (>= 70 % of HBM on the spectrum scan): at the benchmark step's own batch and

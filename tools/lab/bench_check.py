@@ -1,4 +1,4 @@
-"""lab: the figures of one bench.py JSON line that get quoted in DESIGN.md, one per line"""
+"""lab: the figures of one `bench.py --full` JSON line that get quoted in DESIGN.md, one per line"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("headline", d["value"], "ms/step", d["ms_per_step"], "roofline", d["roofline"]["frac"])

@@ -2,7 +2,7 @@
 # lab: the benchmark step by the covariance kernel's waves per CU (its 120-VGPR waves fill the register file at 16 per CU:
 # does leaving room for an EVD / scan wave beside them pay?)
 export DOA_HIP_LIB=$PWD/_ab/libdoa_hip_lab.so
-B="--no-cpu-baseline --no-scan-roofline --no-other-configs"
+B="--full --no-cpu-baseline --no-scan-roofline --no-other-configs"
 for rep in 1 2; do
 for w in 16 14 12 10 8; do
     export DOA_COV_WAVES_PER_CU=$w

@@ -14,7 +14,7 @@ run() {   # name, rocprof args..., -- program...
     rocprofv3 "$@" > $out/$name.log 2>&1 || echo "$name FAILED rc=$?" >> $out/commands.txt
 }
 T="--kernel-trace --stats --output-format csv"
-B="--no-cpu-baseline --no-scan-roofline --no-other-configs"
+B="--full --no-cpu-baseline --no-scan-roofline --no-other-configs"
 BENCH_SERIAL="python3 bench.py --steps 200 --warmup 20 --streams 1 $B"
 BENCH_OVL="python3 bench.py --steps 200 --warmup 20 $B"
 SCAN_L="python3 tools/profile_scan.py --batch 262144 --reps 40"
