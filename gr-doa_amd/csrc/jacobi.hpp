@@ -100,11 +100,14 @@ __device__ __forceinline__ JacobiRot<T> jacobi_rotation_classic(T app, T aqq, T 
 
 // Exact power-of-two scale that brings max |entry| into [1, 2) (eigenvectors, ranks and therefore P_N do not
 // depend on the scale; eigenvalues themselves are never output).  m = max |entry| as float; 0, inf, NaN -> 1.
+// The whole normal range is covered: for the top binade (e = 254) the factor is 2^-127, subnormal in float, and the
+// products with the item's normal entries are still exact.  A subnormal m (e = 0: every entry below 2^-126) is left
+// unscaled: out of the range the kernels are held to.
 template <typename T> __device__ __forceinline__ T jacobi_prescale(float m)
 {
     const int e = (__float_as_int(m) >> 23) & 0xff;
     if (e == 0 || e == 255) return (T)1;
-    return (T)__int_as_float((254 - e) << 23);              // 2^-(e-127)
+    return ldexp((T)1, 127 - e);                            // 2^-(e-127)
 }
 
 // Cyclic complex Jacobi on a Hermitian matrix kept as its real diagonal dg[] and strict upper
@@ -180,7 +183,7 @@ __device__ __forceinline__ void herm_jacobi(T (&dg)[N], T (&ur)[N][N], T (&ui)[N
 }
 
 // One covariance item -> its coefficient record, everything in this lane's registers (N <= 4 unrolled):
-// upper triangle of R (cheevd uplo='U'; element (r,c) at r + c*N) -> prescale -> cyclic Jacobi ->
+// upper triangle of R (cheevd uplo='U'; element (r,c) at r + c*N) -> prescale (float) -> cyclic Jacobi ->
 // ascending ranks (the eig_sym contract; ties -> lower index) -> P_N = sum over the N-M smallest of v v^H
 // -> u_l = sum_r P_N[r+l][r].  u[0] = u_0, u[2l-1] + j u[2l] = u_l, u[2N-1] = 0.  pn_out (optional):
 // column-major P_N as float2.
@@ -205,8 +208,28 @@ __device__ __forceinline__ void evd_item_coefficients(const float2 *__restrict__
     for (int r = 0; r < N; r++)
 #pragma unroll U
         for (int c = 0; c < N; c++) { vr[r][c] = (r == c) ? (T)1 : (T)0; vi[r][c] = 0; }
-    // 0, or NaN when the item holds a non-finite entry (0 * inf = 0 * NaN = NaN).  (No pre-scaling here: the classical
-    // rotation works in T throughout, and float-origin data cannot leave double's range.)
+    // float: pre-scaled like the other kernels (unscaled, dn = sum dg^2 overflows above ~1e19 and the absolute `tiny`
+    // ends the sweep early on small items).  double: no pre-scaling -- float-origin data cannot leave double's range, and
+    // the classical rotation then commutes exactly with a power-of-two scale of R.
+    if constexpr (sizeof(T) == 4) {
+        float m = 0.f;
+#pragma unroll U
+        for (int c = 0; c < N; c++) {
+            m = fmaxf(m, fabsf((float)dg[c]));
+#pragma unroll U
+            for (int r = 0; r < N; r++)
+                if (r < c) m = fmaxf(m, fmaxf(fabsf((float)ar[r][c]), fabsf((float)ai[r][c])));
+        }
+        const T sc = jacobi_prescale<T>(m);
+#pragma unroll U
+        for (int c = 0; c < N; c++) {
+            dg[c] *= sc;
+#pragma unroll U
+            for (int r = 0; r < N; r++)
+                if (r < c) { ar[r][c] *= sc; ai[r][c] *= sc; }
+        }
+    }
+    // 0, or NaN when the item holds a non-finite entry (0 * inf = 0 * NaN = NaN)
     T poison = 0;
 #pragma unroll U
     for (int c = 0; c < N; c++) {
