@@ -12,14 +12,17 @@
 // registers; partials meet in one DPP wave all-reduce and lanes 0..N^2-1 write the 8N^2-byte item
 // as one contiguous segment.  No LDS, no atomics.  Overlapping windows take a read-once two-kernel
 // path (cov_piece_kernel + cov_combine_kernel); 8 < N <= 16 runs on the matrix cores (cov_mfma_kernel).
-#include "common.hpp"
+// Every streaming kernel is templated on a sample loader (Fc32Samples / Sc16Samples): the sc16 form reads complex
+// int16 and widens in registers, with the same lanes, accumulators and summation order as the fc32 form.
+#include "kernels.hpp"
 
+#include <cmath>
 #include <cstdlib>
 
 namespace doa {
 
 struct CovArgs {
-    const float2 *in[DOA_MAX_ANT_ELE];
+    const void *in[DOA_MAX_ANT_ELE];   // N streams of the loader's sample type
     float2 *out;
     int n_ch;      // N
     int K;         // snapshot_size
@@ -33,7 +36,49 @@ struct CovArgs {
     float2 *pieces;       // [n_steps][2][N*N] raw sums of the pieces A_j, B_j
     int q, r;             // K = q*S + r
     int n_steps;          // n_out + q
+    float scale;          // sc16: the widening factor (Sc16Samples); unused for fc32
 };
+
+// Sample loaders.  A kernel asks for sample i of a stream (one) or for samples i and i+1 as (re_i, im_i, re_i+1, im_i+1)
+// (pair, one load); which samples a lane takes, which accumulator they meet and in what order is the kernel's business and
+// the same for every loader, so the sc16 and fc32 instantiations sum the same floats in the same order.
+//   fc32: gr_complex, 8 B per sample, pair = one 16-byte load.
+//   sc16: complex int16 (real first, 4 B per sample; one `int` here), pair = one 8-byte load, widened in registers as
+//         __fmul_rn((float)q, scale) per component -- one rounding, no contraction into the accumulating FMAs, so the
+//         kernel sees exactly the floats np.float32(q) * np.float32(scale) of an fc32 caller.
+// Both loaders run at the same unroll depth UN (as many load instructions in flight, half the bytes for sc16).  Twice the
+// sc16 depth, to keep as many BYTES in flight as fc32, measured worse on MI355X: the widened pairs raise the wave kernel
+// at N = 4 from 116 to 180 VGPRs, which halves its occupancy (K1 at the benchmark shape 16.0 against 12.6 us, at K = 2048 /
+// overlap 512 38.4 against 24.6 us, N = 8 37.5 against 34.9, N = 16 on the matrix cores unchanged; profiles/sc16_k1.txt).
+struct Fc32Samples {
+    typedef float2 sample_t;
+    template <bool NT> __device__ static __forceinline__ float4 pair(const sample_t *p, float)
+    {
+        return load_f4<NT>(reinterpret_cast<const float4 *>(p));
+    }
+    __device__ static __forceinline__ float2 one(const sample_t *p, float) { return *p; }
+};
+struct Sc16Samples {
+    typedef int sample_t;                  // low half = re, high half = im (little-endian int16 pair)
+    __device__ static __forceinline__ float2 widen(int w, float s)
+    {
+        return make_float2(__fmul_rn((float)(short)(w & 0xffff), s), __fmul_rn((float)(w >> 16), s));
+    }
+    template <bool NT> __device__ static __forceinline__ float4 pair(const sample_t *p, float s)
+    {
+        typedef int i32x2 __attribute__((ext_vector_type(2)));
+        i32x2 v;
+        if constexpr (NT) v = __builtin_nontemporal_load(reinterpret_cast<const i32x2 *>(p));
+        else v = *reinterpret_cast<const i32x2 *>(p);
+        const float2 a = widen(v.x, s), b = widen(v.y, s);
+        return make_float4(a.x, a.y, b.x, b.y);
+    }
+    __device__ static __forceinline__ float2 one(const sample_t *p, float s) { return widen(*p, s); }
+};
+template <class L> __device__ __forceinline__ const typename L::sample_t *stream(const CovArgs &g, int k)
+{
+    return static_cast<const typename L::sample_t *>(g.in[k]);
+}
 
 template <int TN> struct TriAcc {
     float d[TN];
@@ -58,8 +103,9 @@ template <int TN> __device__ __forceinline__ void tri_accumulate(TriAcc<TN> &acc
 }
 
 // One wave per snapshot, N = TN <= 8, Hermitian symmetry exploited.
-// VEC2: all streams 16-B aligned at every window start (base % 16 == 0, S even) -> float4 loads.
-template <int TN, bool VEC2, int UN, bool NT = false>
+// VEC2: all streams aligned to two samples at every window start (base 16-B aligned for fc32, 8-B for sc16; S even) ->
+// one load per sample pair.
+template <class L, int TN, bool VEC2, int UN, bool NT = false>
 __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
 {
     const int lane = threadIdx.x & (kWave - 1);
@@ -88,7 +134,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
             for (int u = 0; u < UN; u++)
 #pragma unroll
                 for (int a = 0; a < TN; a++)
-                    v[u][a] = load_f4<NT>(reinterpret_cast<const float4 *>(g.in[a] + base + 2 * (size_t)(p + u * kWave)));
+                    v[u][a] = L::template pair<NT>(stream<L>(g, a) + base + 2 * (size_t)(p + u * kWave), g.scale);
 #pragma unroll
             for (int u = 0; u < UN; u++) {
                 float2 x0[TN], x1[TN];
@@ -101,7 +147,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
         for (; p < npair; p += kWave) {
             float4 v[TN];
 #pragma unroll
-            for (int a = 0; a < TN; a++) v[a] = load_f4<NT>(reinterpret_cast<const float4 *>(g.in[a] + base + 2 * (size_t)p));
+            for (int a = 0; a < TN; a++) v[a] = L::template pair<NT>(stream<L>(g, a) + base + 2 * (size_t)p, g.scale);
             float2 x0[TN], x1[TN];
 #pragma unroll
             for (int a = 0; a < TN; a++) { x0[a] = make_float2(v[a].x, v[a].y); x1[a] = make_float2(v[a].z, v[a].w); }
@@ -111,7 +157,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
         if ((g.K & 1) && lane == 0) {
             float2 x[TN];
 #pragma unroll
-            for (int a = 0; a < TN; a++) x[a] = g.in[a][base + (size_t)(g.K - 1)];
+            for (int a = 0; a < TN; a++) x[a] = L::one(stream<L>(g, a) + (base + (size_t)(g.K - 1)), g.scale);
             tri_accumulate<TN>(acc, x);
         }
     } else {
@@ -119,7 +165,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
         for (int t = lane; t < g.K; t += kWave) {
             float2 x[TN];
 #pragma unroll
-            for (int a = 0; a < TN; a++) x[a] = g.in[a][base + (size_t)t];
+            for (int a = 0; a < TN; a++) x[a] = L::one(stream<L>(g, a) + (base + (size_t)t), g.scale);
             tri_accumulate<TN>(acc, x);
         }
     }
@@ -178,10 +224,9 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
 // K = 2048, overlap = 512), and the overlap's multiply-adds are not repeated either.  The price is
 // one more (tiny) launch, so windows without overlap stay on cov_wave_kernel.
 // ---------------------------------------------------------------------------------------------
-template <int TN, int UN, bool NT>
+template <class L, int TN, int UN, bool NT>
 __device__ __forceinline__ void accumulate_pairs(TriAcc<TN> &acc, const CovArgs &g, size_t first, int npair, int lane)
 {
-    const float2 *const *in = g.in;
     int p = lane;
     for (; p + (UN - 1) * kWave < npair; p += UN * kWave) {
         float4 v[UN][TN];
@@ -189,7 +234,7 @@ __device__ __forceinline__ void accumulate_pairs(TriAcc<TN> &acc, const CovArgs 
         for (int u = 0; u < UN; u++)
 #pragma unroll
             for (int a = 0; a < TN; a++)
-                v[u][a] = load_f4<NT>(reinterpret_cast<const float4 *>(in[a] + first + 2 * (size_t)(p + u * kWave)));
+                v[u][a] = L::template pair<NT>(stream<L>(g, a) + first + 2 * (size_t)(p + u * kWave), g.scale);
 #pragma unroll
         for (int u = 0; u < UN; u++) {
             float2 x0[TN], x1[TN];
@@ -202,7 +247,7 @@ __device__ __forceinline__ void accumulate_pairs(TriAcc<TN> &acc, const CovArgs 
     for (; p < npair; p += kWave) {
         float4 v[TN];
 #pragma unroll
-        for (int a = 0; a < TN; a++) v[a] = load_f4<NT>(reinterpret_cast<const float4 *>(in[a] + first + 2 * (size_t)p));
+        for (int a = 0; a < TN; a++) v[a] = L::template pair<NT>(stream<L>(g, a) + first + 2 * (size_t)p, g.scale);
         float2 x0[TN], x1[TN];
 #pragma unroll
         for (int a = 0; a < TN; a++) { x0[a] = make_float2(v[a].x, v[a].y); x1[a] = make_float2(v[a].z, v[a].w); }
@@ -244,8 +289,8 @@ template <int TN> __device__ __forceinline__ float2 tri_reduce_to_lane(TriAcc<TN
     return r;
 }
 
-// requires: S and r even, every stream base 16-B aligned (float4 loads at every piece start)
-template <int TN, int UN, bool NT>
+// requires: S and r even, every stream base aligned to two samples (one pair load at every piece start)
+template <class L, int TN, int UN, bool NT>
 __global__ __launch_bounds__(256) void cov_piece_kernel(CovArgs g)
 {
     const int lane = threadIdx.x & (kWave - 1);
@@ -257,13 +302,13 @@ __global__ __launch_bounds__(256) void cov_piece_kernel(CovArgs g)
         TriAcc<TN> acc;
         if (g.r > 0) {                                     // piece A_j
             tri_clear<TN>(acc);
-            accumulate_pairs<TN, UN, NT>(acc, g, base, g.r >> 1, lane);
+            accumulate_pairs<L, TN, UN, NT>(acc, g, base, g.r >> 1, lane);
             const float2 v = tri_reduce_to_lane<TN>(acc, lane);
             if (lane < TN * TN) po[lane] = v;
         }
         if (step + 1 < g.n_steps) {                        // piece B_j (the last step only contributes its A)
             tri_clear<TN>(acc);
-            accumulate_pairs<TN, UN, NT>(acc, g, base + (size_t)g.r, (g.S - g.r) >> 1, lane);
+            accumulate_pairs<L, TN, UN, NT>(acc, g, base + (size_t)g.r, (g.S - g.r) >> 1, lane);
             const float2 v = tri_reduce_to_lane<TN>(acc, lane);
             if (lane < TN * TN) po[TN * TN + lane] = v;
         }
@@ -312,19 +357,20 @@ __global__ __launch_bounds__(256) void cov_combine_kernel(CovArgs g)
 // C/D layout (row = 4*(l>>4)+reg, col = l&15) is written straight to the column-major item.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-template <bool VEC2> __global__ __launch_bounds__(256) void cov_mfma_kernel(CovArgs g)
+// UN wave-iterations (16 UN samples per lane group) of loads in flight.
+template <class L, bool VEC2, int UN> __global__ __launch_bounds__(256) void cov_mfma_kernel(CovArgs g)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave0 = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
     const int n_waves = gridDim.x * (blockDim.x / kWave);
     const int ch = lane & 15, grp = lane >> 4;
     const bool live = ch < g.n_ch;
-    const float2 *src = g.in[live ? ch : 0];
+    const typename L::sample_t *src = stream<L>(g, live ? ch : 0);
     for (int snap = wave0; snap < g.n_out; snap += n_waves) {
         // VEC2: per 16-sample block this lane takes samples {2 grp, 2 grp + 1, 8 + 2 grp, 9 + 2 grp}: each 16-byte
         // load instruction then covers 64 contiguous bytes per channel (two full 32-byte sectors) instead of four
-        // half-used ones; which four samples meet in one MFMA step does not matter for the sum
-        const float2 *p = src + (size_t)snap * (size_t)g.S + (VEC2 ? 2 : 4) * grp;
+        // half-used ones; which four samples meet in one MFMA step does not matter for the sum (sc16: two 8-byte loads)
+        const typename L::sample_t *p = src + (size_t)snap * (size_t)g.S + (VEC2 ? 2 : 4) * grp;
         f32x4_t acc_re = {0.f, 0.f, 0.f, 0.f}, acc_im = {0.f, 0.f, 0.f, 0.f};
         auto step = [&](float xr, float xi) {
             acc_re = __builtin_amdgcn_mfma_f32_16x16x4f32(xr, xr, acc_re, 0, 0, 0);
@@ -333,7 +379,6 @@ template <bool VEC2> __global__ __launch_bounds__(256) void cov_mfma_kernel(CovA
             acc_im = __builtin_amdgcn_mfma_f32_16x16x4f32(-xr, xi, acc_im, 0, 0, 0);
         };
         int t = 0;
-        constexpr int UN = 4;                          // 4 wave-iterations (64 samples) of loads in flight
         for (; t + 16 * UN <= g.K; t += 16 * UN) {
             float2 x[UN][4];
 #pragma unroll
@@ -341,13 +386,13 @@ template <bool VEC2> __global__ __launch_bounds__(256) void cov_mfma_kernel(CovA
                 if constexpr (VEC2) {
                     // default cache policy on purpose: the two loads of a block share 128-byte lines and
                     // want to meet in L1 (non-temporal: 169 vs 120 us)
-                    const float4 v0 = *reinterpret_cast<const float4 *>(p + t + 16 * u);
-                    const float4 v1 = *reinterpret_cast<const float4 *>(p + t + 16 * u + 8);
+                    const float4 v0 = L::template pair<false>(p + t + 16 * u, g.scale);
+                    const float4 v1 = L::template pair<false>(p + t + 16 * u + 8, g.scale);
                     x[u][0] = make_float2(v0.x, v0.y); x[u][1] = make_float2(v0.z, v0.w);
                     x[u][2] = make_float2(v1.x, v1.y); x[u][3] = make_float2(v1.z, v1.w);
                 } else {
 #pragma unroll
-                    for (int j = 0; j < 4; j++) x[u][j] = p[t + 16 * u + j];
+                    for (int j = 0; j < 4; j++) x[u][j] = L::one(p + t + 16 * u + j, g.scale);
                 }
             }
 #pragma unroll
@@ -360,7 +405,7 @@ template <bool VEC2> __global__ __launch_bounds__(256) void cov_mfma_kernel(CovA
             for (int j = 0; j < 4; j++) {
                 const int sidx = t + 4 * grp + j;
                 float2 v = make_float2(0.f, 0.f);
-                if (live && sidx < g.K) v = src[(size_t)snap * (size_t)g.S + sidx];
+                if (live && sidx < g.K) v = L::one(src + ((size_t)snap * (size_t)g.S + sidx), g.scale);
                 step(v.x, v.y);
             }
         }
@@ -411,7 +456,7 @@ static int cov_waves_per_cu(int n_ch)
 }
 
 // the read-once two-kernel path (see cov_piece_kernel)
-template <int TN> static void launch_pieces(const CovArgs &g, hipStream_t st)
+template <class L, int TN> static void launch_pieces(const CovArgs &g, hipStream_t st)
 {
     const int waves_per_block = 4;
     int blocks = (g.n_steps + waves_per_block - 1) / waves_per_block;
@@ -420,14 +465,14 @@ template <int TN> static void launch_pieces(const CovArgs &g, hipStream_t st)
         if (blocks > cap) blocks = cap;
     }
     constexpr int UN = (TN <= 6) ? 4 : 2;
-    hipLaunchKernelGGL((cov_piece_kernel<TN, UN, true>), dim3(blocks), dim3(waves_per_block * kWave), 0, st, g);
+    hipLaunchKernelGGL((cov_piece_kernel<L, TN, UN, true>), dim3(blocks), dim3(waves_per_block * kWave), 0, st, g);
     const long long total = (long long)g.n_out * g.n_ch * g.n_ch;
     hipLaunchKernelGGL(cov_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g);
 }
 
-template <int TN> static void launch_wave(const CovArgs &g, bool vec2, hipStream_t st)
+template <class L, int TN> static void launch_wave(const CovArgs &g, bool vec2, hipStream_t st)
 {
-    if (g.pieces) { launch_pieces<TN>(g, st); return; }
+    if (g.pieces) { launch_pieces<L, TN>(g, st); return; }
     const int waves_per_block = 4;
     int blocks = (g.n_out + waves_per_block - 1) / waves_per_block;
     if (cov_waves_per_cu(TN) > 0) {
@@ -436,14 +481,14 @@ template <int TN> static void launch_wave(const CovArgs &g, bool vec2, hipStream
     }
     dim3 grid(blocks), block(waves_per_block * kWave);
     // UN*TN 16-byte loads in flight per wave (UN = 1, 2, 8 measured within 3 % of UN = 4 at N = 4; N = 6: 44 us with
-    // UN = 4 against 55 with 2; N = 7: 68 us with 2 against 74 with 1)
+    // UN = 4 against 55 with 2; N = 7: 68 us with 2 against 74 with 1); sc16: UN 8-byte loads, see Sc16Samples
     constexpr int UN = (TN <= 6) ? 4 : 2;
     if (!vec2) {
-        hipLaunchKernelGGL((cov_wave_kernel<TN, false, 1, false>), grid, block, 0, st, g);
+        hipLaunchKernelGGL((cov_wave_kernel<L, TN, false, 1, false>), grid, block, 0, st, g);
         return;
     }
     // read-once stream: non-temporal loads (+19 % on MI355X against the default cache policy)
-    hipLaunchKernelGGL((cov_wave_kernel<TN, true, UN, true>), grid, block, 0, st, g);
+    hipLaunchKernelGGL((cov_wave_kernel<L, TN, true, UN, true>), grid, block, 0, st, g);
 }
 
 // Launches K1 on `st`.  d_in: N device pointers.  Returns DOA_OK / error.
@@ -456,18 +501,50 @@ size_t autocorrelate_workspace_bytes(int N, int K, int ovl, int n_out)
     return (size_t)(n_out + K / S) * 2 * N * N * sizeof(float2);
 }
 
+template <class L> static void launch_routes(const CovArgs &g, bool vec2, hipStream_t st)
+{
+    switch (g.n_ch) {
+    case 1: launch_wave<L, 1>(g, vec2, st); break;
+    case 2: launch_wave<L, 2>(g, vec2, st); break;
+    case 3: launch_wave<L, 3>(g, vec2, st); break;
+    case 4: launch_wave<L, 4>(g, vec2, st); break;
+    case 5: launch_wave<L, 5>(g, vec2, st); break;
+    case 6: launch_wave<L, 6>(g, vec2, st); break;
+    case 7: launch_wave<L, 7>(g, vec2, st); break;
+    case 8: launch_wave<L, 8>(g, vec2, st); break;
+    default: {
+        int blocks = (g.n_out + 3) / 4;
+        const int mfma_wpc = DOA_LAB_ENV_INT("DOA_COV_MFMA_WAVES_PER_CU", 16);
+        if (blocks > cu_count() * mfma_wpc / 4) blocks = cu_count() * mfma_wpc / 4;        // <= 16 waves per CU, grid-stride beyond
+        constexpr int UN = 4;                          // 4 wave-iterations (64 samples) of loads in flight
+        if (vec2) hipLaunchKernelGGL((cov_mfma_kernel<L, true, UN>), dim3(blocks), dim3(256), 0, st, g);
+        else      hipLaunchKernelGGL((cov_mfma_kernel<L, false, UN>), dim3(blocks), dim3(256), 0, st, g);
+        if (g.avg == 1) {
+            const int nn = g.n_ch * g.n_ch, half = (nn + 1) / 2;
+            const long long total = (long long)g.n_out * half;
+            hipLaunchKernelGGL(cov_fb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g.out, nn,
+                               (long long)g.n_out, g.fb_hk);
+        }
+    }
+    }
+}
+
 int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *const *d_in, void *d_out,
-                         hipStream_t st, const void *d_gain_outer, void *d_workspace)
+                         hipStream_t st, const void *d_gain_outer, void *d_workspace, int format, float scale)
 {
     if (n_out <= 0) return DOA_OK;
     CovArgs g;
     memset(&g, 0, sizeof g);
+    const bool sc16 = (format == DOA_SAMPLE_SC16);
+    const int sb = sc16 ? 4 : 8;                   // bytes per sample
+    // the route rule is the same in both formats: every stream aligned to one sample is required, every stream aligned to
+    // two samples with S even takes the pair loads (and, with overlap, the read-once path)
     bool vec2 = ((K - ovl) % 2 == 0);
     for (int k = 0; k < N; k++) {
-        g.in[k] = static_cast<const float2 *>(d_in[k]);
+        g.in[k] = d_in[k];
         if (!d_in[k]) { set_error("autocorrelate: input stream %d is NULL", k); return DOA_ERR_INVALID_ARG; }
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % 8) { set_error("autocorrelate: input stream %d is not 8-byte aligned", k); return DOA_ERR_INVALID_ARG; }
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % 16) vec2 = false;
+        if (reinterpret_cast<uintptr_t>(d_in[k]) % sb) { set_error("autocorrelate: input stream %d is not %d-byte aligned", k, sb); return DOA_ERR_INVALID_ARG; }
+        if (reinterpret_cast<uintptr_t>(d_in[k]) % (2 * sb)) vec2 = false;
     }
     for (int k = N; k < DOA_MAX_ANT_ELE; k++) g.in[k] = g.in[0];
     g.out = static_cast<float2 *>(d_out);
@@ -475,34 +552,31 @@ int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *
     g.inv_k = (float)(1.0 / K);
     g.fb_hk = (float)(0.5 / K);
     g.gain = static_cast<const float2 *>(d_gain_outer);
+    g.scale = sc16 ? scale : 1.0f;
     if (d_workspace && vec2 && autocorrelate_workspace_bytes(N, K, ovl, n_out) > 0) {
         g.pieces = static_cast<float2 *>(d_workspace);
         g.q = K / g.S; g.r = K % g.S; g.n_steps = n_out + g.q;
     }
-    switch (N) {
-    case 1: launch_wave<1>(g, vec2, st); break;
-    case 2: launch_wave<2>(g, vec2, st); break;
-    case 3: launch_wave<3>(g, vec2, st); break;
-    case 4: launch_wave<4>(g, vec2, st); break;
-    case 5: launch_wave<5>(g, vec2, st); break;
-    case 6: launch_wave<6>(g, vec2, st); break;
-    case 7: launch_wave<7>(g, vec2, st); break;
-    case 8: launch_wave<8>(g, vec2, st); break;
-    default: {
-        int blocks = (n_out + 3) / 4;
-        const int mfma_wpc = DOA_LAB_ENV_INT("DOA_COV_MFMA_WAVES_PER_CU", 16);
-        if (blocks > cu_count() * mfma_wpc / 4) blocks = cu_count() * mfma_wpc / 4;        // <= 16 waves per CU, grid-stride beyond
-        if (vec2) hipLaunchKernelGGL(cov_mfma_kernel<true>, dim3(blocks), dim3(256), 0, st, g);
-        else      hipLaunchKernelGGL(cov_mfma_kernel<false>, dim3(blocks), dim3(256), 0, st, g);
-        if (avg == 1) {
-            const int nn = N * N, half = (nn + 1) / 2;
-            const long long total = (long long)n_out * half;
-            hipLaunchKernelGGL(cov_fb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g.out, nn,
-                               (long long)n_out, g.fb_hk);
-        }
-    }
-    }
+    if (sc16) launch_routes<Sc16Samples>(g, vec2, st);
+    else      launch_routes<Fc32Samples>(g, vec2, st);
     DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+int check_input_format(const char *what, int format, float scale)
+{
+    if (format != DOA_SAMPLE_FC32 && format != DOA_SAMPLE_SC16) {
+        set_error("%s_set_input_format: unknown format %d (DOA_SAMPLE_FC32 = 0, DOA_SAMPLE_SC16 = 1)", what, format);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(scale) || !(scale > 0.0f)) {
+        set_error("%s_set_input_format: scale must be finite and > 0 (got %g)", what, (double)scale);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (format == DOA_SAMPLE_FC32 && scale != 1.0f) {
+        set_error("%s_set_input_format: fc32 samples are not rescaled (scale must be 1.0, got %g)", what, (double)scale);
+        return DOA_ERR_INVALID_ARG;
+    }
     return DOA_OK;
 }
 
@@ -517,6 +591,8 @@ struct doa_autocorrelate {
     hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out, d_gain, d_work;
     bool has_gain = false;
+    int format = DOA_SAMPLE_FC32;       // doa_autocorrelate_set_input_format
+    float scale = 1.0f;
 };
 
 extern "C" {
@@ -579,6 +655,15 @@ int doa_autocorrelate_fuse_antenna_correction(doa_autocorrelate_t *h, const floa
     return DOA_OK;
 }
 
+int doa_autocorrelate_set_input_format(doa_autocorrelate_t *h, int format, float scale)
+{
+    doa::clear_error();
+    if (!h) { doa::set_error("autocorrelate_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
+    if (const int rc = doa::check_input_format("autocorrelate", format, scale); rc != DOA_OK) return rc;
+    h->format = format; h->scale = scale;
+    return DOA_OK;
+}
+
 int doa_autocorrelate_history(const doa_autocorrelate_t *h) { return h ? h->overlap + 1 : DOA_ERR_INVALID_ARG; }
 
 int doa_autocorrelate_forecast(const doa_autocorrelate_t *h, int noutput_items)
@@ -608,7 +693,7 @@ int doa_autocorrelate_work_dev(doa_autocorrelate_t *h, int noutput_items, const 
     if (rc != DOA_OK) return rc;
     rc = doa::launch_autocorrelate(h->inputs, h->snapshot, h->overlap, h->avg, noutput_items, d_input_items,
                                    d_output_items0, static_cast<hipStream_t>(hip_stream),
-                                   h->has_gain ? h->d_gain.p : nullptr, ws ? h->d_work.p : nullptr);
+                                   h->has_gain ? h->d_gain.p : nullptr, ws ? h->d_work.p : nullptr, h->format, h->scale);
     return rc == DOA_OK ? noutput_items : rc;
 }
 
@@ -624,9 +709,10 @@ int doa_autocorrelate_work(doa_autocorrelate_t *h, int noutput_items, const void
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const int N = h->inputs;
     const size_t span = (size_t)doa_autocorrelate_input_span(h, noutput_items);
+    const size_t sb = doa::sample_bytes(h->format);
     // distance between the device copies of the streams: 16-B aligned, staggered against the 8 KiB aliasing period
-    const size_t span_al = doa::stream_stride_bytes(span * sizeof(float2)) / sizeof(float2);
-    int rc = h->d_in.reserve(span_al * N * sizeof(float2));
+    const size_t stride = doa::stream_stride_bytes(span * sb);
+    int rc = h->d_in.reserve(stride * N);
     if (rc != DOA_OK) return rc;
     const size_t out_bytes = (size_t)noutput_items * N * N * sizeof(float2);
     rc = h->d_out.reserve(out_bytes);
@@ -634,15 +720,15 @@ int doa_autocorrelate_work(doa_autocorrelate_t *h, int noutput_items, const void
     const void *d_ptrs[DOA_MAX_ANT_ELE];
     for (int k = 0; k < N; k++) {
         if (!input_items[k]) { doa::set_error("autocorrelate_work: input_items[%d] is NULL", k); return DOA_ERR_INVALID_ARG; }
-        float2 *dst = h->d_in.as<float2>() + k * span_al;
-        DOA_HIP_TRY(hipMemcpyAsync(dst, input_items[k], span * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+        char *dst = h->d_in.as<char>() + k * stride;
+        DOA_HIP_TRY(hipMemcpyAsync(dst, input_items[k], span * sb, hipMemcpyHostToDevice, h->stream));
         d_ptrs[k] = dst;
     }
     const size_t ws = doa::autocorrelate_workspace_bytes(N, h->snapshot, h->overlap, noutput_items);
     if (ws) rc = h->d_work.reserve(ws);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_autocorrelate(N, h->snapshot, h->overlap, h->avg, noutput_items, d_ptrs, h->d_out.p, h->stream,
-                                   h->has_gain ? h->d_gain.p : nullptr, ws ? h->d_work.p : nullptr);
+                                   h->has_gain ? h->d_gain.p : nullptr, ws ? h->d_work.p : nullptr, h->format, h->scale);
     if (rc != DOA_OK) return rc;
     DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
     DOA_HIP_TRY(hipStreamSynchronize(h->stream));

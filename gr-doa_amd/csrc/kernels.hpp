@@ -7,8 +7,13 @@ namespace doa {
 // K1  (autocorrelate.hip)
 // d_gain_outer: optional N*N float2 table w[a + b*N] = g_a conj(g_b) (fused antenna correction), or NULL
 size_t autocorrelate_workspace_bytes(int N, int K, int ovl, int n_out);
+// format / scale: DOA_SAMPLE_FC32 (scale unused) or DOA_SAMPLE_SC16 (widened in registers as __fmul_rn((float)q, scale))
 int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *const *d_in, void *d_out,
-                         hipStream_t st, const void *d_gain_outer = nullptr, void *d_workspace = nullptr);
+                         hipStream_t st, const void *d_gain_outer = nullptr, void *d_workspace = nullptr,
+                         int format = DOA_SAMPLE_FC32, float scale = 1.0f);
+// validation shared by the three doa_*_set_input_format entries (DOA_OK, or DOA_ERR_INVALID_ARG with the error set)
+int check_input_format(const char *what, int format, float scale);
+inline size_t sample_bytes(int format) { return format == DOA_SAMPLE_SC16 ? 4 : 8; }
 
 // Host-built tables of MUSIC_lin_array (music.hip): z_i = exp(j*psi_i), psi_i = k_i * d with
 // k_i = float(-2*pi*cos(theta_i)) on the reference's float-accumulated theta grid.

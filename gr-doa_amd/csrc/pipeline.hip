@@ -29,6 +29,8 @@ struct doa_music_pipeline {
     doa::PeakTables peaks;
     doa::DevBuf d_cov, d_coef, d_cheb, d_spec, d_scratch, d_gain;
     bool has_gain = false;
+    int format = DOA_SAMPLE_FC32;   // doa_music_pipeline_set_input_format
+    float scale = 1.0f;
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     doa::DevBuf d_in[2], d_res;
@@ -56,7 +58,8 @@ struct PipeWs {
 static int run_k1(doa_music_pipeline *h, int n, const void *const *d_in, void *cov, const PipeWs &ws, hipStream_t st)
 {
     if (~h->stages & 1u) return DOA_OK;         // doa_music_pipeline_set_stages (profiling aid; all stages in production)
-    return doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_in, cov, st, h->has_gain ? h->d_gain.p : nullptr, ws.work);
+    return doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_in, cov, st, h->has_gain ? h->d_gain.p : nullptr, ws.work,
+                                     h->format, h->scale);
 }
 static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, void *mx, void *am, const PipeWs &ws, hipStream_t st)
 {
@@ -179,6 +182,15 @@ int doa_music_pipeline_fuse_antenna_correction(doa_music_pipeline_t *h, const fl
     if (rc != DOA_OK) return rc;
     DOA_HIP_TRY(hipMemcpy(h->d_gain.p, w, sizeof(float2) * N * N, hipMemcpyHostToDevice));
     h->has_gain = true;
+    return DOA_OK;
+}
+
+int doa_music_pipeline_set_input_format(doa_music_pipeline_t *h, int format, float scale)
+{
+    doa::clear_error();
+    if (!h) { doa::set_error("music_pipeline_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
+    if (const int rc = doa::check_input_format("music_pipeline", format, scale); rc != DOA_OK) return rc;
+    h->format = format; h->scale = scale;
     return DOA_OK;
 }
 
@@ -327,6 +339,7 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     if (const int src = doa::ensure_stream_pair(h->hst); src != DOA_OK) return src;
     const size_t nonoverlap = (size_t)(h->K - h->ovl);
+    const size_t sb = doa::sample_bytes(h->format);     // bytes per input sample: 8 (fc32) or 4 (sc16)
     // Scheduler-sized calls (a GNU Radio work() hands over a few to a few hundred items): the fixed costs are what
     // counts -- N pageable host-to-device copies, up to four copies back and two stream synchronisations.  Below
     // kSmallCallBytes of input the window of every stream is packed into ONE page-locked staging buffer (the same
@@ -336,8 +349,8 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
     {
         static const size_t kSmallCallBytes = [] { const char *e = getenv("DOA_PIPE_SMALL_CALL_KB"); return (size_t)(e ? atoi(e) : 2048) << 10; }();
         const size_t span = (size_t)(noutput_items - 1) * nonoverlap + h->K;
-        const size_t span_al = (span + 1) & ~(size_t)1;
-        const size_t in_bytes = span_al * N * sizeof(float2);
+        const size_t span_al = (span + 1) & ~(size_t)1;       // streams two samples apart: pair-load aligned
+        const size_t in_bytes = span_al * N * sb;
         const size_t n = (size_t)noutput_items;
         // sections of the result block [max | argmax | cov | spectrum], each on a 256-byte boundary (the scan kernels'
         // 16-byte stores need aligned spectrum rows)
@@ -359,8 +372,8 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
             char *hs = h->h_stage.as<char>();
             const void *d_ptrs[DOA_MAX_ANT_ELE];
             for (int k = 0; k < N; k++) {
-                memcpy(hs + (size_t)k * span_al * sizeof(float2), input_items[k], span * sizeof(float2));
-                d_ptrs[k] = h->d_in[0].as<float2>() + (size_t)k * span_al;
+                memcpy(hs + (size_t)k * span_al * sb, input_items[k], span * sb);
+                d_ptrs[k] = h->d_in[0].as<char>() + (size_t)k * span_al * sb;
             }
             // From the upload on, every exit synchronises the stream first: a copy still reading the staging buffer
             // would race the next call's memcpy into it.
@@ -393,14 +406,14 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
     // Chunks of ~32 MiB of new samples alternate over two streams: while one chunk's results travel back
     // the next chunk's samples travel in (PCIe is full duplex; the kernels themselves are ~1 % of a
     // chunk's transfer time).  The overlap needs page-locked caller buffers; pageable ones still work.
-    size_t chunk = ((size_t)32 << 20) / (nonoverlap * N * sizeof(float2));
+    size_t chunk = ((size_t)32 << 20) / (nonoverlap * N * sb);
     chunk = chunk < 1 ? 1 : (chunk > (size_t)noutput_items ? (size_t)noutput_items : chunk);
     const size_t span_max = (chunk - 1) * nonoverlap + h->K;
     // distance between the device copies of the streams: 16-B aligned and staggered against the 8 KiB aliasing period
-    const size_t span_al = doa::stream_stride_bytes(span_max * sizeof(float2)) / sizeof(float2);
+    const size_t stride = doa::stream_stride_bytes(span_max * sb);
     int rc = h->d_res.reserve((size_t)h->max_batch * M * 2 * sizeof(float));
     for (auto &b : h->d_in)
-        if (rc == DOA_OK) rc = b.reserve(span_al * N * sizeof(float2));
+        if (rc == DOA_OK) rc = b.reserve(stride * N);
     if (const size_t ws = doa::autocorrelate_workspace_bytes(N, h->K, h->ovl, (int)chunk); ws && rc == DOA_OK)
         rc = h->d_work[1].reserve(ws);                 // lane 0 uses the workspace create() sized for max_batch
     if (rc != DOA_OK) return rc;
@@ -413,9 +426,9 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
         const size_t span = (n - 1) * nonoverlap + h->K;
         const void *d_ptrs[DOA_MAX_ANT_ELE];
         for (int k = 0; k < N; k++) {
-            float2 *dst = h->d_in[lane].as<float2>() + k * span_al;
-            const float2 *src = static_cast<const float2 *>(input_items[k]) + s0 * nonoverlap;
-            DOA_HIP_TRY(hipMemcpyAsync(dst, src, span * sizeof(float2), hipMemcpyHostToDevice, st));
+            char *dst = h->d_in[lane].as<char>() + k * stride;
+            const char *src = static_cast<const char *>(input_items[k]) + s0 * nonoverlap * sb;
+            DOA_HIP_TRY(hipMemcpyAsync(dst, src, span * sb, hipMemcpyHostToDevice, st));
             d_ptrs[k] = dst;
         }
         if (h->fail_chunk == chunk_index) { doa::set_error("music_pipeline_work: injected failure in chunk %d", chunk_index); return DOA_ERR_HIP; }

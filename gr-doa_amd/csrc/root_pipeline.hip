@@ -19,6 +19,8 @@ struct doa_root_pipeline {
     int device = 0;
     doa::DevBuf d_cov, d_coef, d_status, d_gain;
     bool has_gain = false;
+    int format = DOA_SAMPLE_FC32;   // doa_root_pipeline_set_input_format
+    float scale = 1.0f;
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     doa::DevBuf d_in[2], d_res;
@@ -40,7 +42,8 @@ size_t coef_bytes(const doa_root_pipeline *h, size_t items) { return items * doa
 // K1 -> EVD -> roots for n items on `st`
 int run_chain(doa_root_pipeline *h, int n, const void *const *d_in, void *cov, void *angles, const RootWs &ws, hipStream_t st)
 {
-    int rc = doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_in, cov, st, h->has_gain ? h->d_gain.p : nullptr, ws.work);
+    int rc = doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_in, cov, st, h->has_gain ? h->d_gain.p : nullptr, ws.work,
+                                       h->format, h->scale);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_music_evd(h->N, h->M, n, cov, nullptr, ws.coef, nullptr, h->bits, st);
     if (rc != DOA_OK) return rc;
@@ -128,6 +131,15 @@ int doa_root_pipeline_fuse_antenna_correction(doa_root_pipeline_t *h, const floa
     if (rc != DOA_OK) return rc;
     DOA_HIP_TRY(hipMemcpy(h->d_gain.p, w, sizeof(float2) * N * N, hipMemcpyHostToDevice));
     h->has_gain = true;
+    return DOA_OK;
+}
+
+int doa_root_pipeline_set_input_format(doa_root_pipeline_t *h, int format, float scale)
+{
+    doa::clear_error();
+    if (!h) { doa::set_error("root_pipeline_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
+    if (const int rc = doa::check_input_format("root_pipeline", format, scale); rc != DOA_OK) return rc;
+    h->format = format; h->scale = scale;
     return DOA_OK;
 }
 
@@ -262,6 +274,7 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
     if (const int src = doa::ensure_stream_pair(h->hst); src != DOA_OK) return src;
     const size_t nonoverlap = (size_t)(h->K - h->ovl);
     const size_t n_all = (size_t)noutput_items;
+    const size_t sb = doa::sample_bytes(h->format);     // bytes per input sample: 8 (fc32) or 4 (sc16)
     // result block on the device: [angles | status] per call, sections 256-byte aligned
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t ang_b = n_all * M * sizeof(float), st_b = n_all * sizeof(int);
@@ -270,8 +283,8 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
     {
         static const size_t kSmallCallBytes = [] { const char *e = getenv("DOA_PIPE_SMALL_CALL_KB"); return (size_t)(e ? atoi(e) : 2048) << 10; }();
         const size_t span = (n_all - 1) * nonoverlap + h->K;
-        const size_t span_al = (span + 1) & ~(size_t)1;
-        const size_t in_bytes = span_al * N * sizeof(float2);
+        const size_t span_al = (span + 1) & ~(size_t)1;       // streams two samples apart: pair-load aligned
+        const size_t in_bytes = span_al * N * sb;
         const size_t cov_b = cov_out ? n_all * N * N * sizeof(float2) : 0;
         const size_t off_st = up(ang_b), off_cov = off_st + up(st_b);
         const size_t out_bytes = off_cov + cov_b;
@@ -284,8 +297,8 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
             char *hs = h->h_stage.as<char>();
             const void *d_ptrs[DOA_MAX_ANT_ELE];
             for (int k = 0; k < N; k++) {
-                memcpy(hs + (size_t)k * span_al * sizeof(float2), input_items[k], span * sizeof(float2));
-                d_ptrs[k] = h->d_in[0].as<float2>() + (size_t)k * span_al;
+                memcpy(hs + (size_t)k * span_al * sb, input_items[k], span * sb);
+                d_ptrs[k] = h->d_in[0].as<char>() + (size_t)k * span_al * sb;
             }
             // from the upload on, every exit synchronises the stream first (a copy still reading the staging buffer would
             // race the next call's memcpy into it)
@@ -311,14 +324,14 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
         }
     }
     // chunks of ~32 MiB of new samples alternating over two streams (as music_pipeline)
-    size_t chunk = ((size_t)32 << 20) / (nonoverlap * N * sizeof(float2));
+    size_t chunk = ((size_t)32 << 20) / (nonoverlap * N * sb);
     chunk = chunk < 1 ? 1 : (chunk > n_all ? n_all : chunk);
     const size_t span_max = (chunk - 1) * nonoverlap + h->K;
-    const size_t span_al = doa::stream_stride_bytes(span_max * sizeof(float2)) / sizeof(float2);
+    const size_t stride = doa::stream_stride_bytes(span_max * sb);
     int rc = h->d_res.reserve(up(ang_b) + st_b);
     if (rc == DOA_OK) rc = h->h_status.reserve(st_b);
     for (auto &b : h->d_in)
-        if (rc == DOA_OK) rc = b.reserve(span_al * N * sizeof(float2));
+        if (rc == DOA_OK) rc = b.reserve(stride * N);
     if (const size_t ws = doa::autocorrelate_workspace_bytes(N, h->K, h->ovl, (int)chunk); ws && rc == DOA_OK)
         rc = h->d_work[1].reserve(ws);
     if (rc != DOA_OK) return rc;
@@ -329,9 +342,9 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
         const size_t span = (n - 1) * nonoverlap + h->K;
         const void *d_ptrs[DOA_MAX_ANT_ELE];
         for (int k = 0; k < N; k++) {
-            float2 *dst = h->d_in[lane].as<float2>() + k * span_al;
-            const float2 *src = static_cast<const float2 *>(input_items[k]) + s0 * nonoverlap;
-            DOA_HIP_TRY(hipMemcpyAsync(dst, src, span * sizeof(float2), hipMemcpyHostToDevice, st));
+            char *dst = h->d_in[lane].as<char>() + k * stride;
+            const char *src = static_cast<const char *>(input_items[k]) + s0 * nonoverlap * sb;
+            DOA_HIP_TRY(hipMemcpyAsync(dst, src, span * sb, hipMemcpyHostToDevice, st));
             d_ptrs[k] = dst;
         }
         if (h->fail_chunk == chunk_index) { doa::set_error("root_pipeline_work: injected failure in chunk %d", chunk_index); return DOA_ERR_HIP; }

@@ -134,6 +134,9 @@ SIGNATURES = {
     "doa_root_pipeline_set_lane_streams": (C.c_int, [_vp, C.c_int, _vpp]),
     "doa_root_pipeline_set_internal_precision": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_work": (C.c_int, [_vp, C.c_int, _vpp, _vp, _vp]),
+    "doa_autocorrelate_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "doa_music_pipeline_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "doa_root_pipeline_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_root_pipeline_inject_failure": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_lanes_idle": (C.c_int, [_vp]),

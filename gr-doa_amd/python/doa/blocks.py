@@ -25,6 +25,11 @@ from ._lib import lib, check, check_handle, ptr_array
 
 _C64 = np.complex64
 _F32 = np.float32
+_I16 = np.int16
+
+# input sample formats of the stream-input blocks (DOA_SAMPLE_FC32 / DOA_SAMPLE_SC16, include/doa_hip.h)
+SC16_DEFAULT_SCALE = 2.0 ** -15
+_FORMATS = {"fc32": 0, "sc16": 1}
 
 
 def _vp(a: np.ndarray) -> C.c_void_p:
@@ -71,11 +76,50 @@ class _Block:
         check(type(self)._set_precision(self._h, int(bits)))
 
 
-class autocorrelate(_Block):
+class _StreamInput:
+    """Input sample format of the blocks that take the antenna streams (autocorrelate and the two pipelines):
+    "fc32" (complex64, the default) or "sc16" (complex int16, int16 arrays of shape [n, 2] or flat 2n, real first),
+    widened on the device as float32(q) * float32(scale) (doa_*_set_input_format, include/doa_hip.h)."""
+
+    _set_format = None
+    input_format, scale = "fc32", 1.0
+
+    def set_input_format(self, fmt, scale=None) -> None:
+        """fmt "fc32" or "sc16"; scale None = 2**-15 for sc16 and 1.0 for fc32.  Takes effect from the next work call."""
+        if fmt not in _FORMATS:
+            raise ValueError(f"unknown input format {fmt!r} (fc32 or sc16)")
+        s = (SC16_DEFAULT_SCALE if fmt == "sc16" else 1.0) if scale is None else float(scale)
+        check(type(self)._set_format(self._h, _FORMATS[fmt], s))
+        self.input_format, self.scale = fmt, s
+
+    def _samples(self, a):
+        """A stream as the work entries index it: complex64 [n] or, for sc16, int16 [n, 2]."""
+        if self.input_format == "sc16":
+            a = np.asarray(a)
+            if a.dtype != _I16:
+                raise TypeError(f"sc16 streams are int16 arrays, got {a.dtype}")
+            return a.reshape(-1, 2)
+        return a
+
+    def _host_streams(self, input_items, span):
+        arrs = []
+        for k in range(self.inputs):
+            if self.input_format == "sc16":
+                a = np.ascontiguousarray(self._samples(input_items[k]))
+            else:
+                a = np.ascontiguousarray(input_items[k], dtype=_C64)
+            if a.shape[0] < span:
+                raise ValueError(f"input {k}: {a.shape[0]} samples, need {span}")
+            arrs.append(a)
+        return arrs
+
+
+class autocorrelate(_StreamInput, _Block):
     """doa.autocorrelate(inputs, snapshot_size, overlap_size, avg_method) — gr::block with
     history overlap_size+1 (reference lib/autocorrelate_impl.cc:47-65)."""
 
     _destroy = staticmethod(lib.doa_autocorrelate_destroy)
+    _set_format = staticmethod(lib.doa_autocorrelate_set_input_format)
 
     def __init__(self, inputs, snapshot_size, overlap_size, avg_method):
         super().__init__()
@@ -102,13 +146,7 @@ class autocorrelate(_Block):
         (at least input_span(noutput_items) long); output_items[0]: [>=n, N*N] complex64.
         Returns (items produced, items consumed per input) — the caller applies consume_each."""
         n = int(noutput_items)
-        span = self.input_span(n)
-        arrs = []
-        for k in range(self.inputs):
-            a = np.ascontiguousarray(input_items[k], dtype=_C64)
-            if a.shape[0] < span:
-                raise ValueError(f"input {k}: {a.shape[0]} samples, need {span}")
-            arrs.append(a)
+        arrs = self._host_streams(input_items, self.input_span(n))
         out = output_items[0]
         assert out.dtype == _C64 and out.flags.c_contiguous and out.size >= n * self.inputs ** 2
         produced = check(lib.doa_autocorrelate_work(self._h, n, ptr_array([a.ctypes.data for a in arrs]),
@@ -123,6 +161,17 @@ class autocorrelate(_Block):
         """Fold a doa.antenna_correction block (or an array of complex gains, or None to undo) into
         this block: equivalent to wiring the correction block in front of it."""
         _fuse(lib.doa_autocorrelate_fuse_antenna_correction, self._h, correction, self.inputs)
+
+
+class autocorrelate_sc16(autocorrelate):
+    """doa.autocorrelate_sc16(inputs, snapshot_size, overlap_size, avg_method, scale=2**-15) — autocorrelate on complex
+    int16 streams (GNU Radio's sc16 items, 4 bytes: int16 real, int16 imaginary), widened on the device as
+    float32(q) * float32(scale); outputs and scheduling as autocorrelate.  Not a block of the reference."""
+
+    def __init__(self, inputs, snapshot_size, overlap_size, avg_method, scale=SC16_DEFAULT_SCALE):
+        super().__init__(inputs, snapshot_size, overlap_size, avg_method)
+        self.set_input_format("sc16", scale)
+        self.in_sig = [(_I16, 2)] * self.inputs
 
 
 def _fuse(fn, handle, correction, n):
@@ -362,13 +411,14 @@ class calibrate_lin_array(_Block):
                                                           C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
 
 
-class music_pipeline(_Block):
+class music_pipeline(_StreamInput, _Block):
     """autocorrelate -> MUSIC_lin_array -> find_local_max(num_targets, pspectrum_len, 0, 180) on
     device-resident streams (the wiring of apps/run_MUSIC_lin_array_simulation.grc); the batch
     entry point the benchmark drives.  Not a block of the reference."""
 
     _destroy = staticmethod(lib.doa_music_pipeline_destroy)
     _set_precision = staticmethod(lib.doa_music_pipeline_set_internal_precision)
+    _set_format = staticmethod(lib.doa_music_pipeline_set_input_format)
 
     def __init__(self, inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets,
                  pspectrum_len, max_batch=4096):
@@ -400,7 +450,7 @@ class music_pipeline(_Block):
             am = output_items[0][done:done + k]
             mx = output_items[1][done:done + k] if len(output_items) > 1 else np.empty((k, self.num_targets), _F32)
             sp = output_items[2][done:done + k] if len(output_items) > 2 else None
-            done += self.work(k, [a[done * S:] for a in input_items], mx, am, spectrum_out=sp)
+            done += self.work(k, [self._samples(a)[done * S:] for a in input_items], mx, am, spectrum_out=sp)
         return done, self.forecast(done)
 
     def fuse_antenna_correction(self, correction) -> None:
@@ -464,13 +514,7 @@ class music_pipeline(_Block):
         its first history sample; max_out / argmax_out [>=n, M] float32; cov_out [>=n, N*N] complex64
         and spectrum_out [>=n, P] float32 are optional."""
         n = int(noutput_items)
-        span = self.input_span(n)
-        arrs = []
-        for k in range(self.inputs):
-            a = np.ascontiguousarray(input_items[k], dtype=_C64)
-            if a.shape[0] < span:
-                raise ValueError(f"input {k}: {a.shape[0]} samples, need {span}")
-            arrs.append(a)
+        arrs = self._host_streams(input_items, self.input_span(n))
         for o, dt, per in ((max_out, _F32, self.num_targets), (argmax_out, _F32, self.num_targets),
                            (cov_out, _C64, self.inputs ** 2), (spectrum_out, _F32, self.pspectrum_len)):
             if o is not None:
@@ -481,7 +525,19 @@ class music_pipeline(_Block):
             none if spectrum_out is None else _vp(spectrum_out), _vp(max_out), _vp(argmax_out)))
 
 
-class root_pipeline(_Block):
+class music_pipeline_sc16(music_pipeline):
+    """music_pipeline on complex int16 streams (sc16 items, widened on the device as float32(q) * float32(scale));
+    the host entries take int16 arrays [n, 2] (or flat 2n), the device entries pointers to int16 data.  Outputs are bit
+    for bit those of music_pipeline on the widened samples.  Not a block of the reference."""
+
+    def __init__(self, inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets, pspectrum_len,
+                 scale=SC16_DEFAULT_SCALE, max_batch=4096):
+        super().__init__(inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets, pspectrum_len, max_batch)
+        self.set_input_format("sc16", scale)
+        self.in_sig = [(_I16, 2)] * self.inputs
+
+
+class root_pipeline(_StreamInput, _Block):
     """autocorrelate -> rootMUSIC_linear_array on device-resident streams (the wiring of
     apps/run_RootMUSIC_lin_array_simulation.grc) as ONE handle: the Root-MUSIC branch of the hot path with the same entry
     points as music_pipeline (work_dev, work_dev_batches over the handle's lanes, detached form, host-buffer work).
@@ -489,6 +545,7 @@ class root_pipeline(_Block):
 
     _destroy = staticmethod(lib.doa_root_pipeline_destroy)
     _set_precision = staticmethod(lib.doa_root_pipeline_set_internal_precision)
+    _set_format = staticmethod(lib.doa_root_pipeline_set_input_format)
 
     def __init__(self, inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets, max_batch=4096):
         super().__init__()
@@ -517,7 +574,7 @@ class root_pipeline(_Block):
         S = self.snapshot_size - self.overlap_size
         while done < n:
             k = min(self.max_batch, n - done)
-            done += self.work(k, [a[done * S:] for a in input_items], output_items[0][done:done + k])
+            done += self.work(k, [self._samples(a)[done * S:] for a in input_items], output_items[0][done:done + k])
         return done, self.forecast(done)
 
     def fuse_antenna_correction(self, correction) -> None:
@@ -565,13 +622,7 @@ class root_pipeline(_Block):
         sample; angles_out [>=n, M] float32; cov_out [>=n, N*N] complex64 is optional.  Raises DoaError(DOA_ERR_NUMERIC) when
         an item has no root inside the unit circle (the outputs of the other items are valid)."""
         n = int(noutput_items)
-        span = self.input_span(n)
-        arrs = []
-        for k in range(self.inputs):
-            a = np.ascontiguousarray(input_items[k], dtype=_C64)
-            if a.shape[0] < span:
-                raise ValueError(f"input {k}: {a.shape[0]} samples, need {span}")
-            arrs.append(a)
+        arrs = self._host_streams(input_items, self.input_span(n))
         for o, dt, per in ((angles_out, _F32, self.num_targets), (cov_out, _C64, self.inputs ** 2)):
             if o is not None:
                 assert o.dtype == dt and o.flags.c_contiguous and o.size >= n * per
@@ -581,6 +632,16 @@ class root_pipeline(_Block):
 
 
 root_music_pipeline = root_pipeline      # the name of the C++ shell (gr::doa::root_music_pipeline) and of grc/doa_root_music_pipeline.xml
+
+
+class root_music_pipeline_sc16(root_pipeline):
+    """root_music_pipeline on complex int16 streams (as music_pipeline_sc16).  Not a block of the reference."""
+
+    def __init__(self, inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets,
+                 scale=SC16_DEFAULT_SCALE, max_batch=4096):
+        super().__init__(inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets, max_batch)
+        self.set_input_format("sc16", scale)
+        self.in_sig = [(_I16, 2)] * self.inputs
 
 
 class compass_mean(_Block):

@@ -113,20 +113,56 @@ def make_batch_streams_torch(num_ant_ele: int, snapshot_size: int, batch: int, n
 
 
 def stream_slab_torch(streams):
-    """Copies N equally long complex64 device tensors into ONE allocation at the distance the library recommends
-    (doa_stream_stride_bytes: streams whose addresses agree modulo 8 KiB share HBM channels; include/doa_hip.h) and
-    returns the N views.  The layout a device-resident producer should use for the streams it hands to
-    autocorrelate / music_pipeline.work_dev."""
+    """Copies N equally long complex64 (or sc16: int16 [n, 2]) device tensors into ONE allocation at the distance the
+    library recommends (doa_stream_stride_bytes: streams whose addresses agree modulo 8 KiB share HBM channels;
+    include/doa_hip.h) and returns the N views.  The layout a device-resident producer should use for the streams it hands
+    to autocorrelate / music_pipeline.work_dev."""
     import torch
     from ._lib import lib
 
-    n, nbytes = len(streams), streams[0].numel() * 8
+    n, nbytes = len(streams), streams[0].numel() * streams[0].element_size()
     stride = int(lib.doa_stream_stride_bytes(nbytes))
     slab = torch.empty(n * stride + 4096, dtype=torch.uint8, device=streams[0].device)
     off0 = (-slab.data_ptr()) % 4096
     out = []
     for k, s in enumerate(streams):
-        v = slab[off0 + k * stride: off0 + k * stride + nbytes].view(torch.complex64)
+        v = slab[off0 + k * stride: off0 + k * stride + nbytes].view(s.dtype).view(s.shape)
         v.copy_(s)
         out.append(v)
     return out
+
+
+def to_sc16(x, scale=2.0 ** -15):
+    """Complex samples -> sc16 (complex int16, GNU Radio / UHD "sc16"): q = rint(x / scale), half to even, saturated to
+    [-32768, 32767], as int16 [..., n, 2] (real first).  x: complex numpy array or torch tensor (or real [..., 2] pairs);
+    the division is done in float64."""
+    if _is_torch(x):
+        import torch
+        r = torch.view_as_real(x) if torch.is_complex(x) else x
+        q = torch.round(r.to(torch.float64) / float(scale))               # torch.round: half to even
+        return q.clamp(-32768, 32767).to(torch.int16)
+    x = np.asarray(x)
+    r = np.stack([x.real, x.imag], axis=-1) if np.iscomplexobj(x) else x
+    q = np.rint(r.astype(np.float64) / float(scale))                       # np.rint: half to even
+    return np.clip(q, -32768, 32767).astype(np.int16)
+
+
+def from_sc16(q, scale=2.0 ** -15):
+    """sc16 -> complex64, exactly as the library widens: re = float32(q_re) * float32(scale) (one float32 rounding), the
+    same for im.  q: int16 [..., n, 2] or flat [2n] (numpy or torch).  The sc16 entries of autocorrelate and the pipelines
+    are bit-identical to the fc32 entries on these samples."""
+    if _is_torch(q):
+        import torch
+        r = q.reshape(*q.shape[:-1], -1, 2) if (q.dim() == 1 or q.shape[-1] != 2) else q
+        w = r.to(torch.float32) * torch.tensor(float(np.float32(scale)), dtype=torch.float32, device=r.device)
+        return torch.complex(w[..., 0].contiguous(), w[..., 1].contiguous())
+    q = np.asarray(q, dtype=np.int16)
+    r = q.reshape(*q.shape[:-1], -1, 2) if (q.ndim == 1 or q.shape[-1] != 2) else q
+    w = r.astype(np.float32) * np.float32(scale)
+    out = np.empty(w.shape[:-1], np.complex64)
+    out.real, out.imag = w[..., 0], w[..., 1]
+    return out
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.startswith("torch")

@@ -13,17 +13,23 @@
 //                           as one gr::block over doa_music_pipeline_work
 //   root_music_pipeline     (not in the reference) autocorrelate -> rootMUSIC_linear_array wired as in
 //                           run_RootMUSIC_lin_array_simulation.grc, as one gr::block over doa_root_pipeline_work
+//   autocorrelate_sc16, music_pipeline_sc16, root_music_pipeline_sc16
+//                           (not in the reference) the same three blocks on complex int16 (sc16) streams: the same
+//                           classes with a 4-byte input item and the handle switched by doa_*_set_input_format
 // — and turn a failing ABI call into the behaviour a GNU Radio block has for it: constructors throw
 // std::runtime_error / std::invalid_argument (as antenna_correction_impl.cc:58-73 does), work()
 // returns WORK_DONE (-1) after logging, which stops the flowgraph.
 #include <doa/MUSIC_lin_array.h>
 #include <doa/antenna_correction.h>
 #include <doa/autocorrelate.h>
+#include <doa/autocorrelate_sc16.h>
 #include <doa/calibrate_lin_array.h>
 #include <doa/find_local_max.h>
 #include <doa/music_pipeline.h>
+#include <doa/music_pipeline_sc16.h>
 #include <doa/rootMUSIC_linear_array.h>
 #include <doa/root_music_pipeline.h>
+#include <doa/root_music_pipeline_sc16.h>
 
 #include <doa_hip.h>
 
@@ -80,21 +86,40 @@ void apply_scheduling_hints(gr::block *b, size_t largest_output_item_bytes)
     if (mult > 1) b->set_output_multiple(mult);
 }
 
+// Input item of the stream-input blocks: gr_complex (the reference's), or sc16 (two int16, 4 bytes) for the *_sc16 blocks,
+// whose handles are switched with doa_*_set_input_format before the first work() call.
+struct input_format {
+    int format = DOA_SAMPLE_FC32;
+    float scale = 1.0f;
+    size_t item_size() const { return format == DOA_SAMPLE_SC16 ? 2 * sizeof(int16_t) : sizeof(gr_complex); }
+};
+template <class H, class F> void apply_input_format(H *h, const input_format &f, F set, const char *what)
+{
+    if (h && f.format != DOA_SAMPLE_FC32 && set(h, f.format, f.scale) != DOA_OK)
+        throw std::invalid_argument(std::string(what) + ": " + doa_last_error());
+}
+
 // ------------------------------------------------------------------------------------------------
-class autocorrelate_hip : public autocorrelate
+template <class Iface> class autocorrelate_hip : public Iface
 {
     doa_autocorrelate_t *d_h;
     int d_nonoverlap;
 
 public:
-    autocorrelate_hip(int inputs, int snapshot_size, int overlap_size, int avg_method)
-        : gr::block("autocorrelate", gr::io_signature::make(inputs, inputs, sizeof(gr_complex)),
+    autocorrelate_hip(const char *name, int inputs, int snapshot_size, int overlap_size, int avg_method, input_format fmt = {})
+        : gr::block(name, gr::io_signature::make(inputs, inputs, (int)fmt.item_size()),
                     gr::io_signature::make(1, 1, sizeof(gr_complex) * inputs * inputs)),
           d_h(doa_autocorrelate_create(inputs, snapshot_size, overlap_size, avg_method)),
           d_nonoverlap(snapshot_size - overlap_size)
     {
         if (!d_h) throw_create("doa::autocorrelate");
-        set_history(doa_autocorrelate_history(d_h));          // overlap_size + 1
+        try {
+            apply_input_format(d_h, fmt, doa_autocorrelate_set_input_format, name);
+        } catch (...) {
+            doa_autocorrelate_destroy(d_h);
+            throw;
+        }
+        this->set_history(doa_autocorrelate_history(d_h));    // overlap_size + 1
         apply_scheduling_hints(this, sizeof(gr_complex) * inputs * inputs);
     }
     ~autocorrelate_hip() override { doa_autocorrelate_destroy(d_h); }
@@ -110,7 +135,7 @@ public:
     {
         const int produced = doa_autocorrelate_work(d_h, noutput_items, input_items.data(), output_items[0]);
         if (produced < 0) return work_failed("doa::autocorrelate", produced);
-        consume_each(d_nonoverlap * produced);
+        this->consume_each(d_nonoverlap * produced);
         return produced;
     }
 };
@@ -234,26 +259,33 @@ public:
 // ------------------------------------------------------------------------------------------------
 // autocorrelate -> MUSIC_lin_array -> find_local_max as one block over doa_music_pipeline_work: one upload, the
 // whole chain on the device, one download of the connected ports (see include/doa/music_pipeline.h)
-class music_pipeline_hip : public music_pipeline
+template <class Iface> class music_pipeline_hip : public Iface
 {
     static constexpr int kMaxBatch = 4096;
     doa_music_pipeline_t *d_h;
     int d_nonoverlap, d_M, d_P;
+    size_t d_in_item;                                     // bytes per input sample
     std::vector<float> d_max_scratch;                     // port 1 (peak values) when it is not connected
 
 public:
-    music_pipeline_hip(int inputs, int snapshot_size, int overlap_size, int avg_method, float norm_spacing,
-                       int num_targets, int pspectrum_len)
-        : gr::block("music_pipeline", gr::io_signature::make(inputs, inputs, sizeof(gr_complex)),
+    music_pipeline_hip(const char *name, int inputs, int snapshot_size, int overlap_size, int avg_method, float norm_spacing,
+                       int num_targets, int pspectrum_len, input_format fmt = {})
+        : gr::block(name, gr::io_signature::make(inputs, inputs, (int)fmt.item_size()),
                     gr::io_signature::makev(1, 3, std::vector<int>{(int)(num_targets * sizeof(float)),
                                                                    (int)(num_targets * sizeof(float)),
                                                                    (int)(pspectrum_len * sizeof(float))})),
           d_h(doa_music_pipeline_create(inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets,
                                         pspectrum_len, kMaxBatch)),
-          d_nonoverlap(snapshot_size - overlap_size), d_M(num_targets), d_P(pspectrum_len)
+          d_nonoverlap(snapshot_size - overlap_size), d_M(num_targets), d_P(pspectrum_len), d_in_item(fmt.item_size())
     {
         if (!d_h) throw_create("doa::music_pipeline");
-        set_history(overlap_size + 1);                        // as doa::autocorrelate (autocorrelate_impl.cc:56-57)
+        try {
+            apply_input_format(d_h, fmt, doa_music_pipeline_set_input_format, name);
+        } catch (...) {
+            doa_music_pipeline_destroy(d_h);
+            throw;
+        }
+        this->set_history(overlap_size + 1);                  // as doa::autocorrelate (autocorrelate_impl.cc:56-57)
         apply_scheduling_hints(this, (size_t)pspectrum_len * sizeof(float));
     }
     ~music_pipeline_hip() override { doa_music_pipeline_destroy(d_h); }
@@ -289,34 +321,42 @@ public:
         while (done < noutput_items) {                        // the handle's workspace holds kMaxBatch items
             const int n = noutput_items - done < kMaxBatch ? noutput_items - done : kMaxBatch;
             for (size_t k = 0; k < in.size(); k++)
-                in[k] = static_cast<const gr_complex *>(input_items[k]) + (size_t)done * d_nonoverlap;
+                in[k] = static_cast<const char *>(input_items[k]) + (size_t)done * d_nonoverlap * d_in_item;
             float *mv = output_items.size() > 1 ? maxv + (size_t)done * d_M : maxv;
             const int produced = doa_music_pipeline_work(d_h, n, in.data(), nullptr, spec ? spec + (size_t)done * d_P : nullptr,
                                                          mv, argmax + (size_t)done * d_M);
             if (produced < 0) return work_failed("doa::music_pipeline", produced);
             done += produced;
         }
-        consume_each(d_nonoverlap * done);                    // autocorrelate_impl.cc:114
+        this->consume_each(d_nonoverlap * done);              // autocorrelate_impl.cc:114
         return done;
     }
 };
 
 // ------------------------------------------------------------------------------------------------
-class root_music_pipeline_hip : public root_music_pipeline
+template <class Iface> class root_music_pipeline_hip : public Iface
 {
     static constexpr int kMaxBatch = 4096;
     doa_root_pipeline_t *d_h;
     int d_nonoverlap, d_M;
+    size_t d_in_item;                                     // bytes per input sample
 
 public:
-    root_music_pipeline_hip(int inputs, int snapshot_size, int overlap_size, int avg_method, float norm_spacing, int num_targets)
-        : gr::block("root_music_pipeline", gr::io_signature::make(inputs, inputs, sizeof(gr_complex)),
+    root_music_pipeline_hip(const char *name, int inputs, int snapshot_size, int overlap_size, int avg_method, float norm_spacing,
+                            int num_targets, input_format fmt = {})
+        : gr::block(name, gr::io_signature::make(inputs, inputs, (int)fmt.item_size()),
                     gr::io_signature::make(1, 1, num_targets * sizeof(float))),
           d_h(doa_root_pipeline_create(inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets, kMaxBatch)),
-          d_nonoverlap(snapshot_size - overlap_size), d_M(num_targets)
+          d_nonoverlap(snapshot_size - overlap_size), d_M(num_targets), d_in_item(fmt.item_size())
     {
         if (!d_h) throw_create("doa::root_music_pipeline");
-        set_history(overlap_size + 1);                        // as doa::autocorrelate (autocorrelate_impl.cc:56-57)
+        try {
+            apply_input_format(d_h, fmt, doa_root_pipeline_set_input_format, name);
+        } catch (...) {
+            doa_root_pipeline_destroy(d_h);
+            throw;
+        }
+        this->set_history(overlap_size + 1);                  // as doa::autocorrelate (autocorrelate_impl.cc:56-57)
         apply_scheduling_hints(this, (size_t)num_targets * sizeof(float));
     }
     ~root_music_pipeline_hip() override { doa_root_pipeline_destroy(d_h); }
@@ -345,14 +385,14 @@ public:
         while (done < noutput_items) {                        // the handle's workspace holds kMaxBatch items
             const int n = noutput_items - done < kMaxBatch ? noutput_items - done : kMaxBatch;
             for (size_t k = 0; k < in.size(); k++)
-                in[k] = static_cast<const gr_complex *>(input_items[k]) + (size_t)done * d_nonoverlap;
+                in[k] = static_cast<const char *>(input_items[k]) + (size_t)done * d_nonoverlap * d_in_item;
             // (an item without a root inside the unit circle: DOA_ERR_NUMERIC -- the reference's work() throws there -- stops
             // the flowgraph like any other failure)
             const int produced = doa_root_pipeline_work(d_h, n, in.data(), nullptr, aoa + (size_t)done * d_M);
             if (produced < 0) return work_failed("doa::root_music_pipeline", produced);
             done += produced;
         }
-        consume_each(d_nonoverlap * done);                    // autocorrelate_impl.cc:114
+        this->consume_each(d_nonoverlap * done);              // autocorrelate_impl.cc:114
         return done;
     }
 };
@@ -362,14 +402,29 @@ public:
 music_pipeline::sptr music_pipeline::make(int inputs, int snapshot_size, int overlap_size, int avg_method,
                                           float norm_spacing, int num_targets, int pspectrum_len)
 {
-    return gnuradio::get_initial_sptr(new music_pipeline_hip(inputs, snapshot_size, overlap_size, avg_method, norm_spacing,
-                                                             num_targets, pspectrum_len));
+    return gnuradio::get_initial_sptr(new music_pipeline_hip<music_pipeline>("music_pipeline", inputs, snapshot_size, overlap_size,
+                                                                             avg_method, norm_spacing, num_targets, pspectrum_len));
+}
+music_pipeline_sc16::sptr music_pipeline_sc16::make(int inputs, int snapshot_size, int overlap_size, int avg_method,
+                                                    float norm_spacing, int num_targets, int pspectrum_len, float scale)
+{
+    return gnuradio::get_initial_sptr(new music_pipeline_hip<music_pipeline_sc16>(
+        "music_pipeline_sc16", inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets, pspectrum_len,
+        input_format{DOA_SAMPLE_SC16, scale}));
 }
 root_music_pipeline::sptr root_music_pipeline::make(int inputs, int snapshot_size, int overlap_size, int avg_method,
                                                     float norm_spacing, int num_targets)
 {
-    return gnuradio::get_initial_sptr(new root_music_pipeline_hip(inputs, snapshot_size, overlap_size, avg_method, norm_spacing,
-                                                                  num_targets));
+    return gnuradio::get_initial_sptr(new root_music_pipeline_hip<root_music_pipeline>("root_music_pipeline", inputs, snapshot_size,
+                                                                                       overlap_size, avg_method, norm_spacing,
+                                                                                       num_targets));
+}
+root_music_pipeline_sc16::sptr root_music_pipeline_sc16::make(int inputs, int snapshot_size, int overlap_size, int avg_method,
+                                                              float norm_spacing, int num_targets, float scale)
+{
+    return gnuradio::get_initial_sptr(new root_music_pipeline_hip<root_music_pipeline_sc16>(
+        "root_music_pipeline_sc16", inputs, snapshot_size, overlap_size, avg_method, norm_spacing, num_targets,
+        input_format{DOA_SAMPLE_SC16, scale}));
 }
 calibrate_lin_array::sptr calibrate_lin_array::make(float norm_spacing, int num_ant_ele, float pilot_angle)
 {
@@ -381,7 +436,14 @@ antenna_correction::sptr antenna_correction::make(int num_ant_ele, char *config_
 }
 autocorrelate::sptr autocorrelate::make(int inputs, int snapshot_size, int overlap_size, int avg_method)
 {
-    return gnuradio::get_initial_sptr(new autocorrelate_hip(inputs, snapshot_size, overlap_size, avg_method));
+    return gnuradio::get_initial_sptr(new autocorrelate_hip<autocorrelate>("autocorrelate", inputs, snapshot_size, overlap_size,
+                                                                          avg_method));
+}
+autocorrelate_sc16::sptr autocorrelate_sc16::make(int inputs, int snapshot_size, int overlap_size, int avg_method, float scale)
+{
+    return gnuradio::get_initial_sptr(new autocorrelate_hip<autocorrelate_sc16>("autocorrelate_sc16", inputs, snapshot_size,
+                                                                               overlap_size, avg_method,
+                                                                               input_format{DOA_SAMPLE_SC16, scale}));
 }
 MUSIC_lin_array::sptr MUSIC_lin_array::make(float norm_spacing, int num_targets, int num_ant_ele, int pspectrum_len)
 {

@@ -140,6 +140,27 @@ DOA_HIP_API int doa_autocorrelate_work_dev(doa_autocorrelate_t *h, int noutput_i
                                            const void *const *d_input_items, void *d_output_items0,
                                            void *hip_stream);
 
+/* Input sample format of the streams (autocorrelate and the two pipelines; every entry of the handle: work, work_dev,
+ * work_dev_batches).  The default is the reference's gr_complex; the setter takes effect from the next work call (work
+ * already enqueued keeps what it was launched with) and may be called between any two calls.
+ *   DOA_SAMPLE_FC32  gr_complex, two float32 (real first), 8 B per sample; scale must be 1.0f (fc32 is never rescaled).
+ *                    Device streams must be 8-byte aligned; 16-byte aligned streams with an even snapshot-overlap take the
+ *                    pair-load kernels (and, with overlap, the read-once path).
+ *   DOA_SAMPLE_SC16  complex int16, two little-endian int16 (real first) -- std::complex<int16_t>, UHD's sc16, GRC's sc16
+ *                    port type -- 4 B per sample, read by the covariance kernel as it is and widened in registers:
+ *                        re = __fmul_rn((float)q_re, scale),  im = __fmul_rn((float)q_im, scale)
+ *                    (one rounding per component, never contracted).  scale: finite, > 0; 1.0f/32768 maps full scale to
+ *                    [-1, 1) exactly, a radio driver's own factor reproduces that driver's fc32 values.  Device streams
+ *                    must be 4-byte aligned; 8-byte aligned streams with an even snapshot-overlap take the same routes as
+ *                    16-byte aligned fc32 streams.  No fc32 copy of the streams is made anywhere.
+ * Parity: on int16 streams q, every output (covariance, spectrum, peaks, angles, status) is BIT-IDENTICAL to the fc32
+ * path's on the streams np.float32(q) * np.float32(scale): the kernels sum the same floats in the same order.
+ * Returns DOA_OK, or DOA_ERR_INVALID_ARG (doa_last_error() says why) for an unknown format, a scale that is not finite or
+ * not > 0, or DOA_SAMPLE_FC32 with a scale other than 1.0f; the handle keeps its previous format then. */
+#define DOA_SAMPLE_FC32 0   /* gr_complex, 8 B/sample: the default and the reference's format */
+#define DOA_SAMPLE_SC16 1   /* complex int16, 4 B/sample (real first) */
+DOA_HIP_API int doa_autocorrelate_set_input_format(doa_autocorrelate_t *h, int format, float scale);
+
 /* ---------------------------------------------------------------------------------------------
  * MUSIC_lin_array — gr::doa::MUSIC_lin_array::make(norm_spacing, num_targets, num_ant_ele,
  *   pspectrum_len) (include/doa/MUSIC_lin_array.h:56).  gr::sync_block.
@@ -317,6 +338,9 @@ DOA_HIP_API int doa_music_pipeline_set_lanes(doa_music_pipeline_t *h, int n_lane
  * another) -- the program that owns the process's streams is the one that can choose. */
 DOA_HIP_API int doa_music_pipeline_set_lane_streams(doa_music_pipeline_t *h, int n_lanes, void *const *hip_streams);
 DOA_HIP_API int doa_music_pipeline_set_internal_precision(doa_music_pipeline_t *h, int bits);
+/* Input sample format of the streams, as doa_autocorrelate_set_input_format (all entries of the handle; the host entry
+ * stages 4 B per sample for sc16, so half the bytes cross PCIe). */
+DOA_HIP_API int doa_music_pipeline_set_input_format(doa_music_pipeline_t *h, int format, float scale);
 /* The same three blocks on HOST buffers (the layouts the GNU Radio scheduler hands to the blocks'
  * work(): input_items[k] = stream k, doa_autocorrelate_input_span(noutput_items) samples; outputs
  * noutput_items items each).  cov_out and spectrum_out may be NULL: only the 2*num_targets floats
@@ -362,6 +386,8 @@ DOA_HIP_API int doa_root_pipeline_synchronize(doa_root_pipeline_t *h);
 DOA_HIP_API int doa_root_pipeline_set_lanes(doa_root_pipeline_t *h, int n_lanes);
 DOA_HIP_API int doa_root_pipeline_set_lane_streams(doa_root_pipeline_t *h, int n_lanes, void *const *hip_streams);
 DOA_HIP_API int doa_root_pipeline_set_internal_precision(doa_root_pipeline_t *h, int bits);
+/* Input sample format of the streams, as doa_autocorrelate_set_input_format. */
+DOA_HIP_API int doa_root_pipeline_set_input_format(doa_root_pipeline_t *h, int format, float scale);
 /* The same chain on HOST buffers (the layouts the GNU Radio scheduler hands to the blocks' work()); cov_out may be NULL.
  * Scheduler-sized calls take one staged copy each way, large ones ~32 MiB chunks alternating over two streams; returns when
  * every output has landed: noutput_items, or DOA_ERR_NUMERIC if some item had no root inside the unit circle (the angles of

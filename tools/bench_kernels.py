@@ -21,7 +21,14 @@ ap.add_argument("--ovl", type=int, default=0, help="overlap_size (windows advanc
 ap.add_argument("--fb", type=int, default=0, help="avg_method (1 = forward-backward)")
 ap.add_argument("--snr", type=float, default=20.0, help="per-source SNR in dB of the random-direction data")
 ap.add_argument("--ablate", default="", help="mcov: multi-stream covariance only; mmusic: multi-stream MUSIC only")
+ap.add_argument("--format", default="fc32", choices=["fc32", "sc16"],
+                help="input sample format of the covariance stage (sc16: the same streams quantised to complex int16 at "
+                     "scale 2**-12; stages cov, music, peak, root, rootpipe, pipe, host)")
 args = ap.parse_args()
+SC16 = args.format == "sc16"
+SC16_SCALE = 2.0 ** -12
+assert not (SC16 and (args.ablate or {"mpipe", "mroot"} & set(args.stages.split(",")))), "--format sc16: single-handle stages only"
+SB = 4 if SC16 else 8   # bytes per input sample
 N, K, P, M, B = args.N, args.K, args.P, args.M, args.batch
 OVL, FB = args.ovl, args.fb
 STEP = K - OVL          # new samples per snapshot; a batch of B windows spans (B-1)*STEP + K samples
@@ -60,6 +67,8 @@ if PAD >= 0:
             chans.append(v)
         padded.append(chans)
     streams = padded
+if SC16:   # the same streams as complex int16 (4 B per sample), in the slab layout the library recommends
+    streams = [doa.sim.stream_slab_torch([doa.sim.to_sc16(t, SC16_SCALE) for t in s_]) for s_ in streams]
 ptrs = [[t.data_ptr() for t in s] for s in streams]
 cov = [torch.empty((B, N * N), dtype=torch.complex64, device="cuda") for _ in range(args.nbuf)]
 spec = [torch.empty((B, P), dtype=torch.float32, device="cuda") for _ in range(args.nbuf)]
@@ -69,6 +78,9 @@ cov_blk = doa.autocorrelate(N, K, OVL, FB)
 music_blk = doa.MUSIC_lin_array(0.5, M, N, P)
 peak_blk = doa.find_local_max(M, P, 0.0, 180.0)
 pipe = doa.music_pipeline(N, K, OVL, FB, 0.5, M, P, B)
+if SC16:
+    cov_blk.set_input_format("sc16", SC16_SCALE)
+    pipe.set_input_format("sc16", SC16_SCALE)
 
 def timeit(fn):
     for i in range(10): fn(i)
@@ -87,7 +99,7 @@ for i in range(nb):   # valid covariances in every buffer for the music stage
     cov_blk.work_dev(B, ptrs[i], cov[i].data_ptr(), st)
 if "cov" in args.stages:
     res["cov_us"] = timeit(lambda i: cov_blk.work_dev(B, ptrs[i % nb], cov[i % nb].data_ptr(), st))
-    res["cov_GBs"] = (N * STEP * 8 + N * N * 8) * B / res["cov_us"][0] / 1e3      # new samples only: the halo is a cache re-read
+    res["cov_GBs"] = (N * STEP * SB + N * N * 8) * B / res["cov_us"][0] / 1e3     # new samples only: the halo is a cache re-read
 if "music" in args.stages:
     res["music_us"] = timeit(lambda i: music_blk.work_dev(B, cov[i % nb].data_ptr(), spec[i % nb].data_ptr(), st))
 if "peak" in args.stages:
@@ -99,6 +111,8 @@ if "root" in args.stages:
 if "rootpipe" in args.stages:
     # configs[2] through ONE handle (doa_root_pipeline): serial steps on one stream
     rp = doa.root_pipeline(N, K, OVL, FB, 0.5, M, B)
+    if SC16:
+        rp.set_input_format("sc16", SC16_SCALE)
     ang_rp = [torch.empty((B, M), dtype=torch.float32, device="cuda") for _ in range(nb)]
     res["rootpipe_us"] = timeit(lambda i: rp.work_dev(B, ptrs[i % nb], cov[i % nb].data_ptr(), ang_rp[i % nb].data_ptr(), None, st))
 skip_later = os.environ.pop("DOA_PIPE_SKIP", None)      # "cov", "evd", "scan" (comma separated): stages to drop AFTER every intermediate holds real data
@@ -162,7 +176,10 @@ if "host" in args.stages:
     import time
     import numpy as np
     for pinned in (False, True):
-        hx = [torch.view_as_complex(torch.randn((B * K, 2), dtype=torch.float32)) for _ in range(N)]
+        if SC16:
+            hx = [torch.randint(-32768, 32768, (B * K, 2), dtype=torch.int16) for _ in range(N)]
+        else:
+            hx = [torch.view_as_complex(torch.randn((B * K, 2), dtype=torch.float32)) for _ in range(N)]
         h_mx, h_am = torch.empty((B, M)), torch.empty((B, M))
         h_spec = torch.empty((B, P))
         if pinned:
@@ -177,7 +194,7 @@ if "host" in args.stages:
                     pipe.work(nit, xs, h_mx.numpy(), h_am.numpy(), spectrum_out=sp)
                 dt = (time.perf_counter() - t0) / reps
                 res[f"host_{'pinned' if pinned else 'pageable'}_{what}_n{nit}"] = {"us_per_call": dt * 1e6, "snapshots_per_s": nit / dt,
-                                                                              "GBs_in": nit * N * K * 8 / dt / 1e9}
+                                                                              "GBs_in": nit * N * K * SB / dt / 1e9}
 if args.ablate:
     import time
     S = args.streams
@@ -198,4 +215,5 @@ if args.ablate:
         torch.cuda.synchronize(); t0 = time.perf_counter(); run(args.reps); torch.cuda.synchronize()
         ts.append((time.perf_counter() - t0) / args.reps * 1e6)
     res["ablate"] = args.ablate; res["ablate_streams"] = S; res["ablate_us"] = (min(ts), sorted(ts)[2])
+res["format"] = args.format
 print(json.dumps({"env": {**{k: v for k, v in os.environ.items() if k.startswith("DOA_")}, **({"DOA_PIPE_SKIP": skip_later} if skip_later else {})}, "batch": B, **res}))
