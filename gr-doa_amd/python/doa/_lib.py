@@ -137,6 +137,20 @@ SIGNATURES = {
     "doa_autocorrelate_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
     "doa_music_pipeline_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
     "doa_root_pipeline_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "doa_phase_offset_est_create": (_vp, [C.c_int, C.c_int]),
+    "doa_phase_offset_est_destroy": (None, [_vp]),
+    "doa_phase_offset_est_reset": (C.c_int, [_vp]),
+    "doa_phase_offset_est_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "doa_phase_offset_est_work": (C.c_int, [_vp, C.c_int, _vpp, _vpp]),
+    "doa_phase_offset_est_work_dev": (C.c_int, [_vp, C.c_int, _vpp, _vpp, _vp]),
+    "doa_phase_offset_est_estimate": (C.c_int, [_vp, C.c_longlong, _vpp, C.c_longlong, _vp, _vp, _vp]),
+    "doa_phase_offset_est_estimate_dev": (C.c_int, [_vp, C.c_longlong, _vpp, C.c_longlong, _vp, _vp, _vp, _vp]),
+    "doa_calib_mean_work": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_calib_mean_work_dev": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_calib_mean_complex_work": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp]),
+    "doa_calib_mean_complex_work_dev": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_write_phase_config": (C.c_int, [C.c_char_p, _vp, C.c_int]),
+    "doa_write_antenna_calib": (C.c_int, [C.c_char_p, _vp, _vp, C.c_int]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_root_pipeline_inject_failure": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_lanes_idle": (C.c_int, [_vp]),

@@ -670,6 +670,241 @@ class compass_mean(_Block):
                                                    C.c_void_p(int(d_next_angle_ptr)), _stream_ptr(stream)))
 
 
+class twinrx_phase_offset_est(_StreamInput, _Block):
+    """doa.twinrx_phase_offset_est(num_ports=2, n_skip_ahead=8192) -- the reference's hier block
+    (python/twinrx_phase_offset_est.py:37-94): skiphead + complex_to_arg on every stream, then arg(x_0) - arg(x_p), unwrapped,
+    as num_ports - 1 float streams (`work`, `work_dev`); and the same fused with the reductions of its savers, nothing
+    materialised (`estimate`, `estimate_dev`: maximum, mean and circular mean of the first `samples` differences).  The
+    block keeps the skiphead state over calls; `reset` starts over."""
+
+    _destroy = staticmethod(lib.doa_phase_offset_est_destroy)
+    _set_format = staticmethod(lib.doa_phase_offset_est_set_input_format)
+
+    def __init__(self, num_ports=2, n_skip_ahead=8192):
+        super().__init__()
+        self.num_ports = self.inputs = int(num_ports)
+        self.n_skip_ahead = int(n_skip_ahead)
+        self._h = check_handle(lib.doa_phase_offset_est_create(self.num_ports, self.n_skip_ahead), "twinrx_phase_offset_est")
+        self.in_sig = [(_C64, 1)] * self.num_ports
+        self.out_sig = [(_F32, 1)] * (self.num_ports - 1)
+
+    def reset(self) -> None:
+        check(lib.doa_phase_offset_est_reset(self._h))
+
+    def work(self, n_items, input_items, output_items) -> int:
+        """input_items: num_ports streams of >= n_items samples; output_items: num_ports - 1 float32 arrays of >= n_items.
+        Returns the floats written to each output (n_items less what the skip still took)."""
+        n = int(n_items)
+        arrs = self._host_streams(input_items, n)
+        outs = list(output_items[:self.num_ports - 1])
+        for o in outs:
+            assert o.dtype == _F32 and o.flags.c_contiguous and o.size >= n
+        return check(lib.doa_phase_offset_est_work(self._h, n, ptr_array([a.ctypes.data for a in arrs]),
+                                                   ptr_array([o.ctypes.data for o in outs])))
+
+    def work_dev(self, n_items, d_input_ptrs, d_output_ptrs, stream=None) -> int:
+        return check(lib.doa_phase_offset_est_work_dev(self._h, int(n_items), ptr_array(d_input_ptrs),
+                                                       ptr_array(d_output_ptrs), _stream_ptr(stream)))
+
+    def estimate(self, n_items, input_items, samples, mean=True, max=True, circ=True):
+        """The fused form on host streams: (mean, max, circ), float32 arrays of num_ports - 1 (None where not asked for)."""
+        n = int(n_items)
+        arrs = self._host_streams(input_items, n)
+        outs = [np.empty(self.num_ports - 1, _F32) if want else None for want in (mean, max, circ)]
+        check(lib.doa_phase_offset_est_estimate(self._h, n, ptr_array([a.ctypes.data for a in arrs]), int(samples),
+                                                *[C.c_void_p(0) if o is None else _vp(o) for o in outs]))
+        return tuple(outs)
+
+    def estimate_dev(self, n_items, d_input_ptrs, samples, d_mean_ptr, d_max_ptr, d_circ_ptr, stream=None) -> None:
+        """The fused form on device pointers; each of the three output pointers may be None / 0."""
+        check(lib.doa_phase_offset_est_estimate_dev(
+            self._h, int(n_items), ptr_array(d_input_ptrs), int(samples), C.c_void_p(int(d_mean_ptr or 0)),
+            C.c_void_p(int(d_max_ptr or 0)), C.c_void_p(int(d_circ_ptr or 0)), _stream_ptr(stream)))
+
+
+def write_phase_config(filename, values) -> None:
+    """The phase file phase_correct_hier reads, one value per line (doa_write_phase_config).  ValueError with the
+    reference's text when the file cannot be written."""
+    v = np.ascontiguousarray(values, dtype=_F32).reshape(-1)
+    if lib.doa_write_phase_config(str(filename).encode(), _vp(v), v.size) < 0:
+        raise ValueError(_lib.last_error())
+
+
+def write_antenna_calib(filename, gains, phases) -> None:
+    """The antenna file antenna_correction reads, "gain phase" per line (doa_write_antenna_calib)."""
+    g = np.ascontiguousarray(gains, dtype=_F32).reshape(-1)
+    p = np.ascontiguousarray(phases, dtype=_F32).reshape(-1)
+    if g.size != p.size:
+        raise ValueError("gains and phases differ in length")
+    if lib.doa_write_antenna_calib(str(filename).encode(), _vp(g), _vp(p), g.size) < 0:
+        raise ValueError(_lib.last_error())
+
+
+def calib_mean(mag_items, phase_items, num_inputs):
+    """(gain, phase): the per-component means of two inputs of vlen-num_inputs float items, on the device
+    (doa_calib_mean_work; the reduction of save_antenna_calib)."""
+    N = int(num_inputs)
+    m = np.ascontiguousarray(mag_items, dtype=_F32).reshape(-1, N)
+    p = np.ascontiguousarray(phase_items, dtype=_F32).reshape(-1, N)
+    if m.shape != p.shape:
+        raise ValueError("magnitude and phase inputs differ in length")
+    g, ph = np.empty(N, _F32), np.empty(N, _F32)
+    check(lib.doa_calib_mean_work(m.shape[0], N, _vp(m), _vp(p), _vp(g), _vp(ph)))
+    return g, ph
+
+
+def calib_mean_complex(c_items, num_inputs):
+    """(gain, phase) from calibrate_lin_array's complex output items: |c| and atan2f(im, re) per element
+    (complex_to_magphase), then the means, on the device (doa_calib_mean_complex_work)."""
+    N = int(num_inputs)
+    c = np.ascontiguousarray(c_items, dtype=_C64).reshape(-1, N)
+    g, ph = np.empty(N, _F32), np.empty(N, _F32)
+    check(lib.doa_calib_mean_complex_work(c.shape[0], N, _vp(c), _vp(g), _vp(ph)))
+    return g, ph
+
+
+def calib_mean_dev(n_items, num_inputs, d_mag_ptr, d_phase_ptr, d_gain_ptr, d_phase_out_ptr, stream=None) -> int:
+    return check(lib.doa_calib_mean_work_dev(int(n_items), int(num_inputs), C.c_void_p(int(d_mag_ptr)), C.c_void_p(int(d_phase_ptr)),
+                                             C.c_void_p(int(d_gain_ptr)), C.c_void_p(int(d_phase_out_ptr)), _stream_ptr(stream)))
+
+
+def calib_mean_complex_dev(n_items, num_inputs, d_c_ptr, d_gain_ptr, d_phase_out_ptr, stream=None) -> int:
+    return check(lib.doa_calib_mean_complex_work_dev(int(n_items), int(num_inputs), C.c_void_p(int(d_c_ptr)),
+                                                     C.c_void_p(int(d_gain_ptr)), C.c_void_p(int(d_phase_out_ptr)),
+                                                     _stream_ptr(stream)))
+
+
+class _PhaseSaver:
+    """What findmax_and_save and average_and_save share: a sink of num_inputs float streams that reduces the first
+    `samples` of each to one number, writes them to config_filename (one per line) and returns -1, which ends the
+    reference's flowgraph.  The constructor truncates the file; where the reference writes "Configuration <name>, not
+    writable" and exits, this raises ValueError with that text."""
+
+    _which = None                         # index into twinrx_phase_offset_est.estimate's (mean, max, circ)
+    _reduce = None
+
+    def __init__(self, samples, num_inputs, config_filename):
+        self.samples, self.num_inputs, self.config_filename = int(samples), int(num_inputs), config_filename
+        write_phase_config(config_filename, [])
+        self.in_sig = [(_F32, 1)] * self.num_inputs
+        self.out_sig = []
+        self.values = None                # what the last call wrote
+
+    def output_multiple(self) -> int:
+        return self.samples               # set_output_multiple(samples) of the reference
+
+    def work(self, input_items, output_items=None) -> int:
+        """input_items: num_inputs host float arrays, as the reference's work takes them (numpy, no device)."""
+        vals = [type(self)._reduce(np.asarray(input_items[i], dtype=_F32)[:self.samples]) for i in range(self.num_inputs)]
+        return self._save(vals)
+
+    def from_estimator(self, est, n_items, input_items, which=None) -> int:
+        """The fused form: `est` (a twinrx_phase_offset_est with num_inputs + 1 ports) reduces its host input streams on
+        the device in one pass, no float stream in between; which = "circ" writes the circular mean instead of this
+        block's own statistic."""
+        if est.num_ports != self.num_inputs + 1:
+            raise ValueError(f"estimator has {est.num_ports} ports, this sink {self.num_inputs} inputs")
+        idx = 2 if which == "circ" else type(self)._which
+        want = [i == idx for i in range(3)]
+        return self._save(est.estimate(n_items, input_items, self.samples, *want)[idx])
+
+    def from_estimator_dev(self, est, n_items, d_input_ptrs, which=None, stream=None) -> int:
+        """from_estimator on device-resident streams (pointers); the num_inputs results come back through a torch tensor."""
+        import torch
+        if est.num_ports != self.num_inputs + 1:
+            raise ValueError(f"estimator has {est.num_ports} ports, this sink {self.num_inputs} inputs")
+        idx = 2 if which == "circ" else type(self)._which
+        res = torch.empty(self.num_inputs, dtype=torch.float32, device="cuda")
+        ptrs = [res.data_ptr() if i == idx else 0 for i in range(3)]
+        stream = torch.cuda.current_stream() if stream is None else stream
+        est.estimate_dev(n_items, d_input_ptrs, self.samples, *ptrs, stream=stream)
+        if hasattr(stream, "synchronize"):
+            stream.synchronize()
+        else:
+            torch.cuda.synchronize()
+        return self._save(res.cpu().numpy())
+
+    def _save(self, vals) -> int:
+        self.values = np.asarray(vals, dtype=_F32).reshape(self.num_inputs)
+        write_phase_config(self.config_filename, self.values)
+        return -1
+
+
+class findmax_and_save(_PhaseSaver):
+    """doa.findmax_and_save(samples_to_findmax, num_inputs, config_filename) -- reference python/findmax_and_save.py:36-78:
+    numpy.amax of the first samples_to_findmax floats of each input."""
+
+    _which = 1
+    _reduce = staticmethod(np.amax)
+
+    def __init__(self, samples_to_findmax, num_inputs, config_filename):
+        super().__init__(samples_to_findmax, num_inputs, config_filename)
+        self.samples_to_findmax = self.samples
+
+
+class average_and_save(_PhaseSaver):
+    """doa.average_and_save(samples_to_average, num_inputs, config_filename) -- reference python/average_and_save.py:35-80:
+    numpy.mean of the first samples_to_average floats of each input (meaningless when the differences straddle +-pi:
+    reproduced, not repaired)."""
+
+    _which = 0
+    _reduce = staticmethod(np.mean)
+
+    def __init__(self, samples_to_average, num_inputs, config_filename):
+        super().__init__(samples_to_average, num_inputs, config_filename)
+        self.samples_to_average = self.samples
+
+
+class save_antenna_calib:
+    """doa.save_antenna_calib(num_inputs, config_filename="", samples_to_average=1024) -- reference
+    python/save_antenna_calib.py:30-75: two inputs of vlen-num_inputs float items (magnitude, phase); per component the mean
+    over ALL items of the call (samples_to_average only sets the output multiple), written as "gain phase" per line.
+    Raises ValueError("Configuration <name>, not valid") where the reference exits."""
+
+    def __init__(self, num_inputs, config_filename="", samples_to_average=1024):
+        self.num_inputs, self.config_filename = int(num_inputs), config_filename
+        self.samples_to_average = int(samples_to_average)
+        write_antenna_calib(config_filename, [], [])
+        self.in_sig = [(_F32, self.num_inputs)] * 2
+        self.out_sig = []
+        self.gains = self.phases = None   # what the last call wrote
+
+    def output_multiple(self) -> int:
+        return self.samples_to_average
+
+    def work(self, input_items, output_items=None) -> int:
+        """input_items = [magnitude items, phase items], host float arrays [n, num_inputs], as the reference's work takes
+        them (numpy.mean per component, no device)."""
+        g = np.asarray(input_items[0], dtype=_F32).reshape(-1, self.num_inputs)
+        p = np.asarray(input_items[1], dtype=_F32).reshape(-1, self.num_inputs)
+        return self._save([np.mean(g[:, i]) for i in range(self.num_inputs)], [np.mean(p[:, i]) for i in range(self.num_inputs)])
+
+    def from_calibration(self, c_items) -> int:
+        """The fused form on calibrate_lin_array's complex output items (host array [n, num_inputs]): magnitude, phase and
+        the means in one device kernel."""
+        return self._save(*calib_mean_complex(c_items, self.num_inputs))
+
+    def from_calibration_dev(self, n_items, d_c_ptr, stream=None) -> int:
+        """from_calibration on a device pointer (calibrate_lin_array.work_dev's output); the 2 num_inputs results come back
+        through a torch tensor."""
+        import torch
+        res = torch.empty(2 * self.num_inputs, dtype=torch.float32, device="cuda")
+        stream = torch.cuda.current_stream() if stream is None else stream
+        calib_mean_complex_dev(n_items, self.num_inputs, d_c_ptr, res.data_ptr(), res.data_ptr() + 4 * self.num_inputs, stream)
+        if hasattr(stream, "synchronize"):
+            stream.synchronize()
+        else:
+            torch.cuda.synchronize()
+        r = res.cpu().numpy()
+        return self._save(r[:self.num_inputs], r[self.num_inputs:])
+
+    def _save(self, gains, phases) -> int:
+        self.gains = np.asarray(gains, dtype=_F32).reshape(self.num_inputs)
+        self.phases = np.asarray(phases, dtype=_F32).reshape(self.num_inputs)
+        write_antenna_calib(self.config_filename, self.gains, self.phases)
+        return -1
+
+
 class sim_source(_Block):
     """The signal front end of apps/run_MUSIC_lin_array_simulation.py (:66-74, :204-210) as one
     device-side generator: tones + per-source Gaussian noise through the array manifold, plus

@@ -25,6 +25,9 @@
  *                                (autocorrelate -> MUSIC_lin_array -> find_local_max(M, P, 0, 180))
  *   doa_root_pipeline_*          the two blocks as wired by apps/run_RootMUSIC_lin_array_simulation.grc
  *                                (autocorrelate -> rootMUSIC_linear_array)
+ *   doa_phase_offset_est_*       python/twinrx_phase_offset_est.py:37-94, fused with the reductions of
+ *                                python/findmax_and_save.py:66-78 and python/average_and_save.py:68-80
+ *   doa_calib_mean_*, doa_write_*  python/save_antenna_calib.py:30-75 and the two calibration file formats
  *
  * Threading: like GNU Radio's thread-per-block scheduler assumes, different handles may be used
  * from different threads concurrently; one handle must not be used from two threads at once.
@@ -412,6 +415,94 @@ DOA_HIP_API int doa_compass_mean_work(doa_compass_mean_t *h, int ninput_items,
 DOA_HIP_API int doa_compass_mean_work_dev(doa_compass_mean_t *h, int ninput_items,
                                           const void *d_input_items0, float *d_next_angle,
                                           void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * phase_offset_est — doa.twinrx_phase_offset_est(num_ports, n_skip_ahead), the reference's hier block
+ *   (python/twinrx_phase_offset_est.py:37-94): blocks.skiphead(n_skip_ahead) and blocks.complex_to_arg on each of the
+ *   num_ports streams, then blocks.sub_ff(stream 0, stream p): num_ports - 1 float streams
+ *       out_{p-1}[i] = atan2f(im x_0[i], re x_0[i]) - atan2f(im x_p[i], re x_p[i]),   p = 1 .. num_ports-1,
+ *   one float subtraction, NOT wrapped into any interval: the values lie in (-2 pi, 2 pi) and take the two branches phi and
+ *   phi -+ 2 pi of the offset phi, which is what the reference's savers are fed.  atan2f(0, 0) = 0; a sample with a NaN or
+ *   Inf component gives NaN for that sample's outputs alone (not the limit atan2f defines for an infinite operand).  2 <= num_ports <= DOA_MAX_ANT_ELE, n_skip_ahead >= 0.
+ *   The handle carries the skiphead state: the first n_skip_ahead samples it is ever given, over any number of calls to
+ *   any of its entries, are dropped on every stream; doa_phase_offset_est_reset starts over.
+ *   What is NOT parity: GNU Radio 3.7's complex_to_arg evaluates a table-driven fast arctangent of its own (not part of the
+ *   gr-doa tree, not reproduced); this is the formula, each output within 4 * 2^-21 rad of its float64 evaluation.
+ * Streaming form (the block as the flowgraph wires it): work consumes n_items samples per stream and writes
+ *   n_items - (skip still owed) floats to each output, from index 0; returns that count (0 while the skip is being paid).
+ *   input_items: num_ports streams (host array of pointers), output_items: num_ports - 1 float streams.
+ * Fused form (the block and its saver in one pass; nothing is materialised): of the n_items samples given, drop what the
+ *   skip still owes, take the first `samples` of the rest -- DOA_ERR_INVALID_ARG if fewer remain (the reference's savers
+ *   get them through set_output_multiple) -- and write num_ports - 1 floats to each output that is not NULL:
+ *     max_out[p-1]   the maximum of the streaming form's floats, bit for bit (numpy.amax: a NaN sticks).  What
+ *                    findmax_and_save writes (python/findmax_and_save.py:66-78): of the two branches the maximum is the
+ *                    one in [0, 2 pi).
+ *     mean_out[p-1]  their mean, summed in double in a fixed order, rounded once.  What average_and_save writes
+ *                    (python/average_and_save.py:68-80), its flaw included: when the difference crosses +-pi the two
+ *                    branches are averaged and the number means nothing.
+ *     circ_out[p-1]  arg(sum_i x_0[i] conj(x_p[i])), products and sum in double, rounded to float: in [-pi, pi].  Not in
+ *                    the reference: the estimate that does not depend on the branch and that noise does not bias.
+ *   Results are bit-identical from run to run, between the host and the device entry and for any stream alignment: the
+ *   samples are summed in a partition that depends on `samples` alone.  Returns DOA_OK.
+ * Device entries: device pointers (the pointer arrays themselves are host arrays), asynchronous on hip_stream; fc32 streams
+ *   8-byte aligned (16-byte aligned streams take 16-byte loads when the skip leaves them so), sc16 4 / 8.  The layout
+ *   advice of doa_stream_stride_bytes applies: every wave reads the same sample range of all streams.  The host estimate
+ *   entry stages ~32 MiB of samples per copy.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct doa_phase_offset_est doa_phase_offset_est_t;
+
+DOA_HIP_API doa_phase_offset_est_t *doa_phase_offset_est_create(int num_ports, int n_skip_ahead);
+DOA_HIP_API void doa_phase_offset_est_destroy(doa_phase_offset_est_t *h);
+/* Forget the samples skipped so far: the next n_skip_ahead samples are dropped again. */
+DOA_HIP_API int doa_phase_offset_est_reset(doa_phase_offset_est_t *h);
+/* Input sample format of the streams: exactly the contract of doa_autocorrelate_set_input_format (sc16 widened in
+ * registers, no fc32 copy made, every output of both forms bit-identical to the fc32 path's on float(q) * scale). */
+DOA_HIP_API int doa_phase_offset_est_set_input_format(doa_phase_offset_est_t *h, int format, float scale);
+DOA_HIP_API int doa_phase_offset_est_work(doa_phase_offset_est_t *h, int n_items, const void *const *input_items,
+                                          void *const *output_items);
+DOA_HIP_API int doa_phase_offset_est_work_dev(doa_phase_offset_est_t *h, int n_items, const void *const *d_input_items,
+                                              void *const *d_output_items, void *hip_stream);
+DOA_HIP_API int doa_phase_offset_est_estimate(doa_phase_offset_est_t *h, long long n_items,
+                                              const void *const *input_items, long long samples, float *mean_out,
+                                              float *max_out, float *circ_out);
+DOA_HIP_API int doa_phase_offset_est_estimate_dev(doa_phase_offset_est_t *h, long long n_items,
+                                                  const void *const *d_input_items, long long samples,
+                                                  float *d_mean_out, float *d_max_out, float *d_circ_out,
+                                                  void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * calib_mean — the reduction of doa.save_antenna_calib (python/save_antenna_calib.py:61-69): two inputs of n_items items
+ *   of num_inputs floats each (magnitude and phase of the estimated antenna responses; wiring
+ *   apps/run_calib_lin_array_simulation.grc: autocorrelate -> calibrate_lin_array -> complex_to_magphase -> here);
+ *   gain_out[m] / phase_out[m] = mean over ALL n_items items of component m (the reference's numpy.mean(G[m::num_inputs])),
+ *   summed in double in a fixed order and rounded once (numpy's float32 pairwise mean differs by a few ulp); NaN for 0 items.
+ *   The complex form takes calibrate_lin_array's output items (num_inputs gr_complex each) and forms |c| and
+ *   atan2f(im, re) itself, so the chain stays on the device.  No handle: the host entries stage through buffers of their
+ *   own.  Return n_items or a negative doa_status.
+ * --------------------------------------------------------------------------------------------- */
+DOA_HIP_API int doa_calib_mean_work(int n_items, int num_inputs, const float *mag_in, const float *phase_in,
+                                    float *gain_out, float *phase_out);
+DOA_HIP_API int doa_calib_mean_work_dev(int n_items, int num_inputs, const float *d_mag_in, const float *d_phase_in,
+                                        float *d_gain_out, float *d_phase_out, void *hip_stream);
+DOA_HIP_API int doa_calib_mean_complex_work(int n_items, int num_inputs, const void *c_in, float *gain_out,
+                                            float *phase_out);
+DOA_HIP_API int doa_calib_mean_complex_work_dev(int n_items, int num_inputs, const void *d_c_in, float *d_gain_out,
+                                                float *d_phase_out, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The calibration files, written.  No device needed.
+ *   doa_write_phase_config   the file doa.phase_correct_hier reads (python/phase_correct_hier.py:33-45) and
+ *                            findmax_and_save / average_and_save write (python/findmax_and_save.py:66-78): n lines, one
+ *                            value each.
+ *   doa_write_antenna_calib  the file doa_antenna_correction_create reads (lib/antenna_correction_impl.cc:56-73) and
+ *                            save_antenna_calib writes (python/save_antenna_calib.py:61-72): n lines "gain phase".
+ * The file is truncated; every float is printed with nine significant digits, so it parses back to the same float32
+ * (the reference prints Python's str() of a numpy float).  A value of 0 is written like any other, although the reference's
+ * phase-file reader drops such a line.  Returns DOA_OK, or DOA_ERR_INVALID_ARG with the reference's message in
+ * doa_last_error(): "Configuration <name>, not writable" (phase file) / "Configuration <name>, not valid" (antenna file).
+ * --------------------------------------------------------------------------------------------- */
+DOA_HIP_API int doa_write_phase_config(const char *filename, const float *values, int n);
+DOA_HIP_API int doa_write_antenna_calib(const char *filename, const float *gains, const float *phases, int n);
 
 /* ---------------------------------------------------------------------------------------------
  * sim_source — the signal front end of the simulation flowgraphs as one generator
