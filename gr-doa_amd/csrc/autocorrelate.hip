@@ -46,6 +46,42 @@ template <class L> __device__ __forceinline__ const typename L::sample_t *stream
     return static_cast<const typename L::sample_t *>(g.in[k]);
 }
 
+// Multi-batch form (kernels.hpp, BatchGroup; N <= 4): snapshot g = batch * n + local reads its batch's own streams and
+// writes its batch's own items.  n_out is the group's total.
+struct CovGroupArgs : CovArgs {
+    const void *gin[kMaxGroup][4];
+    float2 *gout[kMaxGroup];
+    GroupSplit split;
+};
+
+// where one snapshot's samples come from and where its item goes
+template <class L, int TN> struct SnapIO {
+    const typename L::sample_t *in[TN];
+    size_t base;        // first sample of the window in every stream
+    float2 *out;        // the item
+};
+template <class L, int TN> __device__ __forceinline__ SnapIO<L, TN> snap_io(const CovArgs &g, int snap)
+{
+    SnapIO<L, TN> io;
+#pragma unroll
+    for (int a = 0; a < TN; a++) io.in[a] = stream<L>(g, a);
+    io.base = (size_t)snap * (size_t)g.S;
+    io.out = g.out + (size_t)snap * (TN * TN);
+    return io;
+}
+template <class L, int TN> __device__ __forceinline__ SnapIO<L, TN> snap_io(const CovGroupArgs &g, int snap)
+{
+    static_assert(TN <= 4, "the group table holds four streams per batch");
+    unsigned batch, local;
+    g.split((unsigned)__builtin_amdgcn_readfirstlane(snap), batch, local);      // wave-uniform: the table is read with scalar loads
+    SnapIO<L, TN> io;
+#pragma unroll
+    for (int a = 0; a < TN; a++) io.in[a] = static_cast<const typename L::sample_t *>(g.gin[batch][a]);
+    io.base = (size_t)local * (size_t)g.S;
+    io.out = g.gout[batch] + (size_t)local * (TN * TN);
+    return io;
+}
+
 template <int TN> struct TriAcc {
     float d[TN];
     float re[TN * (TN - 1) / 2 > 0 ? TN * (TN - 1) / 2 : 1];
@@ -71,8 +107,9 @@ template <int TN> __device__ __forceinline__ void tri_accumulate(TriAcc<TN> &acc
 // One wave per snapshot, N = TN <= 8, Hermitian symmetry exploited.
 // VEC2: all streams aligned to two samples at every window start (base 16-B aligned for fc32, 8-B for sc16; S even) ->
 // one load per sample pair.
-template <class L, int TN, bool VEC2, int UN, bool NT = false>
-__global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
+// A = CovArgs (one batch) or CovGroupArgs (a group of batches): only snap_io differs.
+template <class L, int TN, bool VEC2, int UN, bool NT = false, class A = CovArgs>
+__global__ __launch_bounds__(256) void cov_wave_kernel(A g)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave0 = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
@@ -80,7 +117,8 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
     // grid-stride over snapshots: the launch may use fewer waves than snapshots so that other kernels
     // (the EVD / scan of the previous batch on another stream) find free wave slots on every CU
     for (int snap = wave0; snap < g.n_out; snap += n_waves) {
-    const size_t base = (size_t)snap * (size_t)g.S;
+    const SnapIO<L, TN> io = snap_io<L, TN>(g, snap);
+    const size_t base = io.base;
 
     TriAcc<TN> acc;
 #pragma unroll
@@ -100,7 +138,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
             for (int u = 0; u < UN; u++)
 #pragma unroll
                 for (int a = 0; a < TN; a++)
-                    v[u][a] = L::template pair<NT>(stream<L>(g, a) + base + 2 * (size_t)(p + u * kWave), g.scale);
+                    v[u][a] = L::template pair<NT>(io.in[a] + base + 2 * (size_t)(p + u * kWave), g.scale);
 #pragma unroll
             for (int u = 0; u < UN; u++) {
                 float2 x0[TN], x1[TN];
@@ -113,7 +151,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
         for (; p < npair; p += kWave) {
             float4 v[TN];
 #pragma unroll
-            for (int a = 0; a < TN; a++) v[a] = L::template pair<NT>(stream<L>(g, a) + base + 2 * (size_t)p, g.scale);
+            for (int a = 0; a < TN; a++) v[a] = L::template pair<NT>(io.in[a] + base + 2 * (size_t)p, g.scale);
             float2 x0[TN], x1[TN];
 #pragma unroll
             for (int a = 0; a < TN; a++) { x0[a] = make_float2(v[a].x, v[a].y); x1[a] = make_float2(v[a].z, v[a].w); }
@@ -123,7 +161,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
         if ((g.K & 1) && lane == 0) {
             float2 x[TN];
 #pragma unroll
-            for (int a = 0; a < TN; a++) x[a] = L::one(stream<L>(g, a) + (base + (size_t)(g.K - 1)), g.scale);
+            for (int a = 0; a < TN; a++) x[a] = L::one(io.in[a] + (base + (size_t)(g.K - 1)), g.scale);
             tri_accumulate<TN>(acc, x);
         }
     } else {
@@ -131,7 +169,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
         for (int t = lane; t < g.K; t += kWave) {
             float2 x[TN];
 #pragma unroll
-            for (int a = 0; a < TN; a++) x[a] = L::one(stream<L>(g, a) + (base + (size_t)t), g.scale);
+            for (int a = 0; a < TN; a++) x[a] = L::one(io.in[a] + (base + (size_t)t), g.scale);
             tri_accumulate<TN>(acc, x);
         }
     }
@@ -174,7 +212,7 @@ __global__ __launch_bounds__(256) void cov_wave_kernel(CovArgs g)
         r.x = __fadd_rn(__fmul_rn(0.5f, r.x), __fmul_rn(g.fb_hk, px));
         r.y = __fadd_rn(__fmul_rn(0.5f, r.y), __fmul_rn(g.fb_hk, -py));
     }
-    if (lane < TN * TN) g.out[(size_t)snap * (TN * TN) + lane] = r;
+    if (lane < TN * TN) io.out[lane] = r;
     }  // snapshot loop
 }
 
@@ -525,6 +563,74 @@ int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *
     }
     if (sc16) launch_routes<Sc16Samples>(g, vec2, st);
     else      launch_routes<Fc32Samples>(g, vec2, st);
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+bool autocorrelate_pair_loads(int N, int K, int ovl, const void *const *d_in, int format)
+{
+    const int sb = (format == DOA_SAMPLE_SC16) ? 4 : 8;
+    if ((K - ovl) % 2) return false;
+    for (int k = 0; k < N; k++)
+        if (reinterpret_cast<uintptr_t>(d_in[k]) % (2 * sb)) return false;
+    return true;
+}
+
+// Grid of a multi-batch K1: ONE WAVE PER SNAPSHOT, no cap.  The single-batch cap (cov_waves_per_cu: 16 waves per CU, which at
+// the benchmark batch is one wave per snapshot anyway) would turn a group into 4096 waves that stay for the whole launch, and
+// the EVD / scan workgroups of the neighbouring lane would find no free wave slots until it ends; with one wave per snapshot
+// workgroups retire all the time.  (Lab builds: DOA_COV_GROUP_WAVES_PER_CU > 0 restores a cap; profiles/grouped_batches.txt.)
+template <class L, int TN> static void launch_wave_group(const CovGroupArgs &g, bool vec2, hipStream_t st)
+{
+    const int waves_per_block = 4;
+    int blocks = (g.n_out + waves_per_block - 1) / waves_per_block;
+    if (const int wpc = DOA_LAB_ENV_INT("DOA_COV_GROUP_WAVES_PER_CU", 0); wpc > 0) {
+        const int cap = cu_count() * wpc / waves_per_block;
+        if (blocks > cap) blocks = cap;
+    }
+    dim3 grid(blocks), block(waves_per_block * kWave);
+    constexpr int UN = 4;                       // as launch_wave for N <= 6
+    if (!vec2) hipLaunchKernelGGL((cov_wave_kernel<L, TN, false, 1, false, CovGroupArgs>), grid, block, 0, st, g);
+    else       hipLaunchKernelGGL((cov_wave_kernel<L, TN, true, UN, true, CovGroupArgs>), grid, block, 0, st, g);
+}
+template <class L> static void launch_group_routes(const CovGroupArgs &g, bool vec2, hipStream_t st)
+{
+    switch (g.n_ch) {
+    case 2: launch_wave_group<L, 2>(g, vec2, st); break;
+    case 3: launch_wave_group<L, 3>(g, vec2, st); break;
+    default: launch_wave_group<L, 4>(g, vec2, st); break;
+    }
+}
+
+int launch_autocorrelate_group(int N, int K, int avg, const BatchGroup &grp, hipStream_t st, const void *d_gain_outer,
+                               int format, float scale)
+{
+    if (grp.n_batches <= 0 || grp.n <= 0) return DOA_OK;
+    if (N < 2 || N > 4 || grp.n_batches > kMaxGroup) { set_error("autocorrelate: not a group shape (N=%d, %d batches)", N, grp.n_batches); return DOA_ERR_INVALID_ARG; }
+    CovGroupArgs g;
+    memset(static_cast<void *>(&g), 0, sizeof g);
+    const bool sc16 = (format == DOA_SAMPLE_SC16);
+    const int sb = sc16 ? 4 : 8;
+    const bool vec2 = autocorrelate_pair_loads(N, K, 0, grp.in[0], format);
+    for (int b = 0; b < kMaxGroup; b++) {
+        const int src = b < grp.n_batches ? b : 0;          // unused entries repeat batch 0: never a wild pointer
+        for (int k = 0; k < 4; k++) {
+            const void *p = grp.in[src][k < N ? k : 0];
+            if (!p) { set_error("autocorrelate: input stream %d of batch %d is NULL", k, src); return DOA_ERR_INVALID_ARG; }
+            if (reinterpret_cast<uintptr_t>(p) % sb) { set_error("autocorrelate: input stream %d is not %d-byte aligned", k, sb); return DOA_ERR_INVALID_ARG; }
+            g.gin[b][k] = p;
+        }
+        if (autocorrelate_pair_loads(N, K, 0, grp.in[src], format) != vec2) { set_error("autocorrelate: a group mixes the two load routes"); return DOA_ERR_INVALID_ARG; }
+        g.gout[b] = static_cast<float2 *>(grp.cov[src]);
+    }
+    g.split = GroupSplit::make(grp.n);
+    g.n_ch = N; g.K = K; g.S = K; g.n_out = grp.n_batches * grp.n; g.avg = avg;
+    g.inv_k = (float)(1.0 / K);
+    g.fb_hk = (float)(0.5 / K);
+    g.gain = static_cast<const float2 *>(d_gain_outer);
+    g.scale = sc16 ? scale : 1.0f;
+    if (sc16) launch_group_routes<Sc16Samples>(g, vec2, st);
+    else      launch_group_routes<Fc32Samples>(g, vec2, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }

@@ -15,6 +15,49 @@ int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *
 int check_input_format(const char *what, int format, float scale);
 inline size_t sample_bytes(int format) { return format == DOA_SAMPLE_SC16 ? 4 : 8; }
 
+// ---- multi-batch ("grouped") launches of the lean route: N <= 4, no overlap, double, P = 256 / 512 / 1024 ----------------
+// One K1, one EVD and one scan launch each cover a GROUP of up to kMaxGroup batches of `n` items each: item
+// g = batch * n + local, 0 <= g < n_batches * n.  The kernels get the group's pointers BY VALUE in their arguments (no
+// device-side table); the records between them (coefficients, Chebyshev form) are packed densely by g in one workspace.
+// The per-item code is the single-batch kernels' own (the same templates), so results do not depend on the grouping.
+// kMaxGroup: profiles/grouped_batches.txt (lab builds carry room for the largest size measured there).
+#ifdef DOA_LAB
+constexpr int kMaxGroup = 16;
+#else
+constexpr int kMaxGroup = 8;
+#endif
+struct BatchGroup {
+    int n_batches = 0, n = 0;
+    const void *const *in[kMaxGroup];   // batch b: its N input stream pointers (host array of device pointers)
+    void *cov[kMaxGroup];               // covariance items of batch b (written by K1, read by the EVD)
+    void *spec[kMaxGroup];              // spectrum rows (or P-float scratch rows per item in the angles-only mode)
+    void *mx[kMaxGroup], *am[kMaxGroup];
+};
+// g -> (batch, local) without a division: magic = floor(2^32 / n) under-estimates the quotient by at most one for
+// g < 2^32 (g (1/n - magic / 2^32) < g / 2^32 < 1), which one compare corrects
+struct GroupSplit {
+    unsigned n, magic;
+    static GroupSplit make(int n_) { return {(unsigned)n_, (unsigned)((1ull << 32) / (unsigned)n_ - (n_ == 1 ? 1 : 0))}; }
+    __device__ __forceinline__ void operator()(unsigned g, unsigned &batch, unsigned &local) const
+    {
+        unsigned q = __umulhi(g, magic);
+        unsigned r = g - q * n;
+        if (r >= n) { q++; r -= n; }
+        batch = q; local = r;
+    }
+};
+// the pair-load route of K1 (all streams aligned to two samples, even step): a group must be uniform in it, because the
+// two routes sum in different orders
+bool autocorrelate_pair_loads(int N, int K, int ovl, const void *const *d_in, int format);
+int launch_autocorrelate_group(int N, int K, int avg, const BatchGroup &grp, hipStream_t st, const void *d_gain_outer,
+                               int format, float scale);
+// the shapes launch_music_evd_group / launch_music_scan_group take (the one-lane EVD route; the lean scan kernel)
+inline bool music_group_shape_ok(int N, int M, int P, int bits)
+{
+    return N >= 2 && N <= 4 && bits == 64 && !(N == 4 && M == 2) && (P == 256 || P == 512 || P == 1024);
+}
+int launch_music_evd_group(int N, int M, const BatchGroup &grp, void *d_coef_d, void *d_cheb, hipStream_t st);
+
 // Host-built tables of MUSIC_lin_array (music.hip): z_i = exp(j*psi_i), psi_i = k_i * d with
 // k_i = float(-2*pi*cos(theta_i)) on the reference's float-accumulated theta grid.
 struct MusicTables {
@@ -55,6 +98,10 @@ int launch_music_scan(const MusicTables &t, int bits, int n_items, const void *d
                       hipStream_t st, const PeakTables *peaks = nullptr, void *d_max = nullptr,
                       void *d_argmax = nullptr, bool *peaks_done = nullptr, bool store_spectrum = true,
                       const void *d_cheb = nullptr);
+// the lean scan + peak pick over a group (music_group_shape_ok shapes, peaks->L == t.P, every grp.spec 16-byte aligned);
+// d_cheb: the group's records, dense by g.  store_spectrum = false: grp.spec are scratch rows (angles only)
+int launch_music_scan_group(const MusicTables &t, const PeakTables &peaks, const BatchGroup &grp, const void *d_cheb,
+                            bool store_spectrum, hipStream_t st);
 
 // K5 (find_local_max.hip)
 struct PeakTables {

@@ -62,6 +62,7 @@ int MusicTables::build(float norm_spacing_, int num_targets, int num_ant_ele, in
 // K4: spectrum scan — kernels in music_scan_impl.hpp, one translation unit per polynomial size
 // ---------------------------------------------------------------------------------------------
 DOA_SCAN_SIZES(DOA_SCAN_EXTERN)
+DOA_SCAN_GROUP_EXTERN(2) DOA_SCAN_GROUP_EXTERN(3) DOA_SCAN_GROUP_EXTERN(4)
 
 int launch_music_scan(const MusicTables &t, int bits, int n_items, const void *d_coef, void *d_spec, void *d_q,
                       hipStream_t st, const PeakTables *peaks, void *d_max, void *d_argmax, bool *peaks_done,
@@ -91,6 +92,23 @@ int launch_music_scan(const MusicTables &t, int bits, int n_items, const void *d
     else if (n <= 12) done = launch_scan_n<12>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
     else done = launch_scan_n<16>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
     if (peaks_done) *peaks_done = done;
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+int launch_music_scan_group(const MusicTables &t, const PeakTables &peaks, const BatchGroup &grp, const void *d_cheb,
+                            bool store_spectrum, hipStream_t st)
+{
+    if (grp.n_batches <= 0 || grp.n <= 0) return DOA_OK;
+    bool ok = music_group_shape_ok(t.N, peaks.M, t.P, 64) && peaks.L == t.P && d_cheb && grp.n_batches <= kMaxGroup;
+    for (int b = 0; b < grp.n_batches && ok; b++)
+        ok = grp.spec[b] && reinterpret_cast<uintptr_t>(grp.spec[b]) % 16 == 0 && grp.mx[b] && grp.am[b];
+    if (!ok) { set_error("MUSIC: not a group the lean scan kernel takes (N=%d, P=%d, %d batches)", t.N, t.P, grp.n_batches); return DOA_ERR_INVALID_ARG; }
+    ScanPeakArgs pk;
+    pk.cheb = d_cheb; pk.xaxis = peaks.d_x.as<float>(); pk.M = peaks.M; pk.store = store_spectrum;
+    if (t.N == 2) launch_scan_group_n<2>(t, grp, pk, st);
+    else if (t.N == 3) launch_scan_group_n<3>(t, grp, pk, st);
+    else launch_scan_group_n<4>(t, grp, pk, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }

@@ -32,8 +32,30 @@ __device__ __forceinline__ void write_cheb_record(double *__restrict__ o, const 
     o[4] = 2 * uy[3] - 2 * uy[1]; o[5] = -4 * uy[2]; o[6] = -8 * uy[3]; o[7] = 0.0;
 }
 
-template <int N, typename T>
-__global__ __launch_bounds__(64) void music_evd_kernel(const float2 *__restrict__ R, float *__restrict__ coef,
+// Where item g's covariance matrix lives: one array (EvdOne), or the arrays of a group of batches (EvdGroup: kernels.hpp,
+// BatchGroup; item g = batch * n + local).  With n not a multiple of 64 the lanes of a wave sit in different batches, so the
+// batch's pointer is picked per lane: a chain of selects over the table's entries (compile-time indices -- a per-lane
+// index into the kernel arguments would put the table into scratch memory).
+struct EvdOne {
+    const float2 *R;
+    template <int N> __device__ __forceinline__ const float2 *item(int g) const { return R + (size_t)g * (N * N); }
+};
+struct EvdGroup {
+    const float2 *cov[kMaxGroup];
+    GroupSplit split;
+    template <int N> __device__ __forceinline__ const float2 *item(int g) const
+    {
+        unsigned batch, local;
+        split((unsigned)g, batch, local);
+        const float2 *R = cov[0];
+#pragma unroll
+        for (int b = 1; b < kMaxGroup; b++) R = (batch == (unsigned)b) ? cov[b] : R;
+        return R + (size_t)local * (N * N);
+    }
+};
+
+template <int N, typename T, class Src = EvdOne>
+__global__ __launch_bounds__(64) void music_evd_kernel(Src src, float *__restrict__ coef,
                                                        double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                        int n_items, int M, double *__restrict__ cheb_d,
                                                        unsigned long long *__restrict__ fallback_count)
@@ -41,7 +63,7 @@ __global__ __launch_bounds__(64) void music_evd_kernel(const float2 *__restrict_
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= n_items) return;
     T u[2 * N];
-    const float2 *Ri = R + (size_t)item * (N * N);
+    const float2 *__restrict__ Ri = src.template item<N>(item);
     float2 *pn_i = pn_out ? pn_out + (size_t)item * (N * N) : nullptr;
     // double: the signal-subspace iteration first (evd_subspace.hpp, one lane per item); the lanes it does not certify run the
     // cyclic Jacobi below (the whole wave skips it when every lane is done)
@@ -1144,11 +1166,39 @@ template <int N> static void launch_evd_n(int M, int n_items, const void *d_R, v
 {
     dim3 block(64), grid((n_items + 63) / 64);
     if (bits == 32)
-        hipLaunchKernelGGL((music_evd_kernel<N, float>), grid, block, 0, st, (const float2 *)d_R, (float *)d_coef,
+        hipLaunchKernelGGL((music_evd_kernel<N, float>), grid, block, 0, st, EvdOne{(const float2 *)d_R}, (float *)d_coef,
                            (double *)d_coef_d, (float2 *)d_pn, n_items, M, (double *)nullptr, (unsigned long long *)nullptr);
     else
-        hipLaunchKernelGGL((music_evd_kernel<N, double>), grid, block, 0, st, (const float2 *)d_R, (float *)d_coef,
+        hipLaunchKernelGGL((music_evd_kernel<N, double>), grid, block, 0, st, EvdOne{(const float2 *)d_R}, (float *)d_coef,
                            (double *)d_coef_d, (float2 *)d_pn, n_items, M, (double *)d_cheb, evd_fallback_counter());
+}
+
+// the one-lane kernel over a group of batches (music_group_shape_ok shapes: double, and not the quad kernel's N = 4, M = 2)
+template <int N> static void launch_evd_group_n(int M, int n_items, const EvdGroup &src, void *d_coef_d, void *d_cheb, hipStream_t st)
+{
+    dim3 block(64), grid((n_items + 63) / 64);
+    hipLaunchKernelGGL((music_evd_kernel<N, double, EvdGroup>), grid, block, 0, st, src, (float *)nullptr, (double *)d_coef_d,
+                       (float2 *)nullptr, n_items, M, (double *)d_cheb, evd_fallback_counter());
+}
+
+int launch_music_evd_group(int N, int M, const BatchGroup &grp, void *d_coef_d, void *d_cheb, hipStream_t st)
+{
+    if (grp.n_batches <= 0 || grp.n <= 0) return DOA_OK;
+    if (N < 2 || N > 4 || (N == 4 && M == 2) || grp.n_batches > kMaxGroup) {
+        set_error("MUSIC: not a group shape (N=%d, M=%d, %d batches)", N, M, grp.n_batches);
+        return DOA_ERR_INVALID_ARG;
+    }
+    EvdGroup src;
+    for (int b = 0; b < kMaxGroup; b++) src.cov[b] = static_cast<const float2 *>(grp.cov[b < grp.n_batches ? b : 0]);
+    src.split = GroupSplit::make(grp.n);
+    const int n_items = grp.n_batches * grp.n;
+    switch (N) {
+    case 2: launch_evd_group_n<2>(M, n_items, src, d_coef_d, d_cheb, st); break;
+    case 3: launch_evd_group_n<3>(M, n_items, src, d_coef_d, d_cheb, st); break;
+    default: launch_evd_group_n<4>(M, n_items, src, d_coef_d, d_cheb, st); break;
+    }
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
 }
 
 int launch_music_evd(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,

@@ -535,11 +535,32 @@ __device__ __forceinline__ void lean_load_table(const T *__restrict__ ztab, int 
         for (int e = 0; e < 4; e++) asm volatile("" :: "v"(zr[j][e]), "v"(zi[j][e]));
 }
 
-template <int N, int CH, typename T, bool MULTI = false, bool PEAKS = true, bool STORE = true, int ABL = 0>
+// Where item g's row, maximum and arg-max go: one batch's arrays (ScanOne), or those of a group of batches (ScanGroup:
+// kernels.hpp, BatchGroup; item g = batch * n + local, wave-uniform, so the table is read with scalar loads).  The records are
+// read at g in both forms.
+struct ScanItemOut { float *row, *val, *loc; };
+struct ScanOne {
+    float *spec, *val, *loc;
+    __device__ __forceinline__ ScanItemOut item(int g, int P, int M) const
+    {
+        return {spec + (size_t)g * P, val + (size_t)g * M, loc + (size_t)g * M};
+    }
+};
+struct ScanGroup {
+    float *spec[kMaxGroup], *val[kMaxGroup], *loc[kMaxGroup];
+    GroupSplit split;
+    __device__ __forceinline__ ScanItemOut item(int g, int P, int M) const
+    {
+        unsigned batch, local;
+        split((unsigned)g, batch, local);
+        return {spec[batch] + (size_t)local * P, val[batch] + (size_t)local * M, loc[batch] + (size_t)local * M};
+    }
+};
+
+template <int N, int CH, typename T, bool MULTI = false, bool PEAKS = true, bool STORE = true, int ABL = 0, class Out = ScanOne>
 __global__ __launch_bounds__(256) void music_scan_peak1_kernel(const T *__restrict__ coef, const T *__restrict__ ztab,
-                                                               float *__restrict__ spec, int n_items,
-                                                               const float *__restrict__ xaxis, float *__restrict__ pk_val,
-                                                               float *__restrict__ pk_loc, int M)
+                                                               Out out, int n_items,
+                                                               const float *__restrict__ xaxis, int M)
 {
     constexpr int P = 256 * CH;
     constexpr int RL = LeanRecord<N, T>::kLen;
@@ -573,8 +594,8 @@ __global__ __launch_bounds__(256) void music_scan_peak1_kernel(const T *__restri
 #pragma unroll
             for (int i = 0; i < RL; i++) c_next[i] = coef[(size_t)nxt * RL + i];
         }
-        lean_scan_item<N, CH, T, MULTI, PEAKS, STORE, ABL>(c, zr, zi, ztab, spec + (size_t)item * P, xs, pk_val + (size_t)item * M,
-                                                          pk_loc + (size_t)item * M, M, lane, lds_row);
+        const ScanItemOut o = out.item(item, P, M);
+        lean_scan_item<N, CH, T, MULTI, PEAKS, STORE, ABL>(c, zr, zi, ztab, o.row, xs, o.val, o.loc, M, lane, lds_row);
     }
 }
 
@@ -835,6 +856,71 @@ static void launch_scan_fast(dim3 grid, dim3 block, hipStream_t st, const T *co,
                            n_items, nullptr, nullptr, nullptr, 0, n_ant);
 }
 
+// The lean benchmark-shape kernel (music_scan_peak1_kernel) for n_items items whose outputs `out` describes: one batch
+// (ScanOne) or a group of batches (ScanGroup, n_items = the group's total) -- the same grid rule for both.
+template <int N, typename T, class Out>
+static void launch_scan_lean(const T *rec, const T *z, int P, int n_items, const Out &out, bool peaks, const ScanPeakArgs &pk,
+                             hipStream_t st)
+{
+    const int waves_per_block = 4;
+    // lab: workgroup size in waves, 1..4 (the kernels are bounded to 256 threads and their per-wave LDS rows to four)
+    const int lwpb_env = DOA_LAB_ENV_INT("DOA_SCAN_WPB", waves_per_block);
+    const int lwpb = lwpb_env < 1 ? 1 : (lwpb_env > 4 ? 4 : lwpb_env);
+    const dim3 lblock(lwpb * kWave);
+    int lb = (n_items + lwpb - 1) / lwpb;
+    // Waves per CU: 12 up to a few items per wave (the benchmark batch: 2048 waves with two items each; one item per wave
+    // makes every wave pay the 16 KiB table load for 4 KiB of output), 16 -- all the 104-VGPR kernel can hold -- beyond:
+    // at large batches the kernel sits between its two ablations (rows stored without arithmetic, arithmetic without
+    // stores: DESIGN.md section 3) and a fourth wave per SIMD is worth 225-229 against 232-240 us per 262144 items.
+    const int per_wave16 = n_items / (cu_count() * 16);
+    const int lwpc_env = DOA_LAB_ENV_INT("DOA_SCAN_LEAN_WAVES_PER_CU", 0);
+    const int lwpc = lwpc_env > 0 ? lwpc_env : (per_wave16 >= 4 ? 16 : 12);
+    const int cap = cu_count() * lwpc / lwpb;
+    if (lb > cap && !DOA_LAB_ENV_INT("DOA_SCAN_NOTRIM", 0)) {
+        // every wave takes the same number of items (4096 items on a cap of 3072 waves would be one round of 3072 and a
+        // second of 1024 with two thirds of the chip idle: 2048 waves with two items each instead)
+        const int cap_waves = cap * lwpb;
+        const int per_wave = (n_items + cap_waves - 1) / cap_waves;
+        const int waves = (n_items + per_wave - 1) / per_wave;
+        lb = (waves + lwpb - 1) / lwpb;
+    } else if (lb > cap) lb = cap;
+    dim3 lgrid(lb);
+#define DOA_LEAN_LAUNCH(CH_, MULTI_, PEAKS_, STORE_)                                                               \
+    hipLaunchKernelGGL((music_scan_peak1_kernel<N, CH_, T, MULTI_, PEAKS_, STORE_, 0, Out>), lgrid, lblock, 0, st, rec, z,  \
+                       out, n_items, pk.xaxis, pk.M)
+#define DOA_LEAN_CH(MULTI_, PEAKS_, STORE_)                                                                        \
+    do {                                                                                                           \
+        if (P == 256) DOA_LEAN_LAUNCH(1, MULTI_, PEAKS_, STORE_);                                                  \
+        else if (P == 512) DOA_LEAN_LAUNCH(2, MULTI_, PEAKS_, STORE_);                                             \
+        else DOA_LEAN_LAUNCH(4, MULTI_, PEAKS_, STORE_);                                                           \
+    } while (0)
+#ifdef DOA_LAB
+    if constexpr (N == 4 && sizeof(T) == 8 && std::is_same<Out, ScanOne>::value) {
+        // ablations of the graded kernel (results invalid): DOA_SCAN_ABLATE=1 no row stores, =2 row stores only
+        const int ablate = DOA_LAB_ENV_INT("DOA_SCAN_ABLATE", 0);
+        if (ablate && P == 1024 && pk.val && pk.store && pk.M == 1) {
+            if (ablate == 1)
+                hipLaunchKernelGGL((music_scan_peak1_kernel<4, 4, T, false, true, true, 1>), lgrid, lblock, 0, st, rec, z, out, n_items,
+                                   pk.xaxis, pk.M);
+            else
+                hipLaunchKernelGGL((music_scan_peak1_kernel<4, 4, T, false, true, true, 2>), lgrid, lblock, 0, st, rec, z, out, n_items,
+                                   pk.xaxis, pk.M);
+            return;
+        }
+    }
+#endif
+    if (!peaks) {
+        if constexpr (std::is_same<Out, ScanOne>::value) DOA_LEAN_CH(false, false, true);   // (groups always pick peaks)
+    } else if (!pk.store) {                                   // angles only (sp is scratch for irregular rows)
+        if (pk.M == 1) DOA_LEAN_CH(false, true, false);
+        else DOA_LEAN_CH(true, true, false);
+    }
+    else if (pk.M == 1) DOA_LEAN_CH(false, true, true);
+    else DOA_LEAN_CH(true, true, true);
+#undef DOA_LEAN_CH
+#undef DOA_LEAN_LAUNCH
+}
+
 // returns true when the fused peak pick ran (fast path only)
 template <int N, typename T>
 static bool launch_scan_nt(const T *co, const T *z, int P, int n_items, void *d_spec, void *d_q, const ScanPeakArgs &pk,
@@ -856,61 +942,7 @@ static bool launch_scan_nt(const T *co, const T *z, int P, int n_items, void *d_
     constexpr bool kPre = LeanRecord<N, T>::kPre;
     if (aligned && !q && n_ant == N && (P == 256 || P == 512 || P == 1024) && (!kPre || pk.cheb)) {
         const T *rec = kPre ? static_cast<const T *>(pk.cheb) : co;
-        // lab: workgroup size in waves, 1..4 (the kernels are bounded to 256 threads and their per-wave LDS rows to four)
-        const int lwpb_env = DOA_LAB_ENV_INT("DOA_SCAN_WPB", waves_per_block);
-        const int lwpb = lwpb_env < 1 ? 1 : (lwpb_env > 4 ? 4 : lwpb_env);
-        const dim3 lblock(lwpb * kWave);
-        int lb = (n_items + lwpb - 1) / lwpb;
-        // Waves per CU: 12 up to a few items per wave (the benchmark batch: 2048 waves with two items each; one item per wave
-        // makes every wave pay the 16 KiB table load for 4 KiB of output), 16 -- all the 104-VGPR kernel can hold -- beyond:
-        // at large batches the kernel sits between its two ablations (rows stored without arithmetic, arithmetic without
-        // stores: DESIGN.md section 3) and a fourth wave per SIMD is worth 225-229 against 232-240 us per 262144 items.
-        const int per_wave16 = n_items / (cu_count() * 16);
-        const int lwpc_env = DOA_LAB_ENV_INT("DOA_SCAN_LEAN_WAVES_PER_CU", 0);
-        const int lwpc = lwpc_env > 0 ? lwpc_env : (per_wave16 >= 4 ? 16 : 12);
-        const int cap = cu_count() * lwpc / lwpb;
-        if (lb > cap && !DOA_LAB_ENV_INT("DOA_SCAN_NOTRIM", 0)) {
-            // every wave takes the same number of items (4096 items on a cap of 3072 waves would be one round of 3072 and a
-            // second of 1024 with two thirds of the chip idle: 2048 waves with two items each instead)
-            const int cap_waves = cap * lwpb;
-            const int per_wave = (n_items + cap_waves - 1) / cap_waves;
-            const int waves = (n_items + per_wave - 1) / per_wave;
-            lb = (waves + lwpb - 1) / lwpb;
-        } else if (lb > cap) lb = cap;
-        dim3 lgrid(lb);
-#define DOA_LEAN_LAUNCH(CH_, MULTI_, PEAKS_, STORE_)                                                               \
-    hipLaunchKernelGGL((music_scan_peak1_kernel<N, CH_, T, MULTI_, PEAKS_, STORE_>), lgrid, lblock, 0, st, rec, z, sp,  \
-                       n_items, pk.xaxis, pk.val, pk.loc, pk.M)
-#define DOA_LEAN_CH(MULTI_, PEAKS_, STORE_)                                                                        \
-    do {                                                                                                           \
-        if (P == 256) DOA_LEAN_LAUNCH(1, MULTI_, PEAKS_, STORE_);                                                  \
-        else if (P == 512) DOA_LEAN_LAUNCH(2, MULTI_, PEAKS_, STORE_);                                             \
-        else DOA_LEAN_LAUNCH(4, MULTI_, PEAKS_, STORE_);                                                           \
-    } while (0)
-#ifdef DOA_LAB
-        if constexpr (N == 4 && sizeof(T) == 8) {
-            // ablations of the graded kernel (results invalid): DOA_SCAN_ABLATE=1 no row stores, =2 row stores only
-            const int ablate = DOA_LAB_ENV_INT("DOA_SCAN_ABLATE", 0);
-            if (ablate && P == 1024 && pk.val && pk.store && pk.M == 1) {
-                if (ablate == 1)
-                    hipLaunchKernelGGL((music_scan_peak1_kernel<4, 4, T, false, true, true, 1>), lgrid, lblock, 0, st, rec, z, sp, n_items,
-                                       pk.xaxis, pk.val, pk.loc, pk.M);
-                else
-                    hipLaunchKernelGGL((music_scan_peak1_kernel<4, 4, T, false, true, true, 2>), lgrid, lblock, 0, st, rec, z, sp, n_items,
-                                       pk.xaxis, pk.val, pk.loc, pk.M);
-                return true;
-            }
-        }
-#endif
-        if (!pk.val) DOA_LEAN_CH(false, false, true);
-        else if (!pk.store) {                                   // angles only (sp is scratch for irregular rows)
-            if (pk.M == 1) DOA_LEAN_CH(false, true, false);
-            else DOA_LEAN_CH(true, true, false);
-        }
-        else if (pk.M == 1) DOA_LEAN_CH(false, true, true);
-        else DOA_LEAN_CH(true, true, true);
-#undef DOA_LEAN_CH
-#undef DOA_LEAN_LAUNCH
+        launch_scan_lean<N, T>(rec, z, P, n_items, ScanOne{sp, pk.val, pk.loc}, pk.val != nullptr, pk, st);
         return pk.val != nullptr;
     }
     // long spectra without diagnostics: P > 2048 in double.  peak_pick<16> on a register-resident row makes the fused fast
@@ -964,5 +996,18 @@ template <int N> bool launch_scan_n(const MusicTables &t, int bits, int n_items,
     return launch_scan_nt<N, double>((const double *)d_coef, t.d_zd.as<double>(), t.P, n_items, d_spec, d_q, pk, t.N, st);
 }
 
+template <int N> void launch_scan_group_n(const MusicTables &t, const BatchGroup &grp, const ScanPeakArgs &pk, hipStream_t st)
+{
+    static_assert(LeanRecord<N, double>::kPre, "groups read the Chebyshev-form records");
+    ScanGroup out;
+    for (int b = 0; b < kMaxGroup; b++) {
+        const int src = b < grp.n_batches ? b : 0;          // unused entries repeat batch 0: never a wild pointer
+        out.spec[b] = static_cast<float *>(grp.spec[src]);
+        out.val[b] = static_cast<float *>(grp.mx[src]);
+        out.loc[b] = static_cast<float *>(grp.am[src]);
+    }
+    out.split = GroupSplit::make(grp.n);
+    launch_scan_lean<N, double>(static_cast<const double *>(pk.cheb), t.d_zd.as<double>(), t.P, grp.n_batches * grp.n, out, true, pk, st);
+}
 
 }  // namespace doa

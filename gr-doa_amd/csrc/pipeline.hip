@@ -12,6 +12,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
+#include <vector>
 
 namespace doa {
 bool find_local_max_fast_ok(int L, const void *d_in);
@@ -233,6 +235,50 @@ int doa_music_pipeline_set_lanes(doa_music_pipeline_t *h, int n_lanes)
     return DOA_OK;
 }
 
+// ---- work_dev_batches: groups of batches -------------------------------------------------------------------------------
+// On the lean route (no overlap, N <= 4, double, P = 256 / 512 / 1024, the one-lane EVD) consecutive batches of a call form
+// GROUPS, and one K1, one EVD and one scan launch each cover a whole group (kernels.hpp, BatchGroup): the two small kernels
+// are slow at 4096 items because the launch is too small for them, not because of their arithmetic, and K1 pays its fixed
+// cost per launch once per group.  Every other shape keeps one chain of launches per batch (a group of one).
+// Tuning (profiles/grouped_batches.txt; the knobs exist in lab builds only):
+//   * groups rotate over at most kGroupLanes = 2 lanes (the handle's lane count stays the upper bound): one lane's K1 hides the
+//     other's EVD and scan; more lanes add nothing to hide and measured slower;
+//   * on one lane a group takes up to kMaxGroup = 8 batches (the fewer launch boundaries the better); on two lanes up to
+//     kLaneGroup = 4, so that the lanes alternate at a finer grain and -- with the benchmark's eight rotating buffer sets --
+//     at all: a group that aliases an earlier one has to follow it on its lane, and groups of eight would all chain on one;
+//   * a shorter first group (a stagger between the lanes without events) measured within the noise and is not used.
+constexpr int kGroupLanes = 2, kLaneGroup = 4;
+static int group_lanes() { const int v = DOA_LAB_ENV_INT("DOA_GROUP_LANES", kGroupLanes); return v < 1 ? 1 : v; }
+static int group_batches(int lanes)
+{
+    const int v = DOA_LAB_ENV_INT("DOA_GROUP_BATCHES", 0) > 0 ? DOA_LAB_ENV_INT("DOA_GROUP_BATCHES", 0) : (lanes == 1 ? doa::kMaxGroup : kLaneGroup);
+    return v > doa::kMaxGroup ? doa::kMaxGroup : v;
+}
+static int group_first() { return DOA_LAB_ENV_INT("DOA_GROUP_FIRST", 0); }     // batches in a call's first group (0: a full one)
+// Angles-only batches use P floats of scratch per item (rows on the scan's irregular path): their groups are bounded so that a
+// lane's scratch rows stay within kAnglesScratchBytes (or one batch's worth)
+constexpr size_t kAnglesScratchBytes = (size_t)32 << 20;
+
+namespace {
+struct PlanGroup {
+    int b0 = 0, nb = 0, cap = 1, lane = -1, req = -1;
+    bool lean = false, store = false, vec2 = false;
+    bool sync_first = false;        // its outputs alias groups on two different lanes: the lanes are joined on the host first
+};
+// output pointer -> index of the last group that writes it (open addressing; never shrinks within a call)
+struct PtrGroups {
+    std::vector<std::pair<const void *, int>> slot;
+    size_t mask;
+    explicit PtrGroups(size_t n_ptrs) { size_t c = 16; while (c < 2 * n_ptrs) c <<= 1; slot.assign(c, {nullptr, -1}); mask = c - 1; }
+    std::pair<const void *, int> &at(const void *p)
+    {
+        size_t i = (reinterpret_cast<uintptr_t>(p) * 0x9E3779B97F4A7C15ull >> 20) & mask;
+        while (slot[i].first && slot[i].first != p) i = (i + 1) & mask;
+        return slot[i];
+    }
+};
+}  // namespace
+
 int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, int noutput_items,
                                         const void *const *d_input_items, void *const *d_cov_out,
                                         void *const *d_spectrum_out, void *const *d_max_out, void *const *d_argmax_out,
@@ -254,26 +300,84 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         }
     if (n_batches == 0 || noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->N;
+    const int N = h->N, n = noutput_items, P = h->peaks.L;
     const int fail_at = h->lanes.fail_batch;
-    h->fail_chunk = -1;                                          // (the test aid is one-shot for whichever entry comes next)
-    if (h->lanes.n_lanes == 1 && hip_stream != DOA_STREAM_DETACHED) {     // nothing to overlap: the caller's stream itself, no events
-        hipStream_t caller = static_cast<hipStream_t>(hip_stream);
-        h->lanes.fail_batch = -1;
-        for (int b = 0; b < n_batches; b++) {
-            if (fail_at == b) {
-                doa::set_error("music_pipeline_work_dev_batches: injected failure in batch %d", b);
-                (void)hipStreamSynchronize(caller);              // the contract of an error return: nothing of the call still runs
-                return DOA_ERR_HIP;
-            }
-            void *cov = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : h->d_cov.p;
-            const int rc = run_dev(h, noutput_items, d_input_items + (size_t)b * N, cov, d_spectrum_out ? d_spectrum_out[b] : nullptr,
-                                   d_max_out[b], d_argmax_out[b], 0, caller);
-            if (rc < 0) { (void)hipStreamSynchronize(caller); return rc; }
-        }
-        return n_batches * noutput_items;
-    }
+    h->fail_chunk = -1; h->lanes.fail_batch = -1;               // (the test aid is one-shot for whichever entry comes next)
+    const bool injected = (fail_at >= 0 && fail_at < n_batches);
+    const int n_run = injected ? fail_at : n_batches;           // batches before the injected failure are launched
+    const bool solo = (h->lanes.n_lanes == 1 && hip_stream != DOA_STREAM_DETACHED);    // nothing to overlap: the caller's stream itself, no events
     const bool dbl = (h->bits == 64);
+
+    // ---- the plan: groups of consecutive batches and their lanes ----
+    const bool lean_shape = h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
+                            (long long)doa::kMaxGroup * n <= (1 << 28);
+    const int L_all = solo ? 1 : h->lanes.n_lanes;
+    const int L = (lean_shape && group_lanes() < L_all) ? group_lanes() : L_all;
+    const int G = lean_shape ? group_batches(L) : 1;
+    const size_t angles_rows = kAnglesScratchBytes / ((size_t)h->max_batch * P * sizeof(float));
+    const int G_angles = (int)(angles_rows < 1 ? 1 : (angles_rows > (size_t)G ? (size_t)G : angles_rows));
+    int rot = h->lanes.next_lane % L;
+    std::vector<PlanGroup> plan;
+    plan.reserve((size_t)n_run / G + 8);
+    PtrGroups writers((size_t)4 * n_run);
+    auto outputs = [&](int b, const void *(&p)[4]) {
+        p[0] = d_cov_out ? d_cov_out[b] : nullptr; p[1] = d_spectrum_out ? d_spectrum_out[b] : nullptr;
+        p[2] = d_max_out[b]; p[3] = d_argmax_out[b];
+    };
+    auto close = [&](PlanGroup &g) {
+        g.lane = (g.req >= 0) ? g.req : rot++ % L;
+    };
+    for (int b = 0; b < n_run; b++) {
+        const void *out[4];
+        outputs(b, out);
+        PlanGroup nb;
+        nb.b0 = b; nb.nb = 1;
+        nb.store = (out[1] != nullptr);
+        nb.lean = lean_shape && reinterpret_cast<uintptr_t>(out[1]) % 16 == 0;
+        nb.vec2 = nb.lean && doa::autocorrelate_pair_loads(N, h->K, h->ovl, d_input_items + (size_t)b * N, h->format);
+        nb.cap = !nb.lean ? 1 : (nb.store ? G : G_angles);
+        if (plan.empty() && group_first() > 0 && group_first() < nb.cap) nb.cap = group_first();
+        // which earlier groups write this batch's outputs: the open one (-> the batch starts a new group), closed ones (-> their lane)
+        const int open = plan.empty() ? -1 : (int)plan.size() - 1;
+        auto requirement = [&](int open_index, bool &in_open, bool &conflict) {
+            int req = -1;
+            in_open = conflict = false;
+            for (const void *p : out) {
+                if (!p) continue;
+                const int gi = writers.at(p).second;
+                if (gi < 0) continue;
+                if (gi == open_index) { in_open = true; continue; }
+                if (req >= 0 && req != plan[gi].lane) conflict = true;
+                req = plan[gi].lane;
+            }
+            return req;
+        };
+        bool in_open, conflict;
+        int req = requirement(open, in_open, conflict);
+        bool join = false;
+        if (open >= 0) {
+            const PlanGroup &g = plan[open];
+            join = g.lean && nb.lean && g.nb < g.cap && g.store == nb.store && g.vec2 == nb.vec2 && !in_open && !conflict &&
+                   (req < 0 || g.req < 0 || g.req == req);
+        }
+        if (join) {
+            plan[open].nb++;
+            if (req >= 0) plan[open].req = req;
+        } else {
+            if (open >= 0) {
+                close(plan[open]);
+                req = requirement(-1, in_open, conflict);       // (the group just closed has a lane now)
+            }
+            nb.req = req; nb.sync_first = conflict;
+            plan.push_back(nb);
+        }
+        for (const void *p : out)
+            if (p) writers.at(p) = {p, (int)plan.size() - 1};
+    }
+    if (!plan.empty()) close(plan.back());
+    h->lanes.next_lane = rot % L;
+
+    // ---- workspaces and launches ----
     bool need_cov = !d_cov_out, need_spec = !d_spectrum_out;
     for (int b = 0; b < n_batches && !(need_cov && need_spec); b++) {
         if (d_cov_out && !d_cov_out[b]) need_cov = true;
@@ -281,24 +385,76 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     }
     const size_t work_bytes = doa::autocorrelate_workspace_bytes(N, h->K, h->ovl, h->max_batch);
     using H = doa_music_pipeline;
-    auto prepare = [&](doa::PipeLane &ln) -> int {
-        int rc = ln.buf[H::kCoef].reserve((size_t)h->max_batch * doa::coef_stride(N) * (dbl ? sizeof(double) : sizeof(float)));
-        if (rc == DOA_OK && doa::music_uses_cheb(N, h->bits)) rc = ln.buf[H::kCheb].reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double));
-        if (rc == DOA_OK && need_cov) rc = ln.buf[H::kCov].reserve((size_t)h->max_batch * N * N * sizeof(float2));
-        if (rc == DOA_OK && need_spec) rc = ln.buf[H::kSpec].reserve((size_t)h->max_batch * h->peaks.L * sizeof(float));
-        if (rc == DOA_OK && work_bytes) rc = ln.buf[H::kWork].reserve(work_bytes);
+    // a lane's buffers hold a whole group: records and covariances are 64-128 B per item; the angles-only scratch rows are bounded (G_angles)
+    auto reserve = [&](doa::DevBuf &coef, doa::DevBuf &cheb, doa::DevBuf &cov, doa::DevBuf &spec, doa::DevBuf &work) -> int {
+        int rc = coef.reserve((size_t)h->max_batch * doa::coef_stride(N) * (dbl ? sizeof(double) : sizeof(float)));
+        if (rc == DOA_OK && doa::music_uses_cheb(N, h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
+        if (rc == DOA_OK && need_cov) rc = cov.reserve((size_t)G * h->max_batch * N * N * sizeof(float2));
+        if (rc == DOA_OK && need_spec) rc = spec.reserve((size_t)G_angles * h->max_batch * P * sizeof(float));
+        if (rc == DOA_OK && work_bytes) rc = work.reserve(work_bytes);
         return rc;
     };
-    auto launch = [&](int b, doa::PipeLane &ln) -> int {
+    auto launch = [&](const PlanGroup &g, const PipeWs &ws, void *lane_cov, hipStream_t st) -> int {
+        if (!g.lean || g.nb == 1) {                              // one batch: the launches of work_dev
+            int rc = DOA_OK;
+            for (int b = g.b0; b < g.b0 + g.nb && rc >= 0; b++) {
+                void *cov = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : lane_cov;
+                rc = run_ws(h, n, d_input_items + (size_t)b * N, cov, d_spectrum_out ? d_spectrum_out[b] : nullptr, d_max_out[b],
+                            d_argmax_out[b], ws, st);
+            }
+            return rc;
+        }
+        doa::BatchGroup grp;
+        grp.n_batches = g.nb; grp.n = n;
+        for (int k = 0; k < g.nb; k++) {
+            const int b = g.b0 + k;
+            grp.in[k] = d_input_items + (size_t)b * N;
+            grp.cov[k] = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : static_cast<char *>(lane_cov) + (size_t)k * n * N * N * sizeof(float2);
+            grp.spec[k] = g.store ? d_spectrum_out[b] : static_cast<char *>(ws.spec_scratch) + (size_t)k * n * P * sizeof(float);
+            grp.mx[k] = d_max_out[b]; grp.am[k] = d_argmax_out[b];
+        }
+        const unsigned skip = ~h->stages & 7u;                   // doa_music_pipeline_set_stages
+        int rc = DOA_OK;
+        if (!(skip & 1)) rc = doa::launch_autocorrelate_group(N, h->K, h->avg, grp, st, h->has_gain ? h->d_gain.p : nullptr, h->format, h->scale);
+        if (rc == DOA_OK && !(skip & 2)) rc = doa::launch_music_evd_group(N, h->music.M, grp, nullptr, ws.cheb, st);
+        if (rc == DOA_OK && !(skip & 4)) rc = doa::launch_music_scan_group(h->music, h->peaks, grp, ws.cheb, g.store, st);
+        return rc;
+    };
+    if (solo) {
+        hipStream_t caller = static_cast<hipStream_t>(hip_stream);
+        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0]);
+        if (rc != DOA_OK) return rc;
+        PipeWs ws;
+        ws.coef = h->d_coef.p; ws.cheb = h->d_cheb.p; ws.spec_scratch = h->d_spec.p; ws.work = h->d_work[0].p;
+        ws.scratch = &h->d_scratch; ws.scratch_item_off = 0;
+        for (size_t u = 0; u < plan.size() && rc >= 0; u++) rc = launch(plan[u], ws, h->d_cov.p, caller);
+        if (rc >= 0 && injected) {
+            doa::set_error("music_pipeline_work_dev_batches: injected failure in batch %d", fail_at);
+            rc = DOA_ERR_HIP;
+        }
+        if (rc < 0) {
+            const std::string msg = doa_last_error();
+            (void)hipStreamSynchronize(caller);                  // the contract of an error return: nothing of the call still runs
+            doa::set_error("%s", msg.c_str());
+            return rc;
+        }
+        return n_batches * n;
+    }
+    auto prepare = [&](doa::PipeLane &ln) -> int {
+        return reserve(ln.buf[H::kCoef], ln.buf[H::kCheb], ln.buf[H::kCov], ln.buf[H::kSpec], ln.buf[H::kWork]);
+    };
+    auto launch_unit = [&](int u, doa::PipeLane &ln) -> int {
+        const PlanGroup &g = plan[u];
+        if (g.sync_first)
+            if (const int rc = h->lanes.synchronize(); rc != DOA_OK) return rc;
         PipeWs ws;
         ws.coef = ln.buf[H::kCoef].p; ws.cheb = ln.buf[H::kCheb].p; ws.spec_scratch = ln.buf[H::kSpec].p; ws.work = ln.buf[H::kWork].p;
         ws.scratch = &ln.buf[H::kScratch]; ws.scratch_item_off = 0;
-        void *cov = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : ln.buf[H::kCov].p;
-        return run_ws(h, noutput_items, d_input_items + (size_t)b * N, cov, d_spectrum_out ? d_spectrum_out[b] : nullptr, d_max_out[b],
-                      d_argmax_out[b], ws, ln.st);
+        return launch(g, ws, ln.buf[H::kCov].p, ln.st);
     };
-    const int rc = h->lanes.run_batches("music_pipeline_work_dev_batches", n_batches, hip_stream, prepare, launch);
-    return rc < 0 ? rc : n_batches * noutput_items;
+    const int rc = h->lanes.run_units("music_pipeline_work_dev_batches", (int)plan.size(), injected ? fail_at : -1, hip_stream, prepare,
+                                      [&](int u) { return plan[u].lane; }, launch_unit);
+    return rc < 0 ? rc : n_batches * n;
 }
 
 int doa_music_pipeline_set_lane_streams(doa_music_pipeline_t *h, int n_lanes, void *const *hip_streams)

@@ -82,21 +82,36 @@ struct PipeLanes {
         return true;
     }
 
-    // Batch b of the call runs launch(b, lane) on lane (next_lane + b) % n_lanes, in order on that lane.  `prepare(lane)` sizes
-    // a lane's buffers (first use / growth); `launch` returns < 0 on failure.  Attached to a stream, the call forks (every lane
-    // waits for what the caller's stream holds now: one event) and joins (the caller's stream waits for every lane: one event
-    // per lane) ONCE, whatever n_batches is: cross-stream events cost tens of microseconds on this runtime and an event per
-    // batch degrades the lanes to the serial rate -- hence also the detached form (caller == DETACHED: no
-    // event at all, the caller joins with synchronize()).
-    // Error contract: whatever fails, from the first lane operation on, the join is still enqueued and -- on an error return --
-    // every lane the call used has been synchronised: "nothing of a failed call is still running", the detached form included.
+    // Batch b of the call runs launch(b, lane) on lane (next_lane + b) % n_lanes, in order on that lane: run_units with one
+    // batch per unit.  doa_*_pipeline_inject_failure(b): batches before b are launched, then the call fails.
     template <class Prepare, class Launch>
     int run_batches(const char *what, int n_batches, void *hip_stream, Prepare prepare, Launch launch)
     {
-        const bool detached = (hip_stream == DOA_STREAM_DETACHED);
-        hipStream_t caller = detached ? nullptr : static_cast<hipStream_t>(hip_stream);
         const int fail_at = fail_batch;
         fail_batch = -1;                                   // one-shot: armed for THIS call only, wherever it ends
+        const int L = n_lanes;
+        const int lane0 = next_lane % L;
+        next_lane = (lane0 + n_batches) % L;
+        const bool injected = (fail_at >= 0 && fail_at < n_batches);
+        return run_units(what, injected ? fail_at : n_batches, injected ? fail_at : -1, hip_stream, prepare,
+                         [&](int u) { return (lane0 + u) % L; }, launch);
+    }
+
+    // The general form: unit u (a batch, or a group of batches) runs launch(u, lane) on lane lane_of(u) (< n_lanes), units of
+    // one lane in order.  `prepare(lane)` sizes a lane's buffers (first use / growth); `launch` returns < 0 on failure.
+    // failed_batch >= 0: after the units the call fails as "injected failure in batch <failed_batch>" (the test aid; the caller
+    // has left that batch and the ones behind it out of the units).  Attached to a stream, the call forks (every lane it uses
+    // waits for what the caller's stream holds now: one event) and joins (the caller's stream waits for every such lane: one
+    // event per lane) ONCE, whatever the number of units is: cross-stream events cost tens of microseconds on this runtime and
+    // an event per batch degrades the lanes to the serial rate -- hence also the detached form (caller ==
+    // DETACHED: no event at all, the caller joins with synchronize()).
+    // Error contract: whatever fails, from the first lane operation on, the join is still enqueued and -- on an error return --
+    // every lane the call used has been synchronised: "nothing of a failed call is still running", the detached form included.
+    template <class Prepare, class LaneOf, class Launch>
+    int run_units(const char *what, int n_units, int failed_batch, void *hip_stream, Prepare prepare, LaneOf lane_of, Launch launch)
+    {
+        const bool detached = (hip_stream == DOA_STREAM_DETACHED);
+        hipStream_t caller = detached ? nullptr : static_cast<hipStream_t>(hip_stream);
         const int L = n_lanes;
         // set-up that cannot leave work behind: failures here return at once
         if (!detached && !fork_ev) DOA_HIP_TRY(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
@@ -111,40 +126,42 @@ struct PipeLanes {
                     if (!lanes[l].st) { lanes[l].st = fresh[n_new++]; lanes[l].own_stream = true; }
             }
         }
+        unsigned used = 0;                                 // bit l: lane l runs a unit of this call
+        for (int u = 0; u < n_units; u++) used |= 1u << lane_of(u);
         for (int l = 0; l < L; l++) {
             auto &ln = lanes[l];
             if (!detached && !ln.done) DOA_HIP_TRY(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
+            if (!((used >> l) & 1u)) continue;
             if (const int rc = prepare(ln); rc != DOA_OK) return rc;
         }
-        const int lane0 = next_lane % L;
-        next_lane = (lane0 + n_batches) % L;
-        const int used = n_batches < L ? n_batches : L;
         int rc = DOA_OK;
         auto fail = [&](hipError_t e, const char *step) {
             if (e != hipSuccess && rc >= 0) { set_error("%s: %s failed: %s", what, step, hipGetErrorString(e)); rc = DOA_ERR_HIP; }
         };
         // fork: from here on every exit goes through the join and, on failure, the lane synchronisation below
-        if (!detached) {
+        if (!detached && used) {
             fail(hipEventRecord(fork_ev, caller), "fork record");
-            for (int u = 0; u < used && rc >= 0; u++) fail(hipStreamWaitEvent(lanes[(lane0 + u) % L].st, fork_ev, 0), "fork wait");
+            for (int l = 0; l < L && rc >= 0; l++)
+                if ((used >> l) & 1u) fail(hipStreamWaitEvent(lanes[l].st, fork_ev, 0), "fork wait");
         }
-        for (int b = 0; b < n_batches && rc >= 0; b++) {
-            if (fail_at == b) {
-                set_error("%s: injected failure in batch %d", what, b);
-                rc = DOA_ERR_HIP;
-                break;
-            }
-            const int r = launch(b, lanes[(lane0 + b) % L]);
+        for (int u = 0; u < n_units && rc >= 0; u++) {
+            const int r = launch(u, lanes[lane_of(u)]);
             if (r < 0) rc = r;
         }
-        for (int u = 0; u < used && !detached; u++) {
-            auto &ln = lanes[(lane0 + u) % L];
+        if (rc >= 0 && failed_batch >= 0) {
+            set_error("%s: injected failure in batch %d", what, failed_batch);
+            rc = DOA_ERR_HIP;
+        }
+        for (int l = 0; l < L && !detached; l++) {
+            if (!((used >> l) & 1u)) continue;
+            auto &ln = lanes[l];
             const hipError_t e1 = hipEventRecord(ln.done, ln.st);
             fail(e1 == hipSuccess ? hipStreamWaitEvent(caller, ln.done, 0) : e1, "join");
         }
         if (rc < 0) {
             const std::string msg = doa_last_error();
-            for (int u = 0; u < used; u++) (void)hipStreamSynchronize(lanes[(lane0 + u) % L].st);
+            for (int l = 0; l < L; l++)
+                if ((used >> l) & 1u) (void)hipStreamSynchronize(lanes[l].st);
             set_error("%s", msg.c_str());
         }
         return rc;

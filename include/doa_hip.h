@@ -307,12 +307,23 @@ DOA_HIP_API int doa_music_pipeline_work_dev(doa_music_pipeline_t *h, int noutput
                                             void *d_spectrum_out, void *d_max_out,
                                             void *d_argmax_out, void *hip_stream);
 /* n_batches independent batches of noutput_items snapshots each (<= max_batch) in ONE call, overlapped by the library:
- * batch b runs its K1 -> EVD -> scan chain on one of the handle's own LANES (a HIP stream plus a private workspace; 4
+ * the batches run their K1 -> EVD -> scan chains on the handle's own LANES (a HIP stream plus a private workspace; 4
  * by default, rotating from call to call), so that the HBM-bound covariance kernel of one batch runs beside the
  * issue-bound EVD / scan kernels of its neighbours -- the overlap a caller otherwise has to build from several handles on
  * several streams of its own (reference work being chained: lib/autocorrelate_impl.cc:83-118 ->
  * lib/MUSIC_lin_array_impl.cc:121-142 -> lib/find_local_max_impl.cc:167-194, wiring
  * apps/run_MUSIC_lin_array_simulation.grc:1099-1370).  Results are bit-identical to n_batches work_dev calls.
+ *   GROUPS: on the lean route (no overlap, inputs <= 4, double inside, pspectrum_len 256 / 512 / 1024, and not inputs = 4
+ *   with two targets) consecutive batches are launched together -- ONE covariance, ONE eigen and ONE scan launch cover a
+ *   group of up to 8 batches on one lane, up to 4 when the groups alternate over two lanes; a group
+ *   ends early where the next batch differs in wanting a spectrum, in the alignment of its streams or of its spectrum
+ *   pointer, or writes a buffer a batch of the group writes.  Every other shape runs one chain of launches per batch.
+ *   ORDER: groups (batches) on one lane run in order, lanes run side by side.  Two batches of a call that share an OUTPUT
+ *   buffer (covariance, spectrum, maxima or arg-max pointer) run in the order of the call: the later one follows the
+ *   earlier one on its lane (if its outputs were last written on two different lanes, the call waits on the host for the
+ *   lanes first), so the later batch's results are the ones that stay.  Batches that share no output buffer are not
+ *   ordered, and nothing orders a batch's INPUTS against another batch's outputs.  Between calls the attached form orders
+ *   everything through the caller's stream; in the detached form the caller joins with doa_music_pipeline_synchronize.
  *   d_input_items   HOST array of n_batches * inputs DEVICE pointers (batch b: entries b*inputs .. b*inputs+inputs-1)
  *   d_cov_out, d_spectrum_out  HOST arrays of n_batches DEVICE pointers; the array or single entries may be NULL (no
  *                   covariance copy wanted / angles-only mode for that batch, as in work_dev)
@@ -332,7 +343,8 @@ DOA_HIP_API int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int
                                                     void *const *d_argmax_out, void *hip_stream);
 /* Host-side join: returns when every lane of the handle has finished what work_dev_batches gave it. */
 DOA_HIP_API int doa_music_pipeline_synchronize(doa_music_pipeline_t *h);
-/* Number of lanes work_dev_batches spreads its batches over (1..8, default 4; 1 = everything on hip_stream itself). */
+/* Upper bound of the lanes work_dev_batches spreads its batches over (1..8, default 4; 1 = everything on hip_stream
+ * itself); grouped launches (above) use at most two of them. */
 DOA_HIP_API int doa_music_pipeline_set_lanes(doa_music_pipeline_t *h, int n_lanes);
 /* Lanes on streams the CALLER created (n_lanes hipStream_t; they stay the caller's, the handle only uses them).  For a
  * host program that draws its streams from a pool of its own (PyTorch, a GNU Radio buffer manager): HIP maps streams
