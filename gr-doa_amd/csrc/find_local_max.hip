@@ -19,6 +19,9 @@
 // walks positions 64k..64k+63; peak_device.hpp: peak_pick_stream<true>); at most 64 elements of such a vector:
 // find_local_max_stream_kernel (sign masks in SGPRs, nothing of the vector in registers); beyond 4096 elements a
 // one-thread-per-vector fallback walks the reference's steps literally.
+// Every kernel is instantiated twice: with the handle's num_max_vals for all items (PeakFixedM), and with a count m_i per item
+// read from an int32 array (PeakCounts): the same code, the item's first m_i slots written by the same peak
+// pick with M = m_i, the other slots of the num_max_vals-wide item NaN.
 #include "kernels.hpp"
 #include "peak_device.hpp"
 
@@ -44,11 +47,35 @@ int PeakTables::build(int num_max_vals, int vector_len, float x_min_, float x_ma
     return DOA_OK;
 }
 
-template <int CH>
+// How many peaks an item wants.  width(): floats per output item; begin(): the item's M for the peak pick (wave-uniform).
+struct PeakFixedM {
+    static constexpr bool kCounted = false;
+    int M;
+    __device__ __forceinline__ int width() const { return M; }
+    __device__ __forceinline__ int begin(int, int, float *, float *) const { return M; }
+};
+// m_i = counts[item]; the slots the pick will not write (all of them for m_i outside 0..M) are set to NaN here by lanes
+// m_i..M-1 (M <= DOA_MAX_PEAKS < 64); returns 0 when there is nothing to pick
+struct PeakCounts {
+    static constexpr bool kCounted = true;
+    const int *counts;
+    int M;
+    __device__ __forceinline__ int width() const { return M; }
+    __device__ __forceinline__ int begin(int item, int lane, float *ov, float *ol) const
+    {
+        const int m = counts[item];
+        const int mm = (m >= 0 && m <= M) ? m : 0;
+        if (lane < M && lane >= mm) { ov[lane] = NAN; ol[lane] = NAN; }
+        return mm;
+    }
+};
+
+template <int CH, class MS>
 __global__ __launch_bounds__(256) void find_local_max_kernel(const float *__restrict__ in, const float *__restrict__ xaxis,
                                                              float *__restrict__ out_val, float *__restrict__ out_loc,
-                                                             int L, int M, int n_items)
+                                                             int L, MS ms, int n_items)
 {
+    const int W = ms.width();
     const int lane = threadIdx.x & (kWave - 1);
     const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
     if (item >= n_items) return;
@@ -65,20 +92,26 @@ __global__ __launch_bounds__(256) void find_local_max_kernel(const float *__rest
             v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.f;
         }
     }
-    peak_pick<CH>(v, lane, L, M, xaxis, out_val + (size_t)item * M, out_loc + (size_t)item * M);
+    const int M = ms.begin(item, lane, out_val + (size_t)item * W, out_loc + (size_t)item * W);
+    if (MS::kCounted && M == 0) return;
+    peak_pick<CH>(v, lane, L, M, xaxis, out_val + (size_t)item * W, out_loc + (size_t)item * W);
 }
 
 // Long or oddly sized vectors (any 1 <= L <= 4096, any alignment): peak_pick_stream (peak_device.hpp) straight
 // out of global memory.
+template <class MS>
 __global__ __launch_bounds__(256) void find_local_max_stream_kernel(const float *__restrict__ in, const float *__restrict__ xaxis,
                                                                     float *__restrict__ out_val, float *__restrict__ out_loc,
-                                                                    int L, int M, int n_items)
+                                                                    int L, MS ms, int n_items)
 {
+    const int W = ms.width();
     const int lane = threadIdx.x & (kWave - 1);
     const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
     if (item >= n_items) return;
     const float *v_in = in + (size_t)item * L;
-    peak_pick_stream([&](int p) { return v_in[p]; }, L, M, xaxis, out_val + (size_t)item * M, out_loc + (size_t)item * M, lane);
+    const int M = ms.begin(item, lane, out_val + (size_t)item * W, out_loc + (size_t)item * W);
+    if (MS::kCounted && M == 0) return;
+    peak_pick_stream([&](int p) { return v_in[p]; }, L, M, xaxis, out_val + (size_t)item * W, out_loc + (size_t)item * W, lane);
 }
 
 // The same through LDS (any 64 < L <= 4096, any alignment): the vector is fetched once with coalesced loads into a row
@@ -86,15 +119,16 @@ __global__ __launch_bounds__(256) void find_local_max_stream_kernel(const float 
 // positions 64k .. 64k+63 of the row, conflict-free.  Per 4096 vectors of 4096 values: 16.8-17.7 us against the 23.0-24.3 of the
 // streaming mask kernel on MUSIC spectra, 29 against 125 on vectors with a peak every few positions.
 // BS = positions per lane: 64 for vectors of up to 4096 values, 16 up to 1024 (all lanes busy).
-template <int BS>
+template <int BS, class MS>
 __global__ __launch_bounds__(256) void find_local_max_blocked_kernel(const float *__restrict__ in, const float *__restrict__ xaxis,
                                                                      float *__restrict__ out_val, float *__restrict__ out_loc,
-                                                                     int L, int M, int n_items, int vec4)
+                                                                     int L, MS ms, int n_items, int vec4)
 {
     constexpr int LMAX = 64 * BS;
     constexpr int LOG_BS = (BS == 16) ? 4 : 6;
     static_assert(BS == 16 || BS == 64, "block size");
     __shared__ float rows[4][LMAX + 64 + 4];
+    const int W = ms.width();
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = threadIdx.x / kWave;
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + wib);
@@ -132,7 +166,9 @@ __global__ __launch_bounds__(256) void find_local_max_blocked_kernel(const float
             // the fences only keep the compiler from moving them)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             if (item + n_waves < n_items) fetch(item + n_waves);
-            peak_pick_stream<true, BS>(PaddedRow{lrow, lrow + (BS + 1) * lane}, L, M, xaxis, out_val + (size_t)item * M, out_loc + (size_t)item * M, lane);
+            const int M = ms.begin(item, lane, out_val + (size_t)item * W, out_loc + (size_t)item * W);
+            if (!MS::kCounted || M > 0)
+            peak_pick_stream<true, BS>(PaddedRow{lrow, lrow + (BS + 1) * lane}, L, M, xaxis, out_val + (size_t)item * W, out_loc + (size_t)item * W, lane);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         }
         return;
@@ -142,19 +178,30 @@ __global__ __launch_bounds__(256) void find_local_max_blocked_kernel(const float
 #pragma unroll 4
         for (int p = lane; p < L; p += kWave) lrow[p + (p >> LOG_BS)] = __builtin_nontemporal_load(v_in + p);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        peak_pick_stream<true, BS>(PaddedRow{lrow, lrow + (BS + 1) * lane}, L, M, xaxis, out_val + (size_t)item * M, out_loc + (size_t)item * M, lane);
+        const int M = ms.begin(item, lane, out_val + (size_t)item * W, out_loc + (size_t)item * W);
+        if (!MS::kCounted || M > 0)
+        peak_pick_stream<true, BS>(PaddedRow{lrow, lrow + (BS + 1) * lane}, L, M, xaxis, out_val + (size_t)item * W, out_loc + (size_t)item * W, lane);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
 }
 
 // Literal walk of the reference's steps, one thread per vector (any L >= 1).  `scratch` holds L
 // signed bytes per item.
-__global__ void find_local_max_serial_kernel(const float *__restrict__ in, const float *__restrict__ xaxis,
-                                             float *__restrict__ out_val, float *__restrict__ out_loc,
-                                             signed char *__restrict__ scratch, int L, int M, int n_items)
+// counts != nullptr: M = counts[item] for this item (W = the width of the output items), the other slots NaN
+__device__ __forceinline__ void find_local_max_serial_body(const float *__restrict__ in, const float *__restrict__ xaxis,
+                                                           float *__restrict__ out_val, float *__restrict__ out_loc,
+                                                           signed char *__restrict__ scratch, int L, int M, int n_items,
+                                                           const int *__restrict__ counts)
 {
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= n_items) return;
+    const int W = M;
+    if (counts) {
+        const int m = counts[item];
+        M = (m >= 0 && m <= W) ? m : 0;
+        for (int j = M; j < W; j++) { out_val[(size_t)item * W + j] = NAN; out_loc[(size_t)item * W + j] = NAN; }
+        if (M == 0) return;
+    }
     const float *v = in + (size_t)item * L;
     signed char *s = scratch + (size_t)item * L;
     int pkidx[DOA_MAX_PEAKS];
@@ -192,20 +239,34 @@ __global__ void find_local_max_serial_kernel(const float *__restrict__ in, const
         for (int j = rounds; j < M; j++) pkidx[j] = fill;
     }
     float loc[DOA_MAX_PEAKS];
-    for (int j = 0; j < M; j++) { out_val[(size_t)item * M + j] = v[pkidx[j]]; loc[j] = xaxis[pkidx[j]]; }
+    for (int j = 0; j < M; j++) { out_val[(size_t)item * W + j] = v[pkidx[j]]; loc[j] = xaxis[pkidx[j]]; }
     for (int a = 1; a < M; a++) {
         const float t = loc[a];
         int b = a - 1;
         while (b >= 0 && loc[b] < t) { loc[b + 1] = loc[b]; b--; }
         loc[b + 1] = t;
     }
-    for (int j = 0; j < M; j++) out_loc[(size_t)item * M + j] = loc[j];
+    for (int j = 0; j < M; j++) out_loc[(size_t)item * W + j] = loc[j];
+}
+__global__ void find_local_max_serial_kernel(const float *__restrict__ in, const float *__restrict__ xaxis,
+                                             float *__restrict__ out_val, float *__restrict__ out_loc,
+                                             signed char *__restrict__ scratch, int L, int M, int n_items)
+{
+    find_local_max_serial_body(in, xaxis, out_val, out_loc, scratch, L, M, n_items, nullptr);
+}
+__global__ void find_local_max_serial_counts_kernel(const float *__restrict__ in, const float *__restrict__ xaxis,
+                                                    float *__restrict__ out_val, float *__restrict__ out_loc,
+                                                    signed char *__restrict__ scratch, int L, int M, int n_items,
+                                                    const int *__restrict__ counts)
+{
+    find_local_max_serial_body(in, xaxis, out_val, out_loc, scratch, L, M, n_items, counts);
 }
 
 
 
-int launch_find_local_max(const PeakTables &t, int n_items, const void *d_in, void *d_max, void *d_argmax,
-                          hipStream_t st)
+// the routes of K5; d_counts == nullptr: the handle's M for every item
+static int launch_find_local_max_routes(const PeakTables &t, int n_items, const void *d_in, const int *d_counts, void *d_max,
+                                        void *d_argmax, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
     const int L = t.L, M = t.M;
@@ -216,6 +277,7 @@ int launch_find_local_max(const PeakTables &t, int n_items, const void *d_in, vo
         set_error("find_local_max: vector_len=%d needs the serial path (call through a handle)", L);
         return DOA_ERR_UNSUPPORTED;
     }
+    const PeakCounts pc{d_counts, M};
     dim3 block(256), grid((n_items + 3) / 4);
     // short, 16-byte aligned vectors of a multiple-of-4 length: the vector lives in registers (CH float4 per
     // lane); everything else up to 4096 elements: the LDS-staged blocked kernel (46.5 -> 23.7 -> 17 us per 4096 vectors of
@@ -223,25 +285,53 @@ int launch_find_local_max(const PeakTables &t, int n_items, const void *d_in, vo
     const bool reg_ok = (L % 4 == 0) && L >= 4 && (reinterpret_cast<uintptr_t>(d_in) % 16 == 0);
     const bool use_reg = reg_ok && L <= 1024;
     const int k5_lab = DOA_LAB_ENV_INT("DOA_K5_STREAM", 0);      // lab: 1 = streaming mask kernel, 2 = register kernel for M > 1 too
+    // every route: the fixed-M kernel, or its per-item-count twin
     if (L > 1024 && k5_lab != 1) {
         // 65 KiB of LDS per 4-wave workgroup: two per CU
         int bb = (n_items + 3) / 4;
         if (bb > cu_count() * 2) bb = cu_count() * 2;
-        hipLaunchKernelGGL(find_local_max_blocked_kernel<64>, dim3(bb), block, 0, st, in, x, ov, ol, L, M, n_items, reg_ok ? 1 : 0);
+        if (d_counts) hipLaunchKernelGGL((find_local_max_blocked_kernel<64, PeakCounts>), dim3(bb), block, 0, st, in, x, ov, ol, L, pc, n_items, reg_ok ? 1 : 0);
+        else hipLaunchKernelGGL((find_local_max_blocked_kernel<64, PeakFixedM>), dim3(bb), block, 0, st, in, x, ov, ol, L, PeakFixedM{M}, n_items, reg_ok ? 1 : 0);
     }
     else if (L > 64 && (!use_reg || (M > 1 && k5_lab != 2)) && k5_lab != 1) {
         // up to 1024 values: 16 positions per lane; also for aligned vectors when more than one peak is wanted (the
         // register kernel's general peak pick costs more than the trip through LDS)
         int bb = (n_items + 3) / 4;
         if (bb > cu_count() * 4) bb = cu_count() * 4;
-        hipLaunchKernelGGL(find_local_max_blocked_kernel<16>, dim3(bb), block, 0, st, in, x, ov, ol, L, M, n_items, reg_ok ? 1 : 0);
+        if (d_counts) hipLaunchKernelGGL((find_local_max_blocked_kernel<16, PeakCounts>), dim3(bb), block, 0, st, in, x, ov, ol, L, pc, n_items, reg_ok ? 1 : 0);
+        else hipLaunchKernelGGL((find_local_max_blocked_kernel<16, PeakFixedM>), dim3(bb), block, 0, st, in, x, ov, ol, L, PeakFixedM{M}, n_items, reg_ok ? 1 : 0);
     }
-    else if (!use_reg)  hipLaunchKernelGGL(find_local_max_stream_kernel, grid, block, 0, st, in, x, ov, ol, L, M, n_items);
-    else if (L <= 256)  hipLaunchKernelGGL(find_local_max_kernel<1>, grid, block, 0, st, in, x, ov, ol, L, M, n_items);
-    else if (L <= 512)  hipLaunchKernelGGL(find_local_max_kernel<2>, grid, block, 0, st, in, x, ov, ol, L, M, n_items);
-    else                hipLaunchKernelGGL(find_local_max_kernel<4>, grid, block, 0, st, in, x, ov, ol, L, M, n_items);
+    else if (!use_reg) {
+        if (d_counts) hipLaunchKernelGGL(find_local_max_stream_kernel<PeakCounts>, grid, block, 0, st, in, x, ov, ol, L, pc, n_items);
+        else hipLaunchKernelGGL(find_local_max_stream_kernel<PeakFixedM>, grid, block, 0, st, in, x, ov, ol, L, PeakFixedM{M}, n_items);
+    }
+    else if (L <= 256) {
+        if (d_counts) hipLaunchKernelGGL((find_local_max_kernel<1, PeakCounts>), grid, block, 0, st, in, x, ov, ol, L, pc, n_items);
+        else hipLaunchKernelGGL((find_local_max_kernel<1, PeakFixedM>), grid, block, 0, st, in, x, ov, ol, L, PeakFixedM{M}, n_items);
+    }
+    else if (L <= 512) {
+        if (d_counts) hipLaunchKernelGGL((find_local_max_kernel<2, PeakCounts>), grid, block, 0, st, in, x, ov, ol, L, pc, n_items);
+        else hipLaunchKernelGGL((find_local_max_kernel<2, PeakFixedM>), grid, block, 0, st, in, x, ov, ol, L, PeakFixedM{M}, n_items);
+    }
+    else {
+        if (d_counts) hipLaunchKernelGGL((find_local_max_kernel<4, PeakCounts>), grid, block, 0, st, in, x, ov, ol, L, pc, n_items);
+        else hipLaunchKernelGGL((find_local_max_kernel<4, PeakFixedM>), grid, block, 0, st, in, x, ov, ol, L, PeakFixedM{M}, n_items);
+    }
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
+}
+
+int launch_find_local_max(const PeakTables &t, int n_items, const void *d_in, void *d_max, void *d_argmax,
+                          hipStream_t st)
+{
+    return launch_find_local_max_routes(t, n_items, d_in, nullptr, d_max, d_argmax, st);
+}
+
+int launch_find_local_max_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
+                                 void *d_argmax, hipStream_t st)
+{
+    if (!d_counts) { set_error("find_local_max: counts missing"); return DOA_ERR_INVALID_ARG; }
+    return launch_find_local_max_routes(t, n_items, d_in, (const int *)d_counts, d_max, d_argmax, st);
 }
 
 int launch_find_local_max_serial(const PeakTables &t, int n_items, const void *d_in, void *d_max, void *d_argmax,
@@ -251,6 +341,18 @@ int launch_find_local_max_serial(const PeakTables &t, int n_items, const void *d
     hipLaunchKernelGGL(find_local_max_serial_kernel, dim3((n_items + 63) / 64), dim3(64), 0, st, (const float *)d_in,
                        t.d_x.as<float>(), (float *)d_max, (float *)d_argmax, (signed char *)d_scratch, t.L, t.M,
                        n_items);
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+int launch_find_local_max_serial_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
+                                        void *d_argmax, void *d_scratch, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    if (!d_counts) { set_error("find_local_max: counts missing"); return DOA_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(find_local_max_serial_counts_kernel, dim3((n_items + 63) / 64), dim3(64), 0, st, (const float *)d_in,
+                       t.d_x.as<float>(), (float *)d_max, (float *)d_argmax, (signed char *)d_scratch, t.L, t.M,
+                       n_items, (const int *)d_counts);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
@@ -270,7 +372,7 @@ struct doa_find_local_max {
     doa::PeakTables tab;
     int device = 0;
     hipStream_t stream = nullptr;
-    doa::DevBuf d_in, d_out0, d_out1, d_scratch;
+    doa::DevBuf d_in, d_out0, d_out1, d_scratch, d_counts;
 };
 
 extern "C" {
@@ -306,7 +408,7 @@ void doa_find_local_max_destroy(doa_find_local_max_t *h)
 {
     if (!h) return;
     h->tab.release();
-    h->d_in.release(); h->d_out0.release(); h->d_out1.release(); h->d_scratch.release();
+    h->d_in.release(); h->d_out0.release(); h->d_out1.release(); h->d_scratch.release(); h->d_counts.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -352,6 +454,58 @@ int doa_find_local_max_work(doa_find_local_max_t *h, int noutput_items, const vo
     if (rc != DOA_OK) return rc;
     DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
     rc = doa_find_local_max_work_dev(h, noutput_items, h->d_in.p, h->d_out0.p, h->d_out1.p, h->stream);
+    if (rc < 0) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out0.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipMemcpyAsync(output_items1, h->d_out1.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    return noutput_items;
+}
+
+int doa_find_local_max_work_dev_counts(doa_find_local_max_t *h, int noutput_items, const void *d_input_items0,
+                                       const void *d_counts, void *d_output_items0, void *d_output_items1, void *hip_stream)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 ||
+        (noutput_items > 0 && (!d_input_items0 || !d_counts || !d_output_items0 || !d_output_items1))) {
+        doa::set_error("find_local_max_work_dev_counts: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    int rc;
+    if (doa::find_local_max_fast_ok(h->tab.L, d_input_items0)) {
+        rc = doa::launch_find_local_max_counts(h->tab, noutput_items, d_input_items0, d_counts, d_output_items0, d_output_items1, st);
+    } else {
+        rc = h->d_scratch.reserve((size_t)noutput_items * h->tab.L);
+        if (rc == DOA_OK)
+            rc = doa::launch_find_local_max_serial_counts(h->tab, noutput_items, d_input_items0, d_counts, d_output_items0,
+                                                          d_output_items1, h->d_scratch.p, st);
+    }
+    return rc == DOA_OK ? noutput_items : rc;
+}
+
+int doa_find_local_max_work_counts(doa_find_local_max_t *h, int noutput_items, const void *input_items0, const void *counts,
+                                   void *output_items0, void *output_items1)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 || (noutput_items > 0 && (!input_items0 || !counts || !output_items0 || !output_items1))) {
+        doa::set_error("find_local_max_work_counts: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const size_t in_bytes = (size_t)noutput_items * h->tab.L * sizeof(float);
+    const size_t out_bytes = (size_t)noutput_items * h->tab.M * sizeof(float);
+    const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
+    int rc = h->d_in.reserve(in_bytes);
+    if (rc == DOA_OK) rc = h->d_out0.reserve(out_bytes);
+    if (rc == DOA_OK) rc = h->d_out1.reserve(out_bytes);
+    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa_find_local_max_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out0.p, h->d_out1.p, h->stream);
     if (rc < 0) return rc;
     DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out0.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
     DOA_HIP_TRY(hipMemcpyAsync(output_items1, h->d_out1.p, out_bytes, hipMemcpyDeviceToHost, h->stream));

@@ -99,7 +99,7 @@ __device__ __forceinline__ JacobiRot<T> jacobi_rotation_classic(T app, T aqq, T 
 }
 
 // Exact power-of-two scale that brings max |entry| into [1, 2) (eigenvectors, ranks and therefore P_N do not
-// depend on the scale; eigenvalues themselves are never output).  m = max |entry| as float; 0, inf, NaN -> 1.
+// depend on the scale; the eigenvalue output of the per-item-count entries undoes it exactly).  m = max |entry| as float; 0, inf, NaN -> 1.
 // The whole normal range is covered: for the top binade (e = 254) the factor is 2^-127, subnormal in float, and the
 // products with the item's normal entries are still exact.  A subnormal m (e = 0: every entry below 2^-126) is left
 // unscaled: out of the range the kernels are held to.
@@ -108,6 +108,56 @@ template <typename T> __device__ __forceinline__ T jacobi_prescale(float m)
     const int e = (__float_as_int(m) >> 23) & 0xff;
     if (e == 0 || e == 255) return (T)1;
     return ldexp((T)1, 127 - e);                            // 2^-(e-127)
+}
+
+// ---- per-item source count (doa_source_count, launch_music_evd_counts) ----------------------------------------------
+// Cnt of the EVD bodies: EvdFixedM = the launch-uniform num_targets of every existing entry (no code added); EvdCounts = a
+// count per item, estimated from the item's eigenvalues (counts_in == nullptr: written to count_out) or supplied by the
+// caller (counts_in), plus the optional eigenvalue output.  Double only.
+struct EvdFixedM {};
+struct EvdCounts {
+    const int *counts_in;   // forced mode: M_i per item; nullptr = estimate
+    int *count_out;         // estimate mode: int32 per item
+    float *eig_out;         // optional: N floats per item, ascending, true scale
+    int K, method, kmax;    // num_snapshots, DOA_SOURCE_COUNT_MDL / _AIC, largest count considered
+};
+template <class Cnt> inline constexpr bool kPerItemCounts = false;
+template <> inline constexpr bool kPerItemCounts<EvdCounts> = true;
+
+// Wax-Kailath order estimate from the eigenvalues l[0] <= ... <= l[N-1] of one covariance item at its true scale:
+//     L_k = sum_{i<m} log l_i - m log((sum_{i<m} l_i) / m),  m = N - k  (the m smallest, summed in ascending index order),
+//     MDL_k = -K L_k + 0.5 k (2N - k) log K,      AIC_k = -2K L_k + 2 k (2N - k),      k = 0 .. kmax,
+// after the floor l_i <- max(l_i, l_{N-1} 2^-40) (rank-deficient items: rounding-level, possibly negative, noise
+// eigenvalues).  Returns the smallest k that attains the minimum, or -1 when l_{N-1} is not a positive finite number (a NaN
+// anywhere in the item reaches every l_i through the callers' poison term).  One pass over i = m - 1 ascending, i.e. k
+// descending: `<=` keeps the smallest k among ties.  MAXN: the compile-time size of l (loops unroll, l stays in registers).
+template <int MAXN>
+__device__ __forceinline__ int source_count_from_eigenvalues(const double (&l)[MAXN], int N, int K, int method, int kmax)
+{
+    double top = l[0];
+#pragma unroll
+    for (int i = 1; i < MAXN; i++) top = (i == N - 1) ? l[i] : top;
+    if (!(top > 0.0) || !(top < INFINITY)) return -1;
+    const double floor_l = top * 0x1p-40;
+    const double dK = (double)K, logK = log(dK);
+    double slog = 0.0, ssum = 0.0, best = 0.0;
+    int best_k = -1;
+#pragma unroll
+    for (int i = 0; i < MAXN; i++) {
+        if (i < N) {
+            const double li = fmax(l[i], floor_l);
+            slog += log(li);
+            ssum += li;
+            const int m = i + 1, k = N - m;
+            if (k <= kmax) {
+                const double Lk = slog - (double)m * log(ssum / (double)m);
+                const double pen = (double)(k * (2 * N - k));
+                const double crit = (method == DOA_SOURCE_COUNT_AIC) ? (-2.0 * dK * Lk + 2.0 * pen) : (-dK * Lk + 0.5 * pen * logK);
+                if (best_k < 0 || crit <= best) { best = crit; best_k = k; }
+            }
+        }
+    }
+    return best_k;
 }
 
 // Cyclic complex Jacobi on a Hermitian matrix kept as its real diagonal dg[] and strict upper
@@ -187,9 +237,13 @@ __device__ __forceinline__ void herm_jacobi(T (&dg)[N], T (&ur)[N][N], T (&ui)[N
 // ascending ranks (the eig_sym contract; ties -> lower index) -> P_N = sum over the N-M smallest of v v^H
 // -> u_l = sum_r P_N[r+l][r].  u[0] = u_0, u[2l-1] + j u[2l] = u_l, u[2N-1] = 0.  pn_out (optional):
 // column-major P_N as float2.
-template <int N, typename T>
+// Cnt = EvdCounts (double): M is this item's own count -- estimated from the eigenvalues or read from cnt.counts_in[item];
+// a count of 0 gives the record of P_N = I exactly (u_0 = N, u_l = 0), a count outside 0..N-1 (the -1 status included) a NaN
+// record; want_record = false stops after the count and the eigenvalue output.
+template <int N, typename T, class Cnt = EvdFixedM>
 __device__ __forceinline__ void evd_item_coefficients(const float2 *__restrict__ Ri, int M, T (&u)[2 * N],
-                                                      float2 *__restrict__ pn_out = nullptr)
+                                                      float2 *__restrict__ pn_out = nullptr, const Cnt &cnt = Cnt{},
+                                                      int item = 0, bool want_record = true)
 {
     constexpr bool UNROLL = (N <= 4);
     constexpr int U = UNROLL ? N : 1;
@@ -241,6 +295,36 @@ __device__ __forceinline__ void evd_item_coefficients(const float2 *__restrict__
 
     herm_jacobi<N, T, UNROLL, true>(dg, ar, ai, vr, vi);
 
+    bool count_bad = false;                              // (EvdCounts only)
+    if constexpr (kPerItemCounts<Cnt>) {
+        static_assert(sizeof(T) == 8, "per-item counts are double only");
+        // eigenvalues by ascending rank (the tie rule of the noise set below); double items are not pre-scaled: true scale
+        double l[N];
+#pragma unroll
+        for (int k = 0; k < N; k++) l[k] = 0.0;
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            int rank = 0;
+#pragma unroll
+            for (int j = 0; j < N; j++) rank += ((dg[j] < dg[i]) || (dg[j] == dg[i] && j < i)) ? 1 : 0;
+#pragma unroll
+            for (int k = 0; k < N; k++) l[k] = (rank == k) ? (double)dg[i] : l[k];
+        }
+#pragma unroll
+        for (int k = 0; k < N; k++) l[k] += (double)poison;
+        if (cnt.eig_out) {
+#pragma unroll
+            for (int k = 0; k < N; k++) cnt.eig_out[(size_t)item * N + k] = (float)l[k];
+        }
+        if (cnt.counts_in) M = cnt.counts_in[item];
+        else {
+            M = source_count_from_eigenvalues<N>(l, N, cnt.K, cnt.method, cnt.kmax);
+            cnt.count_out[item] = M;
+        }
+        if (!want_record) return;
+        count_bad = (M < 0 || M >= N);
+        if (count_bad) M = 0;                            // (any int may come in: keep N - M in range; the record is NaN below)
+    }
     // ascending rank of each eigenvalue (eig_sym contract); noise set = ranks < N-M
     T sel[N];
 #pragma unroll U
@@ -311,6 +395,16 @@ __device__ __forceinline__ void evd_item_coefficients(const float2 *__restrict__
         else { u[2 * l - 1] = ur_; u[2 * l] = ui_; }
     }
     u[2 * N - 1] = 0;
+    if constexpr (kPerItemCounts<Cnt>) {
+        if (count_bad) {
+#pragma unroll
+            for (int k = 0; k < 2 * N; k++) u[k] = (T)NAN;
+        } else if (M == 0) {
+            u[0] = (T)N + poison;
+#pragma unroll
+            for (int k = 1; k < 2 * N; k++) u[k] = poison;
+        }
+    }
 }
 
 }  // namespace doa

@@ -79,6 +79,17 @@ inline int coef_stride(int N) { return 2 * N; }
 // ChebQ) -- the change of basis is per item, so it belongs to the kernel that runs once per item.
 int launch_music_evd(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,
                      int evd_bits, hipStream_t st, void *d_cheb = nullptr);
+// The same stage with a count PER ITEM (double, always the Jacobi forms: one lane per item for N <= 4, 8 lanes for N <= 8,
+// one wave for N <= 16).  Estimate mode (d_counts_in == NULL): the count comes from the item's eigenvalues (jacobi.hpp:
+// source_count_from_eigenvalues; K snapshots, method DOA_SOURCE_COUNT_*, counts 0..kmax) and is written to d_count_out
+// (int32).  Forced mode: the count is read from d_counts_in (int32).  d_eig_out (optional): N floats per item, ascending, at
+// the item's scale.  d_coef_d (double records) and d_cheb (N <= 4) may be NULL (count / eigenvalues only).  Count 0: the
+// record of P_N = I; a count outside 0..N-1: a NaN record.
+int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_counts_in, void *d_count_out, void *d_eig_out,
+                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st);
+// after the scan of a per-item-count call: rows (P floats) of items whose count is outside 0..N-1 become NaN (the scan kernels
+// themselves write 0.0 dB for a NaN record)
+int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, void *d_spec, hipStream_t st);
 inline bool music_uses_cheb(int N, int bits) { return N <= 4 && bits == 64; }
 constexpr int kChebRecord = 8;      // doubles per item
 // diagnostics: items that left the signal-subspace fast path of K2+K3 for the Jacobi fall-back since the last reset
@@ -113,6 +124,13 @@ struct PeakTables {
 };
 int launch_find_local_max(const PeakTables &t, int n_items, const void *d_in, void *d_max, void *d_argmax,
                           hipStream_t st);
+// with a count per item (d_counts: int32 m_i): the first m_i slots as find_local_max(m_i, ...) writes them, items stay t.M
+// floats wide, the other slots NaN; m_i outside 0..t.M: all NaN.  Every route of launch_find_local_max; L > 4096: the
+// serial kernel (d_scratch: L bytes per item).
+int launch_find_local_max_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
+                                 void *d_argmax, hipStream_t st);
+int launch_find_local_max_serial_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
+                                        void *d_argmax, void *d_scratch, hipStream_t st);
 
 // K6 (root_music.hip): polynomial roots from the DOUBLE coefficient records -> angles.
 // d_roots (optional, diagnostics): the 2N-2 roots found per item as double2, in the kernel's lane order.

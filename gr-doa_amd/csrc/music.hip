@@ -113,6 +113,30 @@ int launch_music_scan_group(const MusicTables &t, const PeakTables &peaks, const
     return DOA_OK;
 }
 
+// Per-item counts: the scan kernels write 0.0 dB everywhere for an all-NaN null spectrum (their maximum search drops NaNs),
+// so the rows of items whose count is outside 0..N-1 -- a NaN coefficient record -- are set to NaN here.  One wave per item; a
+// wave with a valid count returns after one load.
+__global__ __launch_bounds__(256) void music_invalid_rows_kernel(const int *__restrict__ counts, int N, float *__restrict__ spec,
+                                                                 int P, int n_items)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    if (item >= n_items) return;
+    const int m = counts[item];
+    if (m >= 0 && m < N) return;
+    float *row = spec + (size_t)item * P;
+    for (int p = lane; p < P; p += kWave) row[p] = NAN;
+}
+
+int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, void *d_spec, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    hipLaunchKernelGGL(music_invalid_rows_kernel, dim3((n_items + 3) / 4), dim3(256), 0, st, (const int *)d_counts, N,
+                       (float *)d_spec, P, n_items);
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
 }  // namespace doa
 
 // ---------------------------------------------------------------------------------------------
@@ -124,7 +148,7 @@ struct doa_MUSIC_lin_array {
     int device = 0;
     long long items_total = 0;
     hipStream_t stream = nullptr;
-    doa::DevBuf d_in, d_out, d_coef, d_pn, d_q, d_cheb;
+    doa::DevBuf d_in, d_out, d_coef, d_pn, d_q, d_cheb, d_counts;
 };
 
 static int music_validate(const char *who, float norm_spacing, int num_targets, int num_ant_ele)
@@ -176,7 +200,7 @@ void doa_MUSIC_lin_array_destroy(doa_MUSIC_lin_array_t *h)
 {
     if (!h) return;
     h->tab.release();
-    h->d_in.release(); h->d_out.release(); h->d_coef.release(); h->d_pn.release(); h->d_q.release(); h->d_cheb.release();
+    h->d_in.release(); h->d_out.release(); h->d_coef.release(); h->d_pn.release(); h->d_q.release(); h->d_cheb.release(); h->d_counts.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -230,6 +254,68 @@ int doa_MUSIC_lin_array_work(doa_MUSIC_lin_array_t *h, int noutput_items, const 
     rc = doa_MUSIC_lin_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
     if (rc < 0) return rc;
     DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    return noutput_items;
+}
+
+int doa_MUSIC_lin_array_work_dev_counts(doa_MUSIC_lin_array_t *h, int noutput_items, const void *d_cov_items,
+                                        const void *d_counts, void *d_spectrum_out, void *hip_stream)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_cov_items || !d_counts || !d_spectrum_out))) {
+        doa::set_error("MUSIC_lin_array_work_dev_counts: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("MUSIC_lin_array_work_dev_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int N = h->tab.N;
+    int rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(N) * sizeof(double));
+    const bool cheb = doa::music_uses_cheb(N, 64);
+    if (rc == DOA_OK && cheb) rc = h->d_cheb.reserve((size_t)noutput_items * doa::kChebRecord * sizeof(double));
+    if (rc != DOA_OK) return rc;
+    rc = doa::launch_music_evd_counts(N, noutput_items, d_cov_items, d_counts, nullptr, nullptr, 0, 0, 0, h->d_coef.p,
+                                      cheb ? h->d_cheb.p : nullptr, st);
+    if (rc != DOA_OK) return rc;
+    rc = doa::launch_music_scan(h->tab, 64, noutput_items, h->d_coef.p, d_spectrum_out, nullptr, st, nullptr, nullptr, nullptr,
+                                nullptr, true, cheb ? h->d_cheb.p : nullptr);
+    if (rc == DOA_OK) rc = doa::launch_music_invalid_rows(N, h->tab.P, noutput_items, d_counts, d_spectrum_out, st);
+    if (rc != DOA_OK) return rc;
+    h->items_total += noutput_items;
+    return noutput_items;
+}
+
+int doa_MUSIC_lin_array_work_counts(doa_MUSIC_lin_array_t *h, int noutput_items, const void *cov_items, const void *counts,
+                                    void *spectrum_out)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 || (noutput_items > 0 && (!cov_items || !counts || !spectrum_out))) {
+        doa::set_error("MUSIC_lin_array_work_counts: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("MUSIC_lin_array_work_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const int N = h->tab.N, P = h->tab.P;
+    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
+    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
+    const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
+    int rc = h->d_in.reserve(in_bytes);
+    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
+    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa_MUSIC_lin_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, h->stream);
+    if (rc < 0) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(spectrum_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
     DOA_HIP_TRY(hipStreamSynchronize(h->stream));
     return noutput_items;
 }

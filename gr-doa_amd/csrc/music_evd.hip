@@ -37,10 +37,12 @@ __device__ __forceinline__ void write_cheb_record(double *__restrict__ o, const 
 // batch's pointer is picked per lane: a chain of selects over the table's entries (compile-time indices -- a per-lane
 // index into the kernel arguments would put the table into scratch memory).
 struct EvdOne {
+    static constexpr bool kCounts = false;
     const float2 *R;
     template <int N> __device__ __forceinline__ const float2 *item(int g) const { return R + (size_t)g * (N * N); }
 };
 struct EvdGroup {
+    static constexpr bool kCounts = false;
     const float2 *cov[kMaxGroup];
     GroupSplit split;
     template <int N> __device__ __forceinline__ const float2 *item(int g) const
@@ -52,6 +54,14 @@ struct EvdGroup {
         for (int b = 1; b < kMaxGroup; b++) R = (batch == (unsigned)b) ? cov[b] : R;
         return R + (size_t)local * (N * N);
     }
+};
+
+// one array, and a count per item (launch_music_evd_counts): the one-lane kernel then runs the Jacobi only
+struct EvdOneCounts {
+    static constexpr bool kCounts = true;
+    const float2 *R;
+    EvdCounts cnt;
+    template <int N> __device__ __forceinline__ const float2 *item(int g) const { return R + (size_t)g * (N * N); }
 };
 
 template <int N, typename T, class Src = EvdOne>
@@ -71,6 +81,9 @@ __global__ __launch_bounds__(64) void music_evd_kernel(Src src, float *__restric
     // the spread of step counts over 64 items (median 4-6, some 11-15, a few fall-backs) costs more than it saves: measured
     // 11.9 against 10.8 us per 4096 items at M = 2 (configs[2]) and 30 against 10.4 us on the simulation flowgraph's shape
     bool done = false;
+    if constexpr (Src::kCounts) {
+        evd_item_coefficients<N, T, EvdCounts>(Ri, M, u, nullptr, src.cnt, item, coef_d || cheb_d);
+    } else {
     if constexpr (sizeof(T) == 8) {
         if (M == 1) {
             done = evd_small_subspace<N, 1>(Ri, u, pn_i);
@@ -78,6 +91,7 @@ __global__ __launch_bounds__(64) void music_evd_kernel(Src src, float *__restric
         }
     }
     if (!done) evd_item_coefficients<N, T>(Ri, M, u, pn_i);
+    }
     // float record for the float scan; double record for the root finder (Root-MUSIC's near-double roots amplify
     // a float rounding of u_l by ~1e3-1e4) and for the double scan
     if (coef) {
@@ -226,12 +240,16 @@ template <int G, typename T, int ROUND> struct RoundLoop {
 // the N x N problem (not padding).  Ranks the eigenvalues ascending (the eig_sym contract), takes the
 // N-M smallest as the noise set and emits the diagonal sums u_l of P_N (or, in calibrate mode, the
 // de-rotated top eigenvector).
-template <int G, typename T>
+// Cnt = EvdCounts: the group's own count M (jacobi.hpp) -- every lane gathers the eigenvalues by rank, brings them back to
+// the item's scale (inv_sc = 1 / prescale, a power of two) and evaluates the criterion redundantly; poison = 0, or NaN for a
+// non-finite item.
+template <int G, typename T, class Cnt = EvdFixedM>
 __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam, bool real_col, int r, int base, int lane,
                                                    int item, bool real_item, int N, int M, float *__restrict__ coef,
                                                    double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                    const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                                   double *__restrict__ cheb_d = nullptr)
+                                                   double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{},
+                                                   T inv_sc = (T)1, T poison = (T)0)
 {
     // eigenvalue of lane r = A[r][r]; ascending rank inside the group; noise set = ranks < N-M
     int rank = 0;
@@ -266,6 +284,35 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
         }
         if (real_item && r < N) cal_out[(size_t)item * N + r] = make_float2((float)wr, (float)((r == 0) ? (T)0 : wi));
         return;
+    }
+    bool count_bad = false, count_zero = false;          // (EvdCounts only)
+    if constexpr (kPerItemCounts<Cnt>) {
+        double l[G];
+#pragma unroll
+        for (int k = 0; k < G; k++) l[k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < G; j++) {
+            const double lj = (double)lane_fetch<T>(lam, base + j);
+            const int rj = __shfl(rank, base + j, kWave);
+#pragma unroll
+            for (int k = 0; k < G; k++) l[k] = (rj == k) ? lj : l[k];
+        }
+        double mine = 0.0;
+#pragma unroll
+        for (int k = 0; k < G; k++) {
+            l[k] = fma(l[k], (double)inv_sc, (double)poison);
+            mine = (k == r) ? l[k] : mine;
+        }
+        if (cnt.eig_out && real_item && r < N) cnt.eig_out[(size_t)item * N + r] = (float)mine;
+        if (cnt.counts_in) M = cnt.counts_in[item];
+        else {
+            M = source_count_from_eigenvalues<G>(l, N, cnt.K, cnt.method, cnt.kmax);
+            if (real_item && r == 0) cnt.count_out[item] = M;
+        }
+        if (!coef && !coef_d) return;
+        count_bad = (M < 0 || M >= N);
+        count_zero = (M == 0);
+        if (count_bad) M = 0;                            // (any int may come in: keep N - M in range; the record is NaN below)
     }
     const bool is_noise = real_col && (rank < N - M);
     const unsigned long long noise_mask = __ballot(is_noise);
@@ -306,6 +353,11 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
         if (!(r + l < N)) { tr = 0; ti = 0; }
         tr = group_sum<G, T>(tr, lane);
         ti = group_sum<G, T>(ti, lane);
+        if constexpr (kPerItemCounts<Cnt>) {
+            // count 0: P_N = I exactly; a count outside 0..N-1: a NaN record
+            if (count_zero) { tr = ((l == 0) ? (T)N : (T)0) + poison; ti = poison; }
+            if (count_bad) { tr = (T)NAN; ti = (T)NAN; }
+        }
         if (r == 0) {
             if (l == 0) {
                 if (co) co[0] = (float)tr;
@@ -341,11 +393,11 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
 }
 
 // the whole group Jacobi of one wave: G lanes per item, `real_item` = this lane's group stores its results
-template <int G, typename T>
+template <int G, typename T, class Cnt = EvdFixedM>
 __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, int item, bool real_item, int N, int M,
                                                float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                               double *__restrict__ cheb_d = nullptr);
+                                               double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{});
 
 template <int G, typename T>
 __global__ __launch_bounds__(64) void music_evd_group_kernel(const float2 *__restrict__ R, float *__restrict__ coef,
@@ -361,11 +413,11 @@ __global__ __launch_bounds__(64) void music_evd_group_kernel(const float2 *__res
     evd_group_wave<G, T>(R + (size_t)item * (N * N), item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out);
 }
 
-template <int G, typename T>
+template <int G, typename T, class Cnt>
 __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, int item, bool real_item, int N, int M,
                                                float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                               double *__restrict__ cheb_d)
+                                               double *__restrict__ cheb_d, const Cnt &cnt)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int r = lane % G, base = lane - r;
@@ -386,6 +438,7 @@ __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, in
         vr[c] = (r == c) ? (T)1 : (T)0; vi[c] = 0;
     }
     T poison = 0;            // 0, or NaN when the item holds a non-finite entry
+    T sc;                    // the item's prescale (a power of two)
     {
         float m = 0.f;
 #pragma unroll
@@ -397,7 +450,7 @@ __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, in
         poison = group_sum<G, T>(poison, lane);
 #pragma unroll
         for (int k = 1; k < G; k <<= 1) m = fmaxf(m, __shfl(m, lane ^ k, kWave));
-        const T sc = jacobi_prescale<T>(m);
+        sc = jacobi_prescale<T>(m);
 #pragma unroll
         for (int c = 0; c < G; c++)
             if (r < N && c < N) { ar[c] *= sc; ai[c] *= sc; }
@@ -425,7 +478,25 @@ __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, in
     // plausible-looking record built from an identity V
 #pragma unroll
     for (int k = 0; k < G; k++) vr[k] += poison;
+    if constexpr (kPerItemCounts<Cnt>)
+        evd_group_epilogue<G, T, Cnt>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out,
+                                      cheb_d, cnt, (T)1 / sc, poison);
+    else
     evd_group_epilogue<G, T>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out, cheb_d);
+}
+
+// the group Jacobi with a count per item (launch_music_evd_counts; double)
+template <int G>
+__global__ __launch_bounds__(64) void music_evd_group_counts_kernel(const float2 *__restrict__ R, double *__restrict__ coef_d,
+                                                                    int n_items, int N, EvdCounts cnt)
+{
+    constexpr int IPW = kWave / G;
+    const int lane = threadIdx.x & (kWave - 1);
+    int item = blockIdx.x * IPW + lane / G;
+    const bool real_item = item < n_items;
+    if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
+    evd_group_wave<G, double, EvdCounts>(R + (size_t)item * (N * N), item, real_item, N, 0, nullptr, coef_d, nullptr, nullptr,
+                                         nullptr, nullptr, cnt);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -811,11 +882,14 @@ __device__ __forceinline__ unsigned caterpillar_mask(unsigned m)
 // calibrate mode through the shared row-per-lane epilogue.
 // One item on one wave (the body of music_evd_block16_kernel; also the fall-back of the subspace-iteration kernel below).
 // sVr / sVi / sLam: 16 x 16 + 16 values of LDS owned by this wave.
-template <typename T, bool LEAN>
+// Cnt = EvdCounts (LEAN only): the item's own count, every lane evaluating the criterion on the eigenvalues the ranking lanes
+// leave sorted in sLam.
+template <typename T, bool LEAN, class Cnt = EvdFixedM>
 __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, int item, float *__restrict__ coef,
                                                  double *__restrict__ coef_d, float2 *__restrict__ pn_out, int N, int M,
                                                  const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                                 T *__restrict__ sVr, T *__restrict__ sVi, T *__restrict__ sLam)
+                                                 T *__restrict__ sVr, T *__restrict__ sVi, T *__restrict__ sLam,
+                                                 const Cnt &cnt = Cnt{})
 {
     constexpr int G = 16;
     const int lane = threadIdx.x & (kWave - 1);
@@ -839,13 +913,14 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
             vr[i][j] = (row == col) ? (T)1 : (T)0; vi[i][j] = 0;
         }
     T poison = 0;            // 0, or NaN when the item holds a non-finite entry
+    T sc;                    // the item's prescale (a power of two)
     {
         float m = 0.f;
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
             for (int j = 0; j < 2; j++) m = fmaxf(m, fmaxf(fabsf((float)xr[i][j]), fabsf((float)xi[i][j])));
-        const T sc = jacobi_prescale<T>(wave_allreduce_max(m));
+        sc = jacobi_prescale<T>(wave_allreduce_max(m));
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -954,16 +1029,38 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
     if constexpr (LEAN) {
         // ranks (ascending, ties -> lower slot) on lanes 0..15; noise set = the N-M smallest real slots
         bool is_noise = false;
+        int rank = 0;
+        T lam = 0;
         if (lane < G) {
-            const T lam = sLam[lane];
-            int rank = 0;
+            lam = sLam[lane];
 #pragma unroll
             for (int j = 0; j < G; j++) {
                 const T lj = sLam[j];
                 rank += ((lj < lam) || (lj == lam && j < lane)) ? 1 : 0;
             }
-            is_noise = !((pad >> lane) & 1u) && (rank < N - M);
         }
+        bool count_bad = false, count_zero = false;          // (EvdCounts only)
+        if constexpr (kPerItemCounts<Cnt>) {
+            // sLam <- the eigenvalues by rank (padding slots rank last), at the item's scale
+            __syncthreads();
+            if (lane < G) sLam[rank] = lam;
+            __syncthreads();
+            const T inv_sc = (T)1 / sc;
+            double l[G];
+#pragma unroll
+            for (int k = 0; k < G; k++) l[k] = fma((double)sLam[k], (double)inv_sc, (double)poison);
+            if (cnt.eig_out && lane < N) cnt.eig_out[(size_t)item * N + lane] = (float)fma((double)sLam[lane], (double)inv_sc, (double)poison);
+            if (cnt.counts_in) M = cnt.counts_in[item];
+            else {
+                M = source_count_from_eigenvalues<G>(l, N, cnt.K, cnt.method, cnt.kmax);
+                if (lane == 0) cnt.count_out[item] = M;
+            }
+            if (!coef && !coef_d) return;
+            count_bad = (M < 0 || M >= N);
+            count_zero = (M == 0);
+            if (count_bad) M = 0;                        // (any int may come in: keep N - M in range; the record is NaN below)
+        }
+        if (lane < G) is_noise = !((pad >> lane) & 1u) && (rank < N - M);
         const unsigned sel = (unsigned)(__ballot(is_noise) & 0xFFFFull);
         // u_l = sum_r sum_{i in noise} V[r+l][i] conj(V[r][i]):  lane = 4 l + c takes the rows r = c (mod 4)
         const int l = lane >> 2, c4 = lane & 3;
@@ -981,6 +1078,11 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
         }
         tr += lane_fetch<T>(tr, lane ^ 1); ti += lane_fetch<T>(ti, lane ^ 1);
         tr += lane_fetch<T>(tr, lane ^ 2); ti += lane_fetch<T>(ti, lane ^ 2);
+        if constexpr (kPerItemCounts<Cnt>) {
+            // count 0: P_N = I exactly; a count outside 0..N-1: a NaN record
+            if (count_zero) { tr = ((l == 0) ? (T)N : (T)0) + poison; ti = poison; }
+            if (count_bad) { tr = (T)NAN; ti = (T)NAN; }
+        }
         if (c4 == 0 && l < N) {
             float *co = coef ? coef + (size_t)item * (2 * N) : nullptr;
             double *cd = coef_d ? coef_d + (size_t)item * (2 * N) : nullptr;
@@ -1010,6 +1112,16 @@ __global__ __launch_bounds__(64) void music_evd_block16_kernel(const float2 *__r
     __shared__ T sVr[16 * 16], sVi[16 * 16], sLam[16];
     const int item = blockIdx.x;                         // grid = n_items
     evd_block16_item<T, LEAN>(R + (size_t)item * (N * N), item, coef, coef_d, pn_out, N, M, pilot, cal_out, sVr, sVi, sLam);
+}
+
+// the block Jacobi with a count per item (launch_music_evd_counts; double)
+__global__ __launch_bounds__(64) void music_evd_block16_counts_kernel(const float2 *__restrict__ R, double *__restrict__ coef_d,
+                                                                      int n_items, int N, EvdCounts cnt)
+{
+    __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
+    const int item = blockIdx.x;                         // grid = n_items
+    evd_block16_item<double, true, EvdCounts>(R + (size_t)item * (N * N), item, nullptr, coef_d, nullptr, N, 0, nullptr, nullptr,
+                                              sVr, sVi, sLam, cnt);
 }
 
 // One wave per item: the signal-subspace iteration (evd_subspace.hpp) first; whatever it does not certify takes the
@@ -1196,6 +1308,47 @@ int launch_music_evd_group(int N, int M, const BatchGroup &grp, void *d_coef_d, 
     case 2: launch_evd_group_n<2>(M, n_items, src, d_coef_d, d_cheb, st); break;
     case 3: launch_evd_group_n<3>(M, n_items, src, d_coef_d, d_cheb, st); break;
     default: launch_evd_group_n<4>(M, n_items, src, d_coef_d, d_cheb, st); break;
+    }
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+template <int N> static void launch_evd_counts_n(int n_items, const void *d_R, const EvdCounts &cnt, void *d_coef_d, void *d_cheb,
+                                                 hipStream_t st)
+{
+    dim3 block(64), grid((n_items + 63) / 64);
+    hipLaunchKernelGGL((music_evd_kernel<N, double, EvdOneCounts>), grid, block, 0, st, EvdOneCounts{(const float2 *)d_R, cnt},
+                       (float *)nullptr, (double *)d_coef_d, (float2 *)nullptr, n_items, 0, (double *)d_cheb,
+                       (unsigned long long *)nullptr);
+}
+
+int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_counts_in, void *d_count_out, void *d_eig_out,
+                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    if (N < 2 || N > DOA_MAX_ANT_ELE) {
+        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (!d_counts_in && (!d_count_out || K < 2 || kmax < 0 || kmax > N - 1 ||
+                         (method != DOA_SOURCE_COUNT_MDL && method != DOA_SOURCE_COUNT_AIC))) {
+        set_error("source count: bad arguments (K=%d, method=%d, kmax=%d, N=%d)", K, method, kmax, N);
+        return DOA_ERR_INVALID_ARG;
+    }
+    const EvdCounts cnt{(const int *)d_counts_in, (int *)d_count_out, (float *)d_eig_out, K, method, kmax};
+    // always the Jacobi forms (the subspace iterations never form the noise eigenvalues)
+    if (N > 8) {
+        hipLaunchKernelGGL(music_evd_block16_counts_kernel, dim3(n_items), dim3(64), 0, st, (const float2 *)d_R, (double *)d_coef_d,
+                           n_items, N, cnt);
+    } else if (N > 4) {
+        hipLaunchKernelGGL((music_evd_group_counts_kernel<8>), dim3((n_items + 7) / 8), dim3(64), 0, st, (const float2 *)d_R,
+                           (double *)d_coef_d, n_items, N, cnt);
+    } else {
+        switch (N) {
+        case 2: launch_evd_counts_n<2>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
+        case 3: launch_evd_counts_n<3>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
+        default: launch_evd_counts_n<4>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
+        }
     }
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;

@@ -225,6 +225,64 @@ int doa_music_pipeline_work_dev(doa_music_pipeline_t *h, int noutput_items, cons
                    static_cast<hipStream_t>(hip_stream));
 }
 
+// K1 as work_dev runs it, ONE eigen launch that estimates each item's count and forms its noise set from it, the scan (no
+// fused peak pick: its M is launch-uniform), the counted peak pick: four launches, and one more when the caller wants the
+// spectrum (launch_music_invalid_rows)
+int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items, const void *const *d_input_items, int method,
+                                     void *d_cov_out, void *d_spectrum_out, void *d_max_out, void *d_argmax_out,
+                                     void *d_count_out, void *d_eig_out, void *hip_stream)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 || !d_input_items || (method != DOA_SOURCE_COUNT_MDL && method != DOA_SOURCE_COUNT_AIC) ||
+        (noutput_items > 0 && (!d_max_out || !d_argmax_out || !d_count_out))) {
+        doa::set_error("music_pipeline_work_dev_auto: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (noutput_items > h->max_batch) {
+        doa::set_error("music_pipeline_work_dev_auto: noutput_items=%d exceeds max_batch=%d", noutput_items, h->max_batch);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("music_pipeline_work_dev_auto: per-item counts need internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (h->K < 2) {
+        doa::set_error("music_pipeline_work_dev_auto: the criterion needs snapshot_size >= 2 (handle has %d)", h->K);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int n = noutput_items;
+    const bool cheb = doa::music_uses_cheb(h->N, 64);
+    // (a handle created at precision 32 and switched to 64 afterwards has no Chebyshev records yet)
+    if (cheb && !h->d_cheb.p)
+        if (int rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double)); rc != DOA_OK) return rc;
+    void *cov = d_cov_out ? d_cov_out : h->d_cov.p;
+    void *spec = d_spectrum_out ? d_spectrum_out : h->d_spec.p;
+    PipeWs ws{};
+    ws.work = h->d_work[0].p;
+    int rc = run_k1(h, n, d_input_items, cov, ws, st);
+    if (rc == DOA_OK)
+        rc = doa::launch_music_evd_counts(h->N, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->music.M, h->d_coef.p,
+                                          cheb ? h->d_cheb.p : nullptr, st);
+    if (rc == DOA_OK)
+        rc = doa::launch_music_scan(h->music, 64, n, h->d_coef.p, spec, nullptr, st, nullptr, nullptr, nullptr, nullptr, true,
+                                    cheb ? h->d_cheb.p : nullptr);
+    // a spectrum the caller sees: the row of a count -1 item is NaN, as MUSIC_lin_array_work_dev_counts leaves it (a fifth,
+    // one-load-per-item launch; the peak pick below does not read the rows of such items)
+    if (rc == DOA_OK && d_spectrum_out) rc = doa::launch_music_invalid_rows(h->N, h->peaks.L, n, d_count_out, spec, st);
+    if (rc != DOA_OK) return rc;
+    if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
+        rc = doa::launch_find_local_max_counts(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, st);
+    } else {
+        rc = h->d_scratch.reserve((size_t)h->max_batch * h->peaks.L);
+        if (rc == DOA_OK)
+            rc = doa::launch_find_local_max_serial_counts(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, h->d_scratch.p, st);
+    }
+    return rc == DOA_OK ? n : rc;
+}
+
 int doa_music_pipeline_set_lanes(doa_music_pipeline_t *h, int n_lanes)
 {
     doa::clear_error();

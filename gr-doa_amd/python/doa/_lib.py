@@ -151,6 +151,15 @@ SIGNATURES = {
     "doa_calib_mean_complex_work_dev": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_write_phase_config": (C.c_int, [C.c_char_p, _vp, C.c_int]),
     "doa_write_antenna_calib": (C.c_int, [C.c_char_p, _vp, _vp, C.c_int]),
+    "doa_source_count_create": (_vp, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "doa_source_count_destroy": (None, [_vp]),
+    "doa_source_count_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_source_count_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_MUSIC_lin_array_work_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_MUSIC_lin_array_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_find_local_max_work_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_find_local_max_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_music_pipeline_work_dev_auto": (C.c_int, [_vp, C.c_int, _vpp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_root_pipeline_inject_failure": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_lanes_idle": (C.c_int, [_vp]),

@@ -26,6 +26,23 @@ from ._lib import lib, check, check_handle, ptr_array
 _C64 = np.complex64
 _F32 = np.float32
 _I16 = np.int16
+_I32 = np.int32
+
+# criteria of the source-count estimate (DOA_SOURCE_COUNT_MDL / DOA_SOURCE_COUNT_AIC, include/doa_hip.h)
+_COUNT_METHODS = {"mdl": 0, "aic": 1}
+
+
+def _count_method(method) -> int:
+    """ "mdl" / "aic" (any case), or the C constant itself; anything else is passed on for the library to reject."""
+    if isinstance(method, str):
+        if method.lower() not in _COUNT_METHODS:
+            raise ValueError(f"unknown source-count method {method!r} (mdl or aic)")
+        return _COUNT_METHODS[method.lower()]
+    return int(method)
+
+
+def _opt_ptr(p) -> C.c_void_p:
+    return C.c_void_p(0 if p is None else int(p))
 
 # input sample formats of the stream-input blocks (DOA_SAMPLE_FC32 / DOA_SAMPLE_SC16, include/doa_hip.h)
 SC16_DEFAULT_SCALE = 2.0 ** -15
@@ -291,6 +308,22 @@ class MUSIC_lin_array(_Block):
         return check(lib.doa_MUSIC_lin_array_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
                                                       C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
 
+    def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
+        """work with a source count PER ITEM (int32 array) in place of num_targets: count 0 gives an all-0.0 dB row, a count
+        outside 0..inputs-1 (source_count's -1 status included) a NaN row (doa_MUSIC_lin_array_work_counts)."""
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        c = np.ascontiguousarray(counts, dtype=_I32)
+        out = output_items[0]
+        assert a.size >= n * self.num_ant_ele ** 2 and c.size >= n
+        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
+        return check(lib.doa_MUSIC_lin_array_work_counts(self._h, n, _vp(a), _vp(c), _vp(out)))
+
+    def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out_ptr, stream=None) -> int:
+        return check(lib.doa_MUSIC_lin_array_work_dev_counts(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
+                                                             _opt_ptr(d_counts_ptr), C.c_void_p(int(d_out_ptr)),
+                                                             _stream_ptr(stream)))
+
     def debug(self, R_items: np.ndarray):
         """(P_N [n, N*N] complex64 column-major items, Q [n, P] float32) for parity tests."""
         a = np.ascontiguousarray(R_items, dtype=_C64).reshape(-1, self.num_ant_ele ** 2)
@@ -332,6 +365,59 @@ class find_local_max(_Block):
         return check(lib.doa_find_local_max_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
                                                      C.c_void_p(int(d_out0_ptr)), C.c_void_p(int(d_out1_ptr)),
                                                      _stream_ptr(stream)))
+
+
+    def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
+        """work with a peak count m_i PER ITEM (int32 array): the first m_i slots of both ports are find_local_max(m_i, ...)'s,
+        the rest of the num_max_vals-wide items NaN; m_i outside 0..num_max_vals: all NaN (doa_find_local_max_work_counts)."""
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_F32)
+        c = np.ascontiguousarray(counts, dtype=_I32)
+        o0, o1 = output_items
+        assert a.size >= n * self.vector_len and c.size >= n
+        for o in (o0, o1):
+            assert o.dtype == _F32 and o.flags.c_contiguous and o.size >= n * self.num_max_vals
+        return check(lib.doa_find_local_max_work_counts(self._h, n, _vp(a), _vp(c), _vp(o0), _vp(o1)))
+
+    def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out0_ptr, d_out1_ptr, stream=None) -> int:
+        return check(lib.doa_find_local_max_work_dev_counts(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
+                                                            _opt_ptr(d_counts_ptr), C.c_void_p(int(d_out0_ptr)),
+                                                            C.c_void_p(int(d_out1_ptr)), _stream_ptr(stream)))
+
+
+class source_count(_Block):
+    """doa.source_count(num_ant_ele, num_snapshots, method="mdl", max_sources=None) — the number of sources per covariance
+    item, estimated on the device from its eigenvalues (Wax-Kailath MDL, or AIC; include/doa_hip.h).  Not a block of the
+    reference, which takes num_targets as a flowgraph parameter.  Port 0: int32 count (-1: non-finite or non-positive item);
+    port 1 (optional): the num_ant_ele eigenvalues, ascending.  max_sources None = num_ant_ele - 1."""
+
+    _destroy = staticmethod(lib.doa_source_count_destroy)
+
+    def __init__(self, num_ant_ele, num_snapshots, method="mdl", max_sources=None):
+        super().__init__()
+        self.num_ant_ele, self.num_snapshots = int(num_ant_ele), int(num_snapshots)
+        self.method = _count_method(method)
+        self.max_sources = self.num_ant_ele - 1 if max_sources is None else int(max_sources)
+        self._h = check_handle(lib.doa_source_count_create(self.num_ant_ele, self.num_snapshots, self.method,
+                                                           self.max_sources), "source_count")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_I32, 1), (_F32, self.num_ant_ele)]
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        """output_items = [counts int32 [n]] or [counts, eigenvalues float32 [n, num_ant_ele]]."""
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        cnt = output_items[0]
+        eig = output_items[1] if len(output_items) > 1 else None
+        assert a.size >= n * self.num_ant_ele ** 2
+        assert cnt.dtype == _I32 and cnt.flags.c_contiguous and cnt.size >= n
+        if eig is not None:
+            assert eig.dtype == _F32 and eig.flags.c_contiguous and eig.size >= n * self.num_ant_ele
+        return check(lib.doa_source_count_work(self._h, n, _vp(a), _vp(cnt), _vp(eig) if eig is not None else C.c_void_p(0)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_count_ptr, d_eig_ptr=None, stream=None) -> int:
+        return check(lib.doa_source_count_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
+                                                   _opt_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _stream_ptr(stream)))
 
 
 class rootMUSIC_linear_array(_Block):
@@ -473,6 +559,15 @@ class music_pipeline(_StreamInput, _Block):
             self._h, int(noutput_items), ptr_array(d_input_ptrs), C.c_void_p(int(d_cov_ptr or 0)),
             C.c_void_p(int(d_spec_ptr or 0)), C.c_void_p(int(d_max_ptr)), C.c_void_p(int(d_argmax_ptr)),
             _stream_ptr(stream)))
+
+    def work_dev_auto(self, noutput_items, d_input_ptrs, d_max_ptr, d_argmax_ptr, d_count_ptr, method="mdl", d_cov_ptr=None,
+                      d_spec_ptr=None, d_eig_ptr=None, stream=None) -> int:
+        """work_dev with the source count estimated per snapshot (K = snapshot_size, at most num_targets sources): max / arg-max
+        stay num_targets wide, the first count slots filled and the rest NaN; counts (int32, required) and the eigenvalues
+        (optional) come out of the same eigen launch (doa_music_pipeline_work_dev_auto)."""
+        return check(lib.doa_music_pipeline_work_dev_auto(
+            self._h, int(noutput_items), ptr_array(d_input_ptrs), _count_method(method), _opt_ptr(d_cov_ptr), _opt_ptr(d_spec_ptr),
+            _opt_ptr(d_max_ptr), _opt_ptr(d_argmax_ptr), _opt_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _stream_ptr(stream)))
 
     def set_lanes(self, n_lanes: int) -> None:
         check(lib.doa_music_pipeline_set_lanes(self._h, int(n_lanes)))

@@ -368,6 +368,70 @@ DOA_HIP_API int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_ite
                                         void *spectrum_out, void *max_out, void *argmax_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * source_count — the number of sources per covariance item, estimated on the device from the item's eigenvalues
+ *   (Wax-Kailath MDL, or AIC), and the entries that take a count PER ITEM instead of the num_targets fixed at create.
+ *   Not a block of the reference: gr-doa takes num_targets as a flowgraph parameter; MUSIC is only right when that number
+ *   is (too small: a source's eigenvector lands in the noise subspace; too large: spurious peaks), and a receiver in the
+ *   field does not know it.
+ * The criterion, one definition for every entry: for one item (column-major num_ant_ele^2 gr_complex, upper triangle only,
+ *   as MUSIC_lin_array) let l_0 <= ... <= l_{N-1} be its eigenvalues in double at the item's true scale.
+ *     status : a non-finite entry, or l_{N-1} <= 0  ->  count -1 (a non-finite item's eigenvalue outputs are NaN)
+ *     floor  : l_i <- max(l_i, l_{N-1} * 2^-40)
+ *     L_k    = sum log l_i - m log((sum l_i) / m) over the m = N - k smallest, summed in ascending index order
+ *     MDL_k  = -K L_k + 0.5 k (2N - k) log K        AIC_k = -2K L_k + 2 k (2N - k)        K = num_snapshots
+ *     count  = the smallest k in 0 .. max_sources that attains the minimum
+ *   (scale-invariant, so forward-backward averaging's factor does not matter; forward-backward-specific parameter counts
+ *   are not applied).  Eigenvalues come from the double Jacobi kernels of MUSIC_lin_array (never the subspace iteration,
+ *   which does not form the noise eigenvalues); internal precision 32 is not supported: DOA_ERR_UNSUPPORTED.
+ * Item layouts: input as MUSIC_lin_array; count_out = one int32 per item; eig_out (optional, NULL = not wanted) =
+ *   num_ant_ele floats per item, the eigenvalues ascending.
+ * create validates before the device is touched: 2 <= num_ant_ele (> DOA_MAX_ANT_ELE: rejected), num_snapshots >= 2,
+ *   method DOA_SOURCE_COUNT_MDL or _AIC, 1 <= max_sources <= num_ant_ele - 1.
+ * --------------------------------------------------------------------------------------------- */
+#define DOA_SOURCE_COUNT_MDL 0
+#define DOA_SOURCE_COUNT_AIC 1
+typedef struct doa_source_count doa_source_count_t;
+
+DOA_HIP_API doa_source_count_t *doa_source_count_create(int num_ant_ele, int num_snapshots, int method, int max_sources);
+DOA_HIP_API void doa_source_count_destroy(doa_source_count_t *h);
+DOA_HIP_API int doa_source_count_work(doa_source_count_t *h, int noutput_items, const void *cov_items, void *count_out,
+                                      void *eig_out);
+DOA_HIP_API int doa_source_count_work_dev(doa_source_count_t *h, int noutput_items, const void *d_cov_items,
+                                          void *d_count_out, void *d_eig_out, void *hip_stream);
+
+/* MUSIC_lin_array with a count per item: counts = one int32 per item, used in place of the handle's num_targets (noise set =
+ * the num_ant_ele - count smallest eigenvalues).  Count 0 is legal: P_N = I exactly, the row is all 0.0 dB.  A count outside
+ * 0 .. num_ant_ele-1 (the -1 status of source_count included) gives a NaN row; other items are not affected.  Always the
+ * double Jacobi route (a uniform count therefore agrees with doa_MUSIC_lin_array_work to the parity bounds, not bit for
+ * bit); a handle at internal precision 32: DOA_ERR_UNSUPPORTED.  NULL counts: DOA_ERR_INVALID_ARG. */
+DOA_HIP_API int doa_MUSIC_lin_array_work_counts(doa_MUSIC_lin_array_t *h, int noutput_items, const void *cov_items,
+                                                const void *counts, void *spectrum_out);
+DOA_HIP_API int doa_MUSIC_lin_array_work_dev_counts(doa_MUSIC_lin_array_t *h, int noutput_items, const void *d_cov_items,
+                                                    const void *d_counts, void *d_spectrum_out, void *hip_stream);
+/* find_local_max with a count per item: counts = one int32 m_i per item.  The first m_i slots of both outputs are what
+ * find_local_max(m_i, vector_len, x_min, x_max) writes for that vector (fill rule and the m_i == 1 global arg-max rule
+ * included); items stay num_max_vals floats wide and the remaining slots are NaN; m_i outside 0 .. num_max_vals: all NaN. */
+DOA_HIP_API int doa_find_local_max_work_counts(doa_find_local_max_t *h, int noutput_items, const void *input_items0,
+                                               const void *counts, void *output_items0, void *output_items1);
+DOA_HIP_API int doa_find_local_max_work_dev_counts(doa_find_local_max_t *h, int noutput_items, const void *d_input_items0,
+                                                   const void *d_counts, void *d_output_items0, void *d_output_items1,
+                                                   void *hip_stream);
+/* music_pipeline with the count estimated per snapshot: K1 exactly as doa_music_pipeline_work_dev runs it (fused gains,
+ * sc16 input and overlap honoured; the covariance is bit-identical), then ONE eigen launch that also estimates the count
+ * (K = snapshot_size, max_sources = the handle's num_targets, `method` as above) and forms each item's noise set from it,
+ * the scan, and the counted peak pick: four launches (a fifth, which only turns the rows of count -1 items into NaN, when
+ * d_spectrum_out is given), asynchronous on hip_stream.  d_count_out (int32 per item) is
+ * required; d_eig_out (num_ant_ele floats per item), d_cov_out and d_spectrum_out may be NULL.  d_max_out / d_argmax_out
+ * stay num_targets floats per item: the first count slots are find_local_max(count, ...)'s, the rest NaN; count -1: the
+ * spectrum row and all slots are NaN; count 0: the row is 0.0 dB and all slots are NaN.  The outputs are bit-identical to
+ * the chain source_count -> MUSIC_lin_array_work_dev_counts -> find_local_max_work_dev_counts on the covariance written.
+ * One batch of at most max_batch items; internal precision 32: DOA_ERR_UNSUPPORTED. */
+DOA_HIP_API int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
+                                                 const void *const *d_input_items, int method, void *d_cov_out,
+                                                 void *d_spectrum_out, void *d_max_out, void *d_argmax_out,
+                                                 void *d_count_out, void *d_eig_out, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
  * root_pipeline — autocorrelate -> rootMUSIC_linear_array on device-resident streams: the Root-MUSIC branch of the hot
  *   path as one handle (the chain apps/run_RootMUSIC_lin_array_simulation.grc wires; reference work being chained:
  *   lib/autocorrelate_impl.cc:83-118 -> lib/rootMUSIC_linear_array_impl.cc:90-152).  Same conventions as music_pipeline:
