@@ -90,6 +90,10 @@ int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_c
 // after the scan of a per-item-count call: rows (P floats) of items whose count is outside 0..N-1 become NaN (the scan kernels
 // themselves write 0.0 dB for a NaN record)
 int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, void *d_spec, hipStream_t st);
+// spatial smoothing (spatial_smooth.hip; definition in include/doa_hip.h): n_items column-major N x N items (upper triangle
+// read) -> S x S items, full Hermitian.  fb: 0 forward, 1 forward-backward.  d_Rs must not overlap d_R (not checked).
+// 16-byte loads and stores when both pointers are 16-byte aligned, 8-byte ones otherwise: the same bits either way.
+int launch_spatial_smooth(int N, int S, int fb, int n_items, const void *d_R, void *d_Rs, hipStream_t st);
 inline bool music_uses_cheb(int N, int bits) { return N <= 4 && bits == 64; }
 constexpr int kChebRecord = 8;      // doubles per item
 // diagnostics: items that left the signal-subspace fast path of K2+K3 for the Jacobi fall-back since the last reset

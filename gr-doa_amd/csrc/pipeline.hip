@@ -33,6 +33,8 @@ struct doa_music_pipeline {
     bool has_gain = false;
     int format = DOA_SAMPLE_FC32;   // doa_music_pipeline_set_input_format
     float scale = 1.0f;
+    int S = 0, fb = 0;              // doa_music_pipeline_set_spatial_smoothing: subarray size (0 = off), forward-backward
+    doa::DevBuf d_smooth;           // the smoothed items (S * S per item) between K1 and the eigen stage
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     doa::DevBuf d_in[2], d_res;
@@ -40,7 +42,7 @@ struct doa_music_pipeline {
     doa::PinnedBuf h_stage;         // scheduler-sized calls: one page-locked staging buffer, one copy each way
     int fail_chunk = -1;            // doa_music_pipeline_inject_failure, host-pointer entry: one-shot, cleared by every call (tests)
     // doa_music_pipeline_work_dev_batches: the library's own overlap lanes (pipeline_lanes.hpp); a lane's buffers:
-    enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch };
+    enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch, kSmooth };
     doa::PipeLanes lanes;
 };
 
@@ -50,6 +52,7 @@ struct PipeWs {
     void *cheb;             // N <= 4, double: their pre-transformed twins for the lean scan kernel (else NULL)
     void *spec_scratch;     // P floats per item, used when the caller does not want the spectrum
     void *work;             // K1's piece sums (overlapping windows), or NULL
+    void *smooth;           // spatial smoothing on: S * S gr_complex per item (else unused)
     doa::DevBuf *scratch;   // grown on demand: the serial peak pick of unusual vector lengths
     size_t scratch_item_off;
 };
@@ -63,6 +66,8 @@ static int run_k1(doa_music_pipeline *h, int n, const void *const *d_in, void *c
     return doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_in, cov, st, h->has_gain ? h->d_gain.p : nullptr, ws.work,
                                      h->format, h->scale);
 }
+// the array the eigen stage, the scan and the peak pick see: the subarray of a smoothed handle
+static int evd_elements(const doa_music_pipeline *h) { return h->S ? h->S : h->N; }
 static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, void *mx, void *am, const PipeWs &ws, hipStream_t st)
 {
     const bool store_spec = (spec != nullptr);
@@ -71,8 +76,13 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
     int rc = DOA_OK;
     const bool dbl = (h->bits == 64);
     void *coef = ws.coef;
+    if (h->S) {                                 // spatial smoothing: one launch, part of stage bit 1; `cov` stays the N x N item
+        if (!(skip & 2)) rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, n, cov, ws.smooth, st);
+        if (rc != DOA_OK) return rc;
+        cov = ws.smooth;
+    }
     if (!(skip & 2))
-        rc = doa::launch_music_evd(h->N, h->music.M, n, cov, dbl ? nullptr : coef, dbl ? coef : nullptr, nullptr, h->bits, st, ws.cheb);
+        rc = doa::launch_music_evd(evd_elements(h), h->music.M, n, cov, dbl ? nullptr : coef, dbl ? coef : nullptr, nullptr, h->bits, st, ws.cheb);
     if (rc != DOA_OK) return rc;
     bool peaks_done = false;
     if (skip & 4) return n;
@@ -107,6 +117,7 @@ static int run_dev(doa_music_pipeline *h, int n, const void *const *d_in, void *
     ws.cheb = h->d_cheb.p ? static_cast<char *>(h->d_cheb.p) + item_off * doa::kChebRecord * sizeof(double) : nullptr;
     ws.spec_scratch = static_cast<char *>(h->d_spec.p) + item_off * h->peaks.L * sizeof(float);
     ws.work = h->d_work[lane].p;
+    ws.smooth = h->S ? h->d_smooth.as<float2>() + item_off * h->S * h->S : nullptr;
     ws.scratch = &h->d_scratch;
     ws.scratch_item_off = item_off;
     return run_ws(h, n, d_in, cov, spec, mx, am, ws, st);
@@ -159,6 +170,7 @@ void doa_music_pipeline_destroy(doa_music_pipeline_t *h)
     h->music.release();
     h->peaks.release();
     h->d_cov.release(); h->d_coef.release(); h->d_cheb.release(); h->d_spec.release(); h->d_scratch.release(); h->d_gain.release();
+    h->d_smooth.release();
     h->d_res.release(); h->h_stage.release();
     for (auto &b : h->d_work) b.release();
     for (auto &b : h->d_in) b.release();
@@ -201,6 +213,31 @@ int doa_music_pipeline_set_stages(doa_music_pipeline_t *h, int stage_mask)
     doa::clear_error();
     if (!h || stage_mask < 0 || stage_mask > 7) { doa::set_error("music_pipeline_set_stages: bad arguments"); return DOA_ERR_INVALID_ARG; }
     h->stages = (unsigned)stage_mask;
+    return DOA_OK;
+}
+
+int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarray_size, int forward_backward)
+{
+    doa::clear_error();
+    if (!h) { doa::set_error("music_pipeline_set_spatial_smoothing: bad arguments"); return DOA_ERR_INVALID_ARG; }
+    const int S = subarray_size, fb = S ? forward_backward : 0;
+    if (S != 0 && (S < 2 || S > h->N || h->music.M >= S || (fb != 0 && fb != 1))) {
+        doa::set_error("music_pipeline_set_spatial_smoothing: need subarray_size 0 (off) or 2 <= subarray_size <= inputs with "
+                       "num_targets < subarray_size, forward_backward 0 or 1 (got %d, %d; inputs=%d num_targets=%d)", S,
+                       forward_backward, h->N, h->music.M);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (S == h->S && fb == h->fb) return DOA_OK;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const int elements = S ? S : h->N;
+    int rc = S ? h->d_smooth.reserve((size_t)h->max_batch * S * S * sizeof(float2)) : DOA_OK;
+    if (rc == DOA_OK && doa::music_uses_cheb(elements, h->bits)) rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double));
+    if (rc != DOA_OK) return rc;
+    // the scan's tables for `elements` antennas (the steering phases themselves depend on norm_spacing and pspectrum_len alone)
+    const int was = h->music.N;
+    rc = h->music.build(h->music.norm_spacing, h->music.M, elements, h->music.P);
+    if (rc != DOA_OK) { h->music.N = was; return rc; }
+    h->S = S; h->fb = fb;
     return DOA_OK;
 }
 
@@ -254,7 +291,8 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const int n = noutput_items;
-    const bool cheb = doa::music_uses_cheb(h->N, 64);
+    const int elements = evd_elements(h);
+    const bool cheb = doa::music_uses_cheb(elements, 64);
     // (a handle created at precision 32 and switched to 64 afterwards has no Chebyshev records yet)
     if (cheb && !h->d_cheb.p)
         if (int rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double)); rc != DOA_OK) return rc;
@@ -263,15 +301,19 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     PipeWs ws{};
     ws.work = h->d_work[0].p;
     int rc = run_k1(h, n, d_input_items, cov, ws, st);
+    if (rc == DOA_OK && h->S) {
+        rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, n, cov, h->d_smooth.p, st);
+        cov = h->d_smooth.p;
+    }
     if (rc == DOA_OK)
-        rc = doa::launch_music_evd_counts(h->N, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->music.M, h->d_coef.p,
+        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->music.M, h->d_coef.p,
                                           cheb ? h->d_cheb.p : nullptr, st);
     if (rc == DOA_OK)
         rc = doa::launch_music_scan(h->music, 64, n, h->d_coef.p, spec, nullptr, st, nullptr, nullptr, nullptr, nullptr, true,
                                     cheb ? h->d_cheb.p : nullptr);
     // a spectrum the caller sees: the row of a count -1 item is NaN, as MUSIC_lin_array_work_dev_counts leaves it (a fifth,
     // one-load-per-item launch; the peak pick below does not read the rows of such items)
-    if (rc == DOA_OK && d_spectrum_out) rc = doa::launch_music_invalid_rows(h->N, h->peaks.L, n, d_count_out, spec, st);
+    if (rc == DOA_OK && d_spectrum_out) rc = doa::launch_music_invalid_rows(elements, h->peaks.L, n, d_count_out, spec, st);
     if (rc != DOA_OK) return rc;
     if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
         rc = doa::launch_find_local_max_counts(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, st);
@@ -367,7 +409,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     const bool dbl = (h->bits == 64);
 
     // ---- the plan: groups of consecutive batches and their lanes ----
-    const bool lean_shape = h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
+    const bool lean_shape = h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
                             (long long)doa::kMaxGroup * n <= (1 << 28);
     const int L_all = solo ? 1 : h->lanes.n_lanes;
     const int L = (lean_shape && group_lanes() < L_all) ? group_lanes() : L_all;
@@ -444,9 +486,11 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     const size_t work_bytes = doa::autocorrelate_workspace_bytes(N, h->K, h->ovl, h->max_batch);
     using H = doa_music_pipeline;
     // a lane's buffers hold a whole group: records and covariances are 64-128 B per item; the angles-only scratch rows are bounded (G_angles)
-    auto reserve = [&](doa::DevBuf &coef, doa::DevBuf &cheb, doa::DevBuf &cov, doa::DevBuf &spec, doa::DevBuf &work) -> int {
+    auto reserve = [&](doa::DevBuf &coef, doa::DevBuf &cheb, doa::DevBuf &cov, doa::DevBuf &spec, doa::DevBuf &work,
+                       doa::DevBuf &smooth) -> int {
         int rc = coef.reserve((size_t)h->max_batch * doa::coef_stride(N) * (dbl ? sizeof(double) : sizeof(float)));
-        if (rc == DOA_OK && doa::music_uses_cheb(N, h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
+        if (rc == DOA_OK && h->S) rc = smooth.reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
+        if (rc == DOA_OK && doa::music_uses_cheb(evd_elements(h), h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
         if (rc == DOA_OK && need_cov) rc = cov.reserve((size_t)G * h->max_batch * N * N * sizeof(float2));
         if (rc == DOA_OK && need_spec) rc = spec.reserve((size_t)G_angles * h->max_batch * P * sizeof(float));
         if (rc == DOA_OK && work_bytes) rc = work.reserve(work_bytes);
@@ -480,10 +524,11 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     };
     if (solo) {
         hipStream_t caller = static_cast<hipStream_t>(hip_stream);
-        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0]);
+        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0], h->d_smooth);
         if (rc != DOA_OK) return rc;
         PipeWs ws;
         ws.coef = h->d_coef.p; ws.cheb = h->d_cheb.p; ws.spec_scratch = h->d_spec.p; ws.work = h->d_work[0].p;
+        ws.smooth = h->d_smooth.p;
         ws.scratch = &h->d_scratch; ws.scratch_item_off = 0;
         for (size_t u = 0; u < plan.size() && rc >= 0; u++) rc = launch(plan[u], ws, h->d_cov.p, caller);
         if (rc >= 0 && injected) {
@@ -499,7 +544,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         return n_batches * n;
     }
     auto prepare = [&](doa::PipeLane &ln) -> int {
-        return reserve(ln.buf[H::kCoef], ln.buf[H::kCheb], ln.buf[H::kCov], ln.buf[H::kSpec], ln.buf[H::kWork]);
+        return reserve(ln.buf[H::kCoef], ln.buf[H::kCheb], ln.buf[H::kCov], ln.buf[H::kSpec], ln.buf[H::kWork], ln.buf[H::kSmooth]);
     };
     auto launch_unit = [&](int u, doa::PipeLane &ln) -> int {
         const PlanGroup &g = plan[u];
@@ -507,6 +552,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
             if (const int rc = h->lanes.synchronize(); rc != DOA_OK) return rc;
         PipeWs ws;
         ws.coef = ln.buf[H::kCoef].p; ws.cheb = ln.buf[H::kCheb].p; ws.spec_scratch = ln.buf[H::kSpec].p; ws.work = ln.buf[H::kWork].p;
+        ws.smooth = ln.buf[H::kSmooth].p;
         ws.scratch = &ln.buf[H::kScratch]; ws.scratch_item_off = 0;
         return launch(g, ws, ln.buf[H::kCov].p, ln.st);
     };
@@ -698,7 +744,7 @@ int doa_music_pipeline_set_internal_precision(doa_music_pipeline_t *h, int bits)
 {
     doa::clear_error();
     if (!h || (bits != 32 && bits != 64)) { doa::set_error("music_pipeline_set_internal_precision: need a handle and bits = 32 or 64"); return DOA_ERR_INVALID_ARG; }
-    if (doa::music_uses_cheb(h->N, bits)) {
+    if (doa::music_uses_cheb(evd_elements(h), bits)) {
         if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
         const int rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double));
         if (rc != DOA_OK) return rc;

@@ -420,6 +420,38 @@ class source_count(_Block):
                                                    _opt_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _stream_ptr(stream)))
 
 
+class spatial_smooth(_Block):
+    """doa.spatial_smooth(num_ant_ele, subarray_size, forward_backward=True) — spatial smoothing of covariance items for
+    coherent sources (multipath, emitters on one oscillator): each num_ant_ele x num_ant_ele item is replaced by the
+    average of its num_ant_ele - subarray_size + 1 overlapping subarray_size x subarray_size diagonal blocks, with
+    forward_backward also of their persymmetric images (definition: include/doa_hip.h).  The output feeds MUSIC_lin_array /
+    rootMUSIC_linear_array / source_count created for subarray_size elements.  Not a block of the reference."""
+
+    _destroy = staticmethod(lib.doa_spatial_smooth_destroy)
+
+    def __init__(self, num_ant_ele, subarray_size, forward_backward=True):
+        super().__init__()
+        self.num_ant_ele, self.subarray_size = int(num_ant_ele), int(subarray_size)
+        self.forward_backward = int(forward_backward)
+        self._h = check_handle(lib.doa_spatial_smooth_create(self.num_ant_ele, self.subarray_size, self.forward_backward),
+                               "spatial_smooth")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_C64, self.subarray_size ** 2)]
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        out = output_items[0]
+        assert a.size >= n * self.num_ant_ele ** 2
+        assert out.dtype == _C64 and out.flags.c_contiguous and out.size >= n * self.subarray_size ** 2
+        return check(lib.doa_spatial_smooth_work(self._h, n, _vp(a), _vp(out)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
+        """d_out_ptr must not overlap d_in_ptr."""
+        return check(lib.doa_spatial_smooth_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
+                                                     C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
+
+
 class rootMUSIC_linear_array(_Block):
     """doa.rootMUSIC_linear_array(norm_spacing, num_targets, inputs) — gr::sync_block
     (reference lib/rootMUSIC_linear_array_impl.cc:46-59)."""
@@ -512,6 +544,7 @@ class music_pipeline(_StreamInput, _Block):
         self.inputs, self.snapshot_size, self.overlap_size = int(inputs), int(snapshot_size), int(overlap_size)
         self.avg_method, self.norm_spacing = int(avg_method), float(norm_spacing)
         self.num_targets, self.pspectrum_len, self.max_batch = int(num_targets), int(pspectrum_len), int(max_batch)
+        self.subarray_size, self.forward_backward = 0, 0            # set_spatial_smoothing
         self._h = check_handle(lib.doa_music_pipeline_create(self.inputs, self.snapshot_size, self.overlap_size,
                                                              self.avg_method, self.norm_spacing, self.num_targets,
                                                              self.pspectrum_len, self.max_batch), "music_pipeline")
@@ -541,6 +574,15 @@ class music_pipeline(_StreamInput, _Block):
 
     def fuse_antenna_correction(self, correction) -> None:
         _fuse(lib.doa_music_pipeline_fuse_antenna_correction, self._h, correction, self.inputs)
+
+    def set_spatial_smoothing(self, subarray_size, forward_backward=True) -> None:
+        """Spatial smoothing between K1 and the eigen stage (coherent sources), from the next work call on, in every entry:
+        eigen stage, scan and peak pick then run for subarray_size elements (num_targets < subarray_size <= inputs); the
+        covariance output stays inputs x inputs; work_dev_auto's eigenvalues are subarray_size per item.  0 switches it off
+        (doa_music_pipeline_set_spatial_smoothing)."""
+        check(lib.doa_music_pipeline_set_spatial_smoothing(self._h, int(subarray_size), int(forward_backward)))
+        self.subarray_size = int(subarray_size)
+        self.forward_backward = int(forward_backward) if self.subarray_size else 0
 
     def set_stages(self, cov=True, evd=True, scan=True) -> None:
         """Profiling aid: drop stages from later work_dev calls (their outputs keep the previous call's values)."""

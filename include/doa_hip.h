@@ -432,6 +432,55 @@ DOA_HIP_API int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int no
                                                  void *d_count_out, void *d_eig_out, void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * spatial_smooth — spatial smoothing of covariance items for COHERENT sources (a source and its multipath echo, emitters
+ *   locked to one oscillator): the signal part of their covariance has rank one, and MUSIC, Root-MUSIC and source_count
+ *   all fail quietly on it.  For a uniform linear array the N x N covariance (N = num_ant_ele) is replaced by the average
+ *   of its L = N - S + 1 overlapping S x S diagonal blocks (S = subarray_size; Shan-Wax-Kailath), with forward_backward
+ *   = 1 also of their persymmetric images (Pillai-Kwon); the smoothed items are covariances of an S-element array with
+ *   the same spacing and go to MUSIC_lin_array / rootMUSIC_linear_array / source_count created for S elements.  Up to
+ *   S - 1 sources can be resolved; forward smoothing restores the rank for up to L mutually coherent sources, the
+ *   forward-backward form for more.  Not a block of the reference.
+ * The definition, one for every entry (tests/spatial_smooth_ref.py restates it in numpy):
+ *   input item   column-major N x N gr_complex, as MUSIC_lin_array takes it; ONLY THE UPPER TRIANGLE IS READ, and of the
+ *                diagonal the real part (its imaginary part is taken as 0): H = the Hermitian matrix these define
+ *   output item  column-major S x S gr_complex, the full Hermitian matrix
+ *   for 0 <= i <= j < S:
+ *     f[i,j]   = sum_{l=0}^{L-1} (double) H[i+l, j+l]        l ascending, re and im separately
+ *     fb == 0 : s = f[i,j]
+ *     fb == 1 : s = 0.5 * (f[i,j] + f[S-1-j, S-1-i])         (= 0.5 (F + J conj(F) J); no conjugate appears)
+ *     out[i,j] = (float)(s * (1.0 / L))                      1.0 / L formed in double; one rounding per component
+ *     out[j,i] = conj(out[i,j]);  Im out[i,i] = +0.0
+ *   No product feeds an addition, so an implementation that does these operations in this order is bit-identical to the
+ *   numpy statement; the device kernel is, for either pointer alignment and any batch size.  Non-finite entries propagate
+ *   by IEEE rules to the outputs whose sums touch them; there is no status output.  S == N with fb == 0 is the Hermitian
+ *   completion of the upper triangle.  (MUSIC and the source count are scale-invariant; the 1 / L keeps the items
+ *   covariances.)
+ * create validates before the device is touched: 2 <= subarray_size <= num_ant_ele <= DOA_MAX_ANT_ELE, forward_backward
+ *   0 or 1.  smoothed_items must NOT overlap cov_items (not checked).  The device entry takes 16-byte loads and stores when
+ *   both pointers are 16-byte aligned and 8-byte ones otherwise (gr_complex alignment is the minimum).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct doa_spatial_smooth doa_spatial_smooth_t;
+
+DOA_HIP_API doa_spatial_smooth_t *doa_spatial_smooth_create(int num_ant_ele, int subarray_size, int forward_backward);
+DOA_HIP_API void doa_spatial_smooth_destroy(doa_spatial_smooth_t *h);
+DOA_HIP_API int doa_spatial_smooth_work(doa_spatial_smooth_t *h, int noutput_items, const void *cov_items,
+                                        void *smoothed_items);
+DOA_HIP_API int doa_spatial_smooth_work_dev(doa_spatial_smooth_t *h, int noutput_items, const void *d_cov_items,
+                                            void *d_smoothed_items, void *hip_stream);
+/* music_pipeline with the smoothing between K1 and the eigen stage: a per-handle setting, taking effect from the next
+ * work call, honoured by every entry (work_dev, work_dev_batches, work, work_dev_auto).  subarray_size == 0 switches it
+ * off (the default).  Otherwise 2 <= subarray_size <= inputs, num_targets < subarray_size, forward_backward 0 or 1; a
+ * bad call returns DOA_ERR_INVALID_ARG and leaves the handle as it was.  When it is on:
+ *   K1 runs exactly as before (fused gains, sc16 and overlap honoured) and d_cov_out stays the inputs x inputs
+ *   covariance, bit-identical to an unsmoothed handle's; ONE more launch writes the smoothed items to a workspace of the
+ *   handle, and eigen stage, scan and peak pick run for subarray_size elements: the outputs are those of the chain
+ *   spatial_smooth -> MUSIC_lin_array(norm_spacing, num_targets, subarray_size, pspectrum_len) -> find_local_max on the
+ *   covariance written.  The smoothing arithmetic is the definition above at either internal precision.
+ *   work_dev_batches runs one chain of launches per batch (no grouped launches for a smoothed handle).
+ *   work_dev_auto: K in the criterion stays snapshot_size, and d_eig_out is subarray_size floats per item. */
+DOA_HIP_API int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarray_size, int forward_backward);
+
+/* ---------------------------------------------------------------------------------------------
  * root_pipeline — autocorrelate -> rootMUSIC_linear_array on device-resident streams: the Root-MUSIC branch of the hot
  *   path as one handle (the chain apps/run_RootMUSIC_lin_array_simulation.grc wires; reference work being chained:
  *   lib/autocorrelate_impl.cc:83-118 -> lib/rootMUSIC_linear_array_impl.cc:90-152).  Same conventions as music_pipeline:
