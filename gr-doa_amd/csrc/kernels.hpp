@@ -140,8 +140,15 @@ int launch_find_local_max_serial_counts(const PeakTables &t, int n_items, const 
 // d_roots (optional, diagnostics): the 2N-2 roots found per item as double2, in the kernel's lane order.
 int launch_root_music(int N, int M, float norm_spacing, int n_items, const void *d_coef, void *d_out,
                       void *d_status, hipStream_t st, void *d_roots = nullptr);
+// with a count per item (d_counts: int32 m_i; root_music.hip, RootCounts): items stay W floats wide.  1 <= m_i <= min(W, N-1):
+// the first m_i slots as launch_root_music writes them for M = m_i, the others NaN, status 0 / 1; m_i == 0: all NaN, status 0,
+// the record is not read; any other value: all NaN, status 2.
+int launch_root_music_counts(int N, int W, float norm_spacing, int n_items, const void *d_coef, const void *d_counts, void *d_out,
+                             void *d_status, hipStream_t st, void *d_roots = nullptr);
 // the selection stage of K6 alone, on caller-supplied roots (n_items x (2N-2) double2): diagnostics
 int launch_root_select(int N, int M, float norm_spacing, int n_items, const void *d_roots, void *d_out, void *d_status,
                        hipStream_t st);
+int launch_root_select_counts(int N, int W, float norm_spacing, int n_items, const void *d_roots, const void *d_counts,
+                              void *d_out, void *d_status, hipStream_t st);
 
 }  // namespace doa

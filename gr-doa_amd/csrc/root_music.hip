@@ -50,6 +50,36 @@ __device__ __forceinline__ double fast_rcp(double x)
     return fma(y, e, y);
 }
 
+// How many angles an item wants (the pattern of find_local_max.hip's PeakFixedM / PeakCounts).  RootFixedM: the handle's
+// num_targets for every item -- no code added, the kernels are the ones they were.  RootCounts: a count m_i per item read from
+// an int32 array; items stay W = num_targets floats wide:
+//   1 <= m_i <= min(W, N-1)  the first m_i slots as the fixed kernel writes them for M = m_i, slots m_i.. NaN, status 0 / 1
+//   m_i == 0                 W NaN, status 0 -- decided from the count: the record of such an item (u_0 = N, u_l = 0: one root
+//                            of multiplicity 2N-2 at 0) is never read and the iteration never runs on it
+//   anything else            W NaN, status 2 ("no usable count"; the estimator's -1 among them)
+// The count is range-checked where it is loaded (item_count); nothing but the checked value leaves that function, so no
+// address and no loop bound is ever formed from a raw count.
+struct RootFixedM {
+    static constexpr bool kCounted = false;
+    int M;
+    __device__ __forceinline__ int width() const { return M; }
+};
+struct RootCounts {
+    static constexpr bool kCounted = true;
+    const int *counts;
+    int W;
+    __device__ __forceinline__ int width() const { return W; }
+    // `item` is already clamped to 0..n_items-1.  Returns m_i (0 when there is nothing to find); code: the status of such an item
+    __device__ __forceinline__ int item_count(int item, int N, int &code) const
+    {
+        const int c = counts[item];
+        const int top = (W < N - 1) ? W : N - 1;
+        const bool usable = (c >= 0) && (c <= top);
+        code = usable ? 0 : 2;
+        return usable ? c : 0;
+    }
+};
+
 // Selection stage (reference lib/rootMUSIC_linear_array_impl.cc:122-145) on the GR lanes of one group, lane k holding
 // root k (is_root: k < 2N-2): dist = 1 - |z| (:122), keep dist > 0 -- strictly inside (:125-127) --, num_targets times the
 // interior root closest to the circle (index_min: ties -> the first, i.e. the lowest root index), angle =
@@ -57,11 +87,18 @@ __device__ __forceinline__ double fast_rcp(double x)
 // roots are exhausted index_min lands on an inf entry, arg(inf + 0i) = 0 and the slot reads 90 degrees --, ascending
 // sort (:144; NaN last).  No interior root at all: the reference raises inside arma::index_min; here NaN angles and
 // status 1.  Shared by the solver kernel and by root_select_kernel (the selection on caller-supplied roots).
-template <int GR>
+// Counted (Cnt = RootCounts): n_want = m, the group's checked count; code = its status when m == 0.  The groups of one wave then want
+// different numbers of picks, and both loops below shuffle: they run to the WAVE-UNIFORM bound W with the effects of the
+// steps j >= m predicated off (dist keeps its value, the rank ignores slot j), so every lane of the wave executes every
+// shuffle -- no lane is ever read while it is switched off -- and every source lane (lane ^ m with m < GR, base + bk with
+// bk < GR, base + j with j < W <= N-1 < GR) lies in the reading lane's own group.  Steps j < m see exactly the state the
+// fixed kernel's steps see for M = m.
+template <int GR, class Cnt>
 __device__ __forceinline__ void root_select(double zr, double zi, bool is_root, int k, int base, int lane, int item,
-                                            bool real_item, int M, double two_pi_d, float *__restrict__ out,
-                                            int *__restrict__ status)
+                                            bool real_item, const Cnt cnt, int n_want, int code, double two_pi_d,
+                                            float *__restrict__ out, int *__restrict__ status)
 {
+    const int M = cnt.width();
     // dist = 1 - |z|; keep dist > 0; the M smallest, one at a time (:122-141)
     double dist = is_root ? 1.0 - sqrt(zr * zr + zi * zi) : -1.0;
     if (!(dist > 0.0)) dist = -1.0;
@@ -82,7 +119,8 @@ __device__ __forceinline__ void root_select(double zr, double zi, bool is_root, 
         if (bk < GR) {
             const double br = __shfl(zr, base + bk, kWave), bi = __shfl(zi, base + bk, kWave);
             ang = atan2(bi, br);
-            if (k == bk) dist = -1.0;
+            if constexpr (Cnt::kCounted) { if (k == bk && j < n_want) dist = -1.0; }
+            else { if (k == bk) dist = -1.0; }
         }
         const float a = (float)(180.0 * acos(ang / two_pi_d) / M_PI);
         if (k == j) my_aoa = a;
@@ -92,9 +130,19 @@ __device__ __forceinline__ void root_select(double zr, double zi, bool is_root, 
     int rank = 0;
     for (int j = 0; j < M; j++) {
         const float kj = __shfl(key, base + j, kWave);
-        rank += (kj < key || (kj == key && j < k)) ? 1 : 0;
+        if constexpr (Cnt::kCounted) rank += (j < n_want && (kj < key || (kj == key && j < k))) ? 1 : 0;
+        else rank += (kj < key || (kj == key && j < k)) ? 1 : 0;
     }
-    if (real_item) {
+    if constexpr (Cnt::kCounted) {
+        if (real_item) {
+            float *o = out + (size_t)item * M;
+            const bool found = (n_want > 0) && (n_inside != 0);
+            // lanes n_want..W-1 (all W of them when nothing was found): NaN; lanes 0..n_want-1: their pick at its rank < n_want
+            if (k < M && (k >= n_want || !found)) o[k] = __builtin_nanf("");
+            if (k < n_want && found) o[rank] = my_aoa;
+            if (k == 0 && status) status[item] = (n_want > 0) ? (found ? 0 : 1) : code;
+        }
+    } else if (real_item) {
         float *o = out + (size_t)item * M;
         if (n_inside == 0) {
             if (k < M) o[k] = __builtin_nanf("");
@@ -108,9 +156,13 @@ __device__ __forceinline__ void root_select(double zr, double zi, bool is_root, 
 
 // DEG = compile-time polynomial degree when it is known to be below GR (N = 4: degree 6 on 8 lanes),
 // so that neither the Horner recurrence nor the root-pair loop spends steps on padding.
-template <int GR, int DEG = GR, bool FLOAT_PHASE = true>
+// Counted (Cnt = RootCounts): a group whose checked count is 0 (a zero count, or no usable one) has is_root = false in all its
+// lanes and all-zero coefficients -- its record is not read --, so its p, p' and steps are finite, its rel is 0 in the float
+// and in the double phase, and the wave leaves the loops as soon as the groups that do have roots to find are done; no
+// cross-lane fetch leaves a group, so nothing of one group reaches another.
+template <int GR, int DEG = GR, bool FLOAT_PHASE = true, class Cnt = RootFixedM>
 __global__ __launch_bounds__(64) void root_music_group_kernel(const double *__restrict__ coef, float *__restrict__ out,
-                                                              int *__restrict__ status, int n_items, int N, int M,
+                                                              int *__restrict__ status, int n_items, int N, const Cnt cnt,
                                                               double two_pi_d, double2 *__restrict__ roots_out,
                                                               int float_iters, float float_tol2)
 {
@@ -121,14 +173,21 @@ __global__ __launch_bounds__(64) void root_music_group_kernel(const double *__re
     const bool real_item = item < n_items;
     if (!real_item) item = n_items - 1;
     const int D = 2 * N - 2;
-    const bool is_root = k < D;
+    int n_want = 0, code = 0;                             // (counted form only)
+    bool is_root = k < D;
+    if constexpr (Cnt::kCounted) {
+        n_want = cnt.item_count(item, N, code);
+        is_root = is_root && (n_want > 0);
+    }
     const double *co = coef + (size_t)item * (2 * N);
     // polynomial c[m], m = 0..D: c[N-1-l] = u_l, c[N-1+l] = conj(u_l); zero above D
     double cr[GR + 1], ci[GR + 1], ca[GR + 1];
 #pragma unroll
     for (int m = 0; m <= GR; m++) {
         double vr = 0.0, vi = 0.0;
-        if (m <= D) {
+        bool have = (m <= D);
+        if constexpr (Cnt::kCounted) have = have && (n_want > 0);
+        if (have) {
             const int l = (m <= N - 1) ? (N - 1 - m) : (m - (N - 1));
             if (l == 0) vr = co[0];
             else { vr = co[2 * l - 1]; vi = (m < N - 1) ? co[2 * l] : -co[2 * l]; }
@@ -256,13 +315,18 @@ __global__ __launch_bounds__(64) void root_music_group_kernel(const double *__re
         for (int m = 0; m <= GR; m++) csum += ca[m];
         if (!(csum < INFINITY)) { zr = __builtin_nan(""); zi = __builtin_nan(""); }
     }
+    if constexpr (Cnt::kCounted) {                        // diagnostics; an item without roots to find: NaN
+        if (roots_out && real_item && k < D)
+            roots_out[(size_t)item * D + k] = is_root ? make_double2(zr, zi) : make_double2(__builtin_nan(""), __builtin_nan(""));
+    } else {
     if (roots_out && real_item && is_root) roots_out[(size_t)item * D + k] = make_double2(zr, zi);    // diagnostics
-    root_select<GR>(zr, zi, is_root, k, base, lane, item, real_item, M, two_pi_d, out, status);
+    }
+    root_select<GR, Cnt>(zr, zi, is_root, k, base, lane, item, real_item, cnt, n_want, code, two_pi_d, out, status);
 }
 
 template <int GR, int DEG = GR>
 static void launch_root_group(int N, int M, int n_items, const void *d_coef, void *d_out, void *d_status, double two_pi_d,
-                              hipStream_t st, void *d_roots)
+                              hipStream_t st, void *d_roots, const void *d_counts = nullptr)
 {
     constexpr int IPW = kWave / GR;
     dim3 block(64), grid((n_items + IPW - 1) / IPW);
@@ -270,18 +334,24 @@ static void launch_root_group(int N, int M, int n_items, const void *d_coef, voi
     // (profiles/r04_lab_root_float_phase.txt has the sweep behind the two numbers)
     const int float_iters = DOA_LAB_ENV_INT("DOA_ROOT_FLOAT_ITERS", 12);
     const float float_tol2 = exp2f(-(float)DOA_LAB_ENV_INT("DOA_ROOT_FLOAT_TOL_LOG2", 33));      // 2^-33 = (1.1e-5)^2
+    if (d_counts) {                                       // a count per item, items M floats wide (always the float phase)
+        hipLaunchKernelGGL((root_music_group_kernel<GR, DEG, true, RootCounts>), grid, block, 0, st, (const double *)d_coef,
+                           (float *)d_out, (int *)d_status, n_items, N, RootCounts{(const int *)d_counts, M}, two_pi_d,
+                           (double2 *)d_roots, float_iters, float_tol2);
+        return;
+    }
     if (DOA_LAB_ENV_INT("DOA_ROOT_FLOAT_PHASE", 1))
         hipLaunchKernelGGL((root_music_group_kernel<GR, DEG, true>), grid, block, 0, st, (const double *)d_coef, (float *)d_out,
-                           (int *)d_status, n_items, N, M, two_pi_d, (double2 *)d_roots, float_iters, float_tol2);
+                           (int *)d_status, n_items, N, RootFixedM{M}, two_pi_d, (double2 *)d_roots, float_iters, float_tol2);
 #ifdef DOA_LAB
     else
         hipLaunchKernelGGL((root_music_group_kernel<GR, DEG, false>), grid, block, 0, st, (const double *)d_coef, (float *)d_out,
-                           (int *)d_status, n_items, N, M, two_pi_d, (double2 *)d_roots, 0, 0.f);
+                           (int *)d_status, n_items, N, RootFixedM{M}, two_pi_d, (double2 *)d_roots, 0, 0.f);
 #endif
 }
 
-int launch_root_music(int N, int M, float norm_spacing, int n_items, const void *d_coef, void *d_out, void *d_status,
-                      hipStream_t st, void *d_roots)
+static int launch_root_any(int N, int M, float norm_spacing, int n_items, const void *d_coef, const void *d_counts, void *d_out,
+                           void *d_status, hipStream_t st, void *d_roots)
 {
     if (n_items <= 0) return DOA_OK;
     const double two_pi_d = 2 * M_PI * (double)norm_spacing;   // 2*datum::pi*d_norm_spacing, float promoted (:135)
@@ -290,22 +360,39 @@ int launch_root_music(int N, int M, float norm_spacing, int n_items, const void 
         return DOA_ERR_UNSUPPORTED;
     }
     const int D = 2 * N - 2;
-    if (D <= 2) launch_root_group<2>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots);
-    else if (D <= 4) launch_root_group<4>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots);
-    else if (D == 6) launch_root_group<8, 6>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots);
-    else if (D <= 8) launch_root_group<8>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots);
-    else if (D <= 16) launch_root_group<16>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots);
-    else launch_root_group<32>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots);
+    if (D <= 2) launch_root_group<2>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots, d_counts);
+    else if (D <= 4) launch_root_group<4>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots, d_counts);
+    else if (D == 6) launch_root_group<8, 6>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots, d_counts);
+    else if (D <= 8) launch_root_group<8>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots, d_counts);
+    else if (D <= 16) launch_root_group<16>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots, d_counts);
+    else launch_root_group<32>(N, M, n_items, d_coef, d_out, d_status, two_pi_d, st, d_roots, d_counts);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
+}
+
+int launch_root_music(int N, int M, float norm_spacing, int n_items, const void *d_coef, void *d_out, void *d_status,
+                      hipStream_t st, void *d_roots)
+{
+    return launch_root_any(N, M, norm_spacing, n_items, d_coef, nullptr, d_out, d_status, st, d_roots);
+}
+
+int launch_root_music_counts(int N, int W, float norm_spacing, int n_items, const void *d_coef, const void *d_counts, void *d_out,
+                             void *d_status, hipStream_t st, void *d_roots)
+{
+    if (n_items > 0 && (!d_counts || W < 1 || W > N - 1)) {
+        set_error("rootMUSIC: per-item counts need the count array and 1 <= num_targets <= num_ant_ele - 1 (got %d, %d)", W, N);
+        return DOA_ERR_INVALID_ARG;
+    }
+    return launch_root_any(N, W, norm_spacing, n_items, d_coef, d_counts, d_out, d_status, st, d_roots);
 }
 
 // The selection stage alone, on caller-supplied roots (diagnostics: doa_rootMUSIC_linear_array_select_debug): the same
 // root_select<GR> instantiation the solver kernel of this array size ends in, fed from memory instead of from the
 // Aberth iteration, so every branch of the rule can be driven with hand-made root lists.
-template <int GR>
+template <int GR, class Cnt = RootFixedM>
 __global__ __launch_bounds__(64) void root_select_kernel(const double2 *__restrict__ roots, float *__restrict__ out,
-                                                         int *__restrict__ status, int n_items, int N, int M, double two_pi_d)
+                                                         int *__restrict__ status, int n_items, int N, const Cnt cnt,
+                                                         double two_pi_d)
 {
     constexpr int IPW = kWave / GR;
     const int lane = threadIdx.x & (kWave - 1);
@@ -314,21 +401,34 @@ __global__ __launch_bounds__(64) void root_select_kernel(const double2 *__restri
     const bool real_item = item < n_items;
     if (!real_item) item = n_items - 1;
     const int D = 2 * N - 2;
-    const bool is_root = k < D;
+    int n_want = 0, code = 0;                             // (counted form only)
+    bool is_root = k < D;
+    if constexpr (Cnt::kCounted) {
+        n_want = cnt.item_count(item, N, code);
+        is_root = is_root && (n_want > 0);                // an item without roots to find: its roots are not read
+    }
     double zr = 0.0, zi = 0.0;
     if (is_root) { const double2 z = roots[(size_t)item * D + k]; zr = z.x; zi = z.y; }
-    root_select<GR>(zr, zi, is_root, k, base, lane, item, real_item, M, two_pi_d, out, status);
+    root_select<GR, Cnt>(zr, zi, is_root, k, base, lane, item, real_item, cnt, n_want, code, two_pi_d, out, status);
 }
 
-int launch_root_select(int N, int M, float norm_spacing, int n_items, const void *d_roots, void *d_out, void *d_status,
-                       hipStream_t st)
+// d_counts == NULL: num_targets = M for every item; else a count per item, items M floats wide
+static int launch_root_select_any(int N, int M, float norm_spacing, int n_items, const void *d_roots, const void *d_counts,
+                                  void *d_out, void *d_status, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
     const double two_pi_d = 2 * M_PI * (double)norm_spacing;
     const int D = 2 * N - 2;
-#define DOA_SELECT(GR_)                                                                                             \
-    hipLaunchKernelGGL((root_select_kernel<GR_>), dim3((n_items + kWave / GR_ - 1) / (kWave / GR_)), dim3(64), 0, st, \
-                       (const double2 *)d_roots, (float *)d_out, (int *)d_status, n_items, N, M, two_pi_d)
+#define DOA_SELECT(GR_)                                                                                                       \
+    do {                                                                                                                      \
+        const dim3 grid_((n_items + kWave / GR_ - 1) / (kWave / GR_));                                                        \
+        if (d_counts)                                                                                                         \
+            hipLaunchKernelGGL((root_select_kernel<GR_, RootCounts>), grid_, dim3(64), 0, st, (const double2 *)d_roots,       \
+                               (float *)d_out, (int *)d_status, n_items, N, RootCounts{(const int *)d_counts, M}, two_pi_d);  \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((root_select_kernel<GR_>), grid_, dim3(64), 0, st, (const double2 *)d_roots, (float *)d_out,   \
+                               (int *)d_status, n_items, N, RootFixedM{M}, two_pi_d);                                         \
+    } while (0)
     if (D <= 2) DOA_SELECT(2);
     else if (D <= 4) DOA_SELECT(4);
     else if (D <= 8) DOA_SELECT(8);
@@ -337,6 +437,22 @@ int launch_root_select(int N, int M, float norm_spacing, int n_items, const void
 #undef DOA_SELECT
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
+}
+
+int launch_root_select(int N, int M, float norm_spacing, int n_items, const void *d_roots, void *d_out, void *d_status,
+                       hipStream_t st)
+{
+    return launch_root_select_any(N, M, norm_spacing, n_items, d_roots, nullptr, d_out, d_status, st);
+}
+
+int launch_root_select_counts(int N, int W, float norm_spacing, int n_items, const void *d_roots, const void *d_counts,
+                              void *d_out, void *d_status, hipStream_t st)
+{
+    if (n_items > 0 && (!d_counts || W < 1 || W > N - 1)) {
+        set_error("rootMUSIC: per-item counts need the count array and 1 <= num_targets <= num_ant_ele - 1 (got %d, %d)", W, N);
+        return DOA_ERR_INVALID_ARG;
+    }
+    return launch_root_select_any(N, W, norm_spacing, n_items, d_roots, d_counts, d_out, d_status, st);
 }
 
 }  // namespace doa
@@ -350,7 +466,7 @@ struct doa_rootMUSIC_linear_array {
     int bits = 64;
     int device = 0;
     hipStream_t stream = nullptr;
-    doa::DevBuf d_in, d_out, d_coef, d_status, d_roots;
+    doa::DevBuf d_in, d_out, d_coef, d_status, d_roots, d_counts;
     doa::PinnedBuf h_status;
 };
 
@@ -391,6 +507,7 @@ void doa_rootMUSIC_linear_array_destroy(doa_rootMUSIC_linear_array_t *h)
 {
     if (!h) return;
     h->d_in.release(); h->d_out.release(); h->d_coef.release(); h->d_status.release(); h->d_roots.release();
+    h->d_counts.release();
     h->h_status.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -443,6 +560,74 @@ int doa_rootMUSIC_linear_array_work(doa_rootMUSIC_linear_array_t *h, int noutput
     const int *stt = h->h_status.as<int>();
     for (int i = 0; i < noutput_items; i++)
         if (stt[i] != 0) {
+            doa::set_error("rootMUSIC_linear_array: item %d has no root strictly inside the unit circle "
+                           "(the reference raises in arma::index_min here)", i);
+            return DOA_ERR_NUMERIC;
+        }
+    return noutput_items;
+}
+
+int doa_rootMUSIC_linear_array_work_dev_counts(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *d_cov_items,
+                                               const void *d_counts, void *d_angles_out, int *d_status_out, void *hip_stream)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_cov_items || !d_counts || !d_angles_out))) {
+        doa::set_error("rootMUSIC_linear_array_work_dev_counts: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("rootMUSIC_linear_array_work_dev_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    int rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
+    if (rc == DOA_OK && !d_status_out) rc = h->d_status.reserve((size_t)noutput_items * sizeof(int));
+    if (rc != DOA_OK) return rc;
+    // forced-count mode: each item's record for its own noise set (a count outside 0..N-1: a NaN record, which the root
+    // kernel does not read)
+    rc = doa::launch_music_evd_counts(h->N, noutput_items, d_cov_items, d_counts, nullptr, nullptr, 0, 0, 0, h->d_coef.p, nullptr, st);
+    if (rc != DOA_OK) return rc;
+    rc = doa::launch_root_music_counts(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, d_counts, d_angles_out,
+                                       d_status_out ? (void *)d_status_out : h->d_status.p, st);
+    return rc == DOA_OK ? noutput_items : rc;
+}
+
+int doa_rootMUSIC_linear_array_work_counts(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *cov_items,
+                                           const void *counts, void *angles_out)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 || (noutput_items > 0 && (!cov_items || !counts || !angles_out))) {
+        doa::set_error("rootMUSIC_linear_array_work_counts: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("rootMUSIC_linear_array_work_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const size_t in_bytes = (size_t)noutput_items * h->N * h->N * sizeof(float2);
+    const size_t out_bytes = (size_t)noutput_items * h->M * sizeof(float);
+    const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
+    int rc = h->d_in.reserve(in_bytes);
+    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
+    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
+    if (rc == DOA_OK) rc = h->d_status.reserve(cnt_bytes);
+    if (rc == DOA_OK) rc = h->h_status.reserve(cnt_bytes);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa_rootMUSIC_linear_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, nullptr, h->stream);
+    if (rc < 0) { (void)hipStreamSynchronize(h->stream); return rc; }
+    DOA_HIP_TRY(hipMemcpyAsync(angles_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipMemcpyAsync(h->h_status.p, h->d_status.p, cnt_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    // status 2 (no usable count) is what the caller asked for, not an error
+    const int *stt = h->h_status.as<int>();
+    for (int i = 0; i < noutput_items; i++)
+        if (stt[i] == 1) {
             doa::set_error("rootMUSIC_linear_array: item %d has no root strictly inside the unit circle "
                            "(the reference raises in arma::index_min here)", i);
             return DOA_ERR_NUMERIC;
@@ -507,6 +692,36 @@ int doa_rootMUSIC_linear_array_select_debug(doa_rootMUSIC_linear_array_t *h, int
     if (status_out)
         DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, (size_t)noutput_items * sizeof(int), hipMemcpyDeviceToHost,
                                    h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    return noutput_items;
+}
+
+int doa_rootMUSIC_linear_array_select_counts_debug(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *roots_in,
+                                                   const void *counts, void *output_items0, int *status_out)
+{
+    doa::clear_error();
+    if (!h || noutput_items <= 0 || !roots_in || !counts || !output_items0) {
+        doa::set_error("rootMUSIC_linear_array_select_counts_debug: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const int D = 2 * h->N - 2;
+    const size_t out_bytes = (size_t)noutput_items * h->M * sizeof(float);
+    const size_t root_bytes = (size_t)noutput_items * D * sizeof(double2);
+    const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
+    int rc = h->d_out.reserve(out_bytes);
+    if (rc == DOA_OK) rc = h->d_roots.reserve(root_bytes);
+    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
+    if (rc == DOA_OK) rc = h->d_status.reserve(cnt_bytes);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_roots.p, roots_in, root_bytes, hipMemcpyHostToDevice, h->stream));
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa::launch_root_select_counts(h->N, h->M, h->norm_spacing, noutput_items, h->d_roots.p, h->d_counts.p, h->d_out.p,
+                                        h->d_status.p, h->stream);
+    if (rc != DOA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
+    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (status_out)
+        DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, cnt_bytes, hipMemcpyDeviceToHost, h->stream));
     DOA_HIP_TRY(hipStreamSynchronize(h->stream));
     return noutput_items;
 }

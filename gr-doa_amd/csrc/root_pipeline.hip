@@ -21,13 +21,15 @@ struct doa_root_pipeline {
     bool has_gain = false;
     int format = DOA_SAMPLE_FC32;   // doa_root_pipeline_set_input_format
     float scale = 1.0f;
+    int S = 0, fb = 0;              // doa_root_pipeline_set_spatial_smoothing: subarray size (0 = off), forward-backward
+    doa::DevBuf d_smooth;           // the smoothed items (S * S per item) between K1 and the eigen stage (max_batch items)
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     doa::DevBuf d_in[2], d_res;
     doa::DevBuf d_work[2];
     doa::PinnedBuf h_stage, h_status;
     int fail_chunk = -1;
-    enum { kCoef = 0, kCov, kStatus, kWork };
+    enum { kCoef = 0, kCov, kStatus, kWork, kSmooth };
     doa::PipeLanes lanes;
 };
 
@@ -36,7 +38,10 @@ struct RootWs {
     void *coef;       // double coefficient records of the chain's items
     void *status;     // one int per item (1 = no root strictly inside the unit circle), or the caller's buffer
     void *work;       // K1's piece sums (overlapping windows), or NULL
+    void *smooth;     // spatial smoothing on: S * S gr_complex per item (else unused)
 };
+// the array the eigen stage and the root finder see: the subarray of a smoothed handle
+int evd_elements(const doa_root_pipeline *h) { return h->S ? h->S : h->N; }
 size_t coef_bytes(const doa_root_pipeline *h, size_t items) { return items * doa::coef_stride(h->N) * sizeof(double); }
 
 // K1 -> EVD -> roots for n items on `st`
@@ -45,9 +50,15 @@ int run_chain(doa_root_pipeline *h, int n, const void *const *d_in, void *cov, v
     int rc = doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_in, cov, st, h->has_gain ? h->d_gain.p : nullptr, ws.work,
                                        h->format, h->scale);
     if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_evd(h->N, h->M, n, cov, nullptr, ws.coef, nullptr, h->bits, st);
+    if (h->S) {                                 // spatial smoothing: one launch; `cov` stays the N x N item
+        rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, n, cov, ws.smooth, st);
+        if (rc != DOA_OK) return rc;
+        cov = ws.smooth;
+    }
+    const int elements = evd_elements(h);
+    rc = doa::launch_music_evd(elements, h->M, n, cov, nullptr, ws.coef, nullptr, h->bits, st);
     if (rc != DOA_OK) return rc;
-    rc = doa::launch_root_music(h->N, h->M, h->norm_spacing, n, ws.coef, angles, ws.status, st);
+    rc = doa::launch_root_music(elements, h->M, h->norm_spacing, n, ws.coef, angles, ws.status, st);
     return rc == DOA_OK ? n : rc;
 }
 // first item whose status word is set, or -1
@@ -106,6 +117,7 @@ void doa_root_pipeline_destroy(doa_root_pipeline_t *h)
     if (!h) return;
     h->d_cov.release(); h->d_coef.release(); h->d_status.release(); h->d_gain.release(); h->d_res.release();
     h->h_stage.release(); h->h_status.release();
+    h->d_smooth.release();
     for (auto &b : h->d_work) b.release();
     for (auto &b : h->d_in) b.release();
     for (auto st : h->hst)
@@ -143,6 +155,27 @@ int doa_root_pipeline_set_input_format(doa_root_pipeline_t *h, int format, float
     return DOA_OK;
 }
 
+int doa_root_pipeline_set_spatial_smoothing(doa_root_pipeline_t *h, int subarray_size, int forward_backward)
+{
+    doa::clear_error();
+    if (!h) { doa::set_error("root_pipeline_set_spatial_smoothing: bad arguments"); return DOA_ERR_INVALID_ARG; }
+    const int S = subarray_size, fb = S ? forward_backward : 0;
+    if (S != 0 && (S < 2 || S > h->N || h->M >= S || (fb != 0 && fb != 1))) {
+        doa::set_error("root_pipeline_set_spatial_smoothing: need subarray_size 0 (off) or 2 <= subarray_size <= inputs with "
+                       "num_targets < subarray_size, forward_backward 0 or 1 (got %d, %d; inputs=%d num_targets=%d)", S,
+                       forward_backward, h->N, h->M);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (S == h->S && fb == h->fb) return DOA_OK;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    // work_dev / work_dev_auto and the host entry (whose chunks lie at their item offsets) share this one; the lanes of
+    // work_dev_batches have their own (kSmooth)
+    if (S)
+        if (int rc = h->d_smooth.reserve((size_t)h->max_batch * S * S * sizeof(float2)); rc != DOA_OK) return rc;
+    h->S = S; h->fb = fb;
+    return DOA_OK;
+}
+
 int doa_root_pipeline_work_dev(doa_root_pipeline_t *h, int noutput_items, const void *const *d_input_items, void *d_cov_out,
                                void *d_angles_out, int *d_status_out, void *hip_stream)
 {
@@ -157,9 +190,53 @@ int doa_root_pipeline_work_dev(doa_root_pipeline_t *h, int noutput_items, const 
     }
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    RootWs ws{h->d_coef.p, d_status_out ? (void *)d_status_out : h->d_status.p, h->d_work[0].p};
+    RootWs ws{h->d_coef.p, d_status_out ? (void *)d_status_out : h->d_status.p, h->d_work[0].p, h->d_smooth.p};
     return run_chain(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : h->d_cov.p, d_angles_out, ws,
                      static_cast<hipStream_t>(hip_stream));
+}
+
+// K1 as work_dev runs it, ONE eigen launch that estimates each item's count and writes its record for the noise set that
+// count gives, the counted root kernel: three launches, four on a smoothed handle
+int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int noutput_items, const void *const *d_input_items, int method,
+                                    void *d_cov_out, void *d_angles_out, void *d_count_out, void *d_eig_out, int *d_status_out,
+                                    void *hip_stream)
+{
+    doa::clear_error();
+    if (!h || noutput_items < 0 || !d_input_items || (method != DOA_SOURCE_COUNT_MDL && method != DOA_SOURCE_COUNT_AIC) ||
+        (noutput_items > 0 && (!d_angles_out || !d_count_out))) {
+        doa::set_error("root_pipeline_work_dev_auto: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (noutput_items > h->max_batch) {
+        doa::set_error("root_pipeline_work_dev_auto: noutput_items=%d exceeds max_batch=%d", noutput_items, h->max_batch);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("root_pipeline_work_dev_auto: per-item counts need internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (h->K < 2) {
+        doa::set_error("root_pipeline_work_dev_auto: the criterion needs snapshot_size >= 2 (handle has %d)", h->K);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int n = noutput_items;
+    const int elements = evd_elements(h);
+    void *cov = d_cov_out ? d_cov_out : h->d_cov.p;
+    int rc = doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_input_items, cov, st, h->has_gain ? h->d_gain.p : nullptr,
+                                       h->d_work[0].p, h->format, h->scale);
+    if (rc == DOA_OK && h->S) {
+        rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, n, cov, h->d_smooth.p, st);
+        cov = h->d_smooth.p;
+    }
+    if (rc == DOA_OK)
+        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, h->d_coef.p, nullptr, st);
+    if (rc == DOA_OK)
+        rc = doa::launch_root_music_counts(elements, h->M, h->norm_spacing, n, h->d_coef.p, d_count_out, d_angles_out,
+                                           d_status_out ? (void *)d_status_out : h->d_status.p, st);
+    return rc == DOA_OK ? n : rc;
 }
 
 int doa_root_pipeline_set_lanes(doa_root_pipeline_t *h, int n_lanes)
@@ -223,7 +300,8 @@ int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, in
                 (void)hipStreamSynchronize(caller);
                 return DOA_ERR_HIP;
             }
-            RootWs ws{h->d_coef.p, (d_status_out && d_status_out[b]) ? (void *)d_status_out[b] : h->d_status.p, h->d_work[0].p};
+            RootWs ws{h->d_coef.p, (d_status_out && d_status_out[b]) ? (void *)d_status_out[b] : h->d_status.p, h->d_work[0].p,
+                      h->d_smooth.p};
             const int rc = run_chain(h, noutput_items, d_input_items + (size_t)b * N,
                                      (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : h->d_cov.p, d_angles_out[b], ws, caller);
             if (rc < 0) { (void)hipStreamSynchronize(caller); return rc; }
@@ -242,11 +320,12 @@ int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, in
         if (rc == DOA_OK && need_cov) rc = ln.buf[H::kCov].reserve((size_t)h->max_batch * N * N * sizeof(float2));
         if (rc == DOA_OK && need_status) rc = ln.buf[H::kStatus].reserve((size_t)h->max_batch * sizeof(int));
         if (rc == DOA_OK && work_bytes) rc = ln.buf[H::kWork].reserve(work_bytes);
+        if (rc == DOA_OK && h->S) rc = ln.buf[H::kSmooth].reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
         return rc;
     };
     auto launch = [&](int b, doa::PipeLane &ln) -> int {
         RootWs ws{ln.buf[H::kCoef].p, (d_status_out && d_status_out[b]) ? (void *)d_status_out[b] : ln.buf[H::kStatus].p,
-                  ln.buf[H::kWork].p};
+                  ln.buf[H::kWork].p, ln.buf[H::kSmooth].p};
         return run_chain(h, noutput_items, d_input_items + (size_t)b * N,
                          (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : ln.buf[H::kCov].p, d_angles_out[b], ws, ln.st);
     };
@@ -306,7 +385,7 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
                 DOA_HIP_TRY(hipMemcpyAsync(h->d_in[0].p, hs, in_bytes, hipMemcpyHostToDevice, st));
                 char *dr = h->d_res.as<char>();
                 if (h->fail_chunk == 0) { doa::set_error("root_pipeline_work: injected failure"); return DOA_ERR_HIP; }
-                RootWs ws{h->d_coef.p, dr + off_st, h->d_work[0].p};
+                RootWs ws{h->d_coef.p, dr + off_st, h->d_work[0].p, h->d_smooth.p};
                 const int rr = run_chain(h, noutput_items, d_ptrs, cov_out ? (void *)(dr + off_cov) : h->d_cov.p, dr, ws, st);
                 if (rr < 0) return rr;
                 DOA_HIP_TRY(hipMemcpyAsync(hs, dr, out_bytes, hipMemcpyDeviceToHost, st));
@@ -349,7 +428,9 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
         }
         if (h->fail_chunk == chunk_index) { doa::set_error("root_pipeline_work: injected failure in chunk %d", chunk_index); return DOA_ERR_HIP; }
         float2 *cov = h->d_cov.as<float2>() + s0 * N * N;
-        RootWs ws{static_cast<char *>(h->d_coef.p) + coef_bytes(h, s0), d_st + s0, h->d_work[lane].p};
+        // (the two copy/compute lanes write disjoint item ranges of the handle's records and smoothed items)
+        RootWs ws{static_cast<char *>(h->d_coef.p) + coef_bytes(h, s0), d_st + s0, h->d_work[lane].p,
+                  h->S ? (void *)(h->d_smooth.as<float2>() + s0 * h->S * h->S) : nullptr};
         const int rr = run_chain(h, (int)n, d_ptrs, cov, d_ang + s0 * M, ws, st);
         if (rr < 0) return rr;
         if (cov_out)

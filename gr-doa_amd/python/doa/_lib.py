@@ -165,6 +165,11 @@ SIGNATURES = {
     "doa_spatial_smooth_work": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "doa_spatial_smooth_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_music_pipeline_set_spatial_smoothing": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "doa_rootMUSIC_linear_array_work_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_rootMUSIC_linear_array_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_rootMUSIC_linear_array_select_counts_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_root_pipeline_work_dev_auto": (C.c_int, [_vp, C.c_int, _vpp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "doa_root_pipeline_set_spatial_smoothing": (C.c_int, [_vp, C.c_int, C.c_int]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_root_pipeline_inject_failure": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_lanes_idle": (C.c_int, [_vp]),

@@ -479,6 +479,26 @@ class rootMUSIC_linear_array(_Block):
         return check(lib.doa_rootMUSIC_linear_array_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
                                                              C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
 
+    def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
+        """work with a source count PER ITEM (int32 array) in place of num_targets: items stay num_targets floats wide, the
+        first count slots are rootMUSIC_linear_array(norm_spacing, count, inputs)'s and the rest NaN; count 0 gives an all-NaN
+        item, and so does a count outside 0..min(num_targets, inputs-1) (source_count's -1 status included).  Raises
+        DoaError(DOA_ERR_NUMERIC) only for an item with a usable count and no root inside the unit circle
+        (doa_rootMUSIC_linear_array_work_counts)."""
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        c = np.ascontiguousarray(counts, dtype=_I32)
+        out = output_items[0]
+        assert a.size >= n * self.num_ant_ele ** 2 and c.size >= n
+        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.num_targets
+        return check(lib.doa_rootMUSIC_linear_array_work_counts(self._h, n, _vp(a), _vp(c), _vp(out)))
+
+    def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
+        """The device form; d_status_ptr (optional): one int32 per item, 0 = fine, 1 = no root inside the unit circle,
+        2 = no usable count."""
+        return check(lib.doa_rootMUSIC_linear_array_work_dev_counts(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
+                                                                    _opt_ptr(d_counts_ptr), C.c_void_p(int(d_out_ptr)),
+                                                                    _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
     def debug(self, R_items: np.ndarray):
         """(angles [n, M] float32, roots [n, 2N-2] complex128, status [n] int32) for parity tests."""
@@ -498,6 +518,18 @@ class rootMUSIC_linear_array(_Block):
         ang = np.empty((n, self.num_targets), dtype=_F32)
         status = np.empty(n, dtype=np.int32)
         check(lib.doa_rootMUSIC_linear_array_select_debug(self._h, n, _vp(z), _vp(ang), _vp(status)))
+        return ang, status
+
+    def select_counts_debug(self, roots: np.ndarray, counts):
+        """select_debug with a count per item (int32 [n]) -> (angles [n, M] float32, status [n] int32; 1 = no interior root,
+        2 = no usable count): the selection stage of work_counts."""
+        z = np.ascontiguousarray(roots, dtype=np.complex128).reshape(-1, 2 * self.num_ant_ele - 2)
+        n = z.shape[0]
+        c = np.ascontiguousarray(counts, dtype=_I32)
+        assert c.size >= n
+        ang = np.empty((n, self.num_targets), dtype=_F32)
+        status = np.empty(n, dtype=np.int32)
+        check(lib.doa_rootMUSIC_linear_array_select_counts_debug(self._h, n, _vp(z), _vp(c), _vp(ang), _vp(status)))
         return ang, status
 
 
@@ -691,6 +723,7 @@ class root_pipeline(_StreamInput, _Block):
         self.num_targets, self.max_batch = int(num_targets), int(max_batch)
         self._h = check_handle(lib.doa_root_pipeline_create(self.inputs, self.snapshot_size, self.overlap_size, self.avg_method,
                                                             self.norm_spacing, self.num_targets, self.max_batch), "root_pipeline")
+        self.subarray_size, self.forward_backward = 0, 0            # set_spatial_smoothing
         # as a flowgraph block (gr::doa::root_music_pipeline of the C++ shells): N complex streams in; out0 = angles
         self.in_sig = [(_C64, 1)] * self.inputs
         self.out_sig = [(_F32, self.num_targets)]
@@ -717,6 +750,15 @@ class root_pipeline(_StreamInput, _Block):
     def fuse_antenna_correction(self, correction) -> None:
         _fuse(lib.doa_root_pipeline_fuse_antenna_correction, self._h, correction, self.inputs)
 
+    def set_spatial_smoothing(self, subarray_size, forward_backward=True) -> None:
+        """Spatial smoothing between K1 and the eigen stage (coherent sources), from the next work call on, in every entry:
+        eigen stage and root finder then run for subarray_size elements (num_targets < subarray_size <= inputs; choose
+        subarray_size >= num_targets + 2); the covariance output stays inputs x inputs; work_dev_auto's eigenvalues are
+        subarray_size per item.  0 switches it off (doa_root_pipeline_set_spatial_smoothing)."""
+        check(lib.doa_root_pipeline_set_spatial_smoothing(self._h, int(subarray_size), int(forward_backward)))
+        self.subarray_size = int(subarray_size)
+        self.forward_backward = int(forward_backward) if self.subarray_size else 0
+
     def inject_failure(self, chunk_index: int) -> None:
         """Test aid: the next work() / work_dev_batches() call fails in chunk / batch `chunk_index` (one-shot; -1 disarms)."""
         check(lib.doa_root_pipeline_inject_failure(self._h, int(chunk_index)))
@@ -728,6 +770,16 @@ class root_pipeline(_StreamInput, _Block):
         return check(lib.doa_root_pipeline_work_dev(
             self._h, int(noutput_items), ptr_array(d_input_ptrs), C.c_void_p(int(d_cov_ptr or 0)), C.c_void_p(int(d_angles_ptr)),
             C.c_void_p(int(d_status_ptr or 0)), _stream_ptr(stream)))
+
+    def work_dev_auto(self, noutput_items, d_input_ptrs, d_angles_ptr, d_count_ptr, method="mdl", d_cov_ptr=None, d_eig_ptr=None,
+                      d_status_ptr=None, stream=None) -> int:
+        """work_dev with the source count estimated per snapshot (K = snapshot_size, at most num_targets sources): the angles
+        stay num_targets wide, the first count slots filled and the rest NaN; counts (int32, required) and the eigenvalues
+        (optional) come out of the same eigen launch; status 2 marks an item without a usable count
+        (doa_root_pipeline_work_dev_auto)."""
+        return check(lib.doa_root_pipeline_work_dev_auto(
+            self._h, int(noutput_items), ptr_array(d_input_ptrs), _count_method(method), _opt_ptr(d_cov_ptr), _opt_ptr(d_angles_ptr),
+            _opt_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
     def set_lanes(self, n_lanes: int) -> None:
         check(lib.doa_root_pipeline_set_lanes(self._h, int(n_lanes)))

@@ -480,6 +480,25 @@ DOA_HIP_API int doa_spatial_smooth_work_dev(doa_spatial_smooth_t *h, int noutput
  *   work_dev_auto: K in the criterion stays snapshot_size, and d_eig_out is subarray_size floats per item. */
 DOA_HIP_API int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarray_size, int forward_backward);
 
+/* rootMUSIC_linear_array with a count per item: counts = one int32 m_i per item, used in place of the handle's num_targets
+ * W.  Items stay W floats wide.  With top = min(W, num_ant_ele - 1):
+ *   1 <= m_i <= top   the first m_i slots are what rootMUSIC_linear_array(norm_spacing, m_i, num_ant_ele) writes for the
+ *                     item's record (selection rule, 90 degrees once the interior roots run out, ascending, NaN last), the
+ *                     slots m_i .. W-1 are NaN; status 0, or 1 (all W slots NaN) when no root lies strictly inside the circle
+ *   m_i == 0          all W slots NaN, status 0 (the root finder does not run on the item)
+ *   any other value   (the -1 of source_count included) all W slots NaN, status 2 = "no usable count"; other items are not
+ *                     affected
+ * The eigen stage is the forced-count launch of doa_MUSIC_lin_array_work_dev_counts (always the double Jacobi route, so a
+ * uniform count agrees with doa_rootMUSIC_linear_array_work to the parity bounds, not bit for bit).  d_status_out (one int
+ * per item) may be NULL.  The host entry returns DOA_ERR_NUMERIC only when some item has status 1 (the angles of the other
+ * items are valid); status 2 items are the caller's own counts and no error.  A handle at internal precision 32:
+ * DOA_ERR_UNSUPPORTED.  NULL counts: DOA_ERR_INVALID_ARG. */
+DOA_HIP_API int doa_rootMUSIC_linear_array_work_counts(doa_rootMUSIC_linear_array_t *h, int noutput_items,
+                                                       const void *cov_items, const void *counts, void *angles_out);
+DOA_HIP_API int doa_rootMUSIC_linear_array_work_dev_counts(doa_rootMUSIC_linear_array_t *h, int noutput_items,
+                                                           const void *d_cov_items, const void *d_counts,
+                                                           void *d_angles_out, int *d_status_out, void *hip_stream);
+
 /* ---------------------------------------------------------------------------------------------
  * root_pipeline — autocorrelate -> rootMUSIC_linear_array on device-resident streams: the Root-MUSIC branch of the hot
  *   path as one handle (the chain apps/run_RootMUSIC_lin_array_simulation.grc wires; reference work being chained:
@@ -522,6 +541,31 @@ DOA_HIP_API int doa_root_pipeline_set_input_format(doa_root_pipeline_t *h, int f
  * the other items are valid, that item's are NaN). */
 DOA_HIP_API int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items,
                                        const void *const *input_items, void *cov_out, void *angles_out);
+/* root_pipeline with the count estimated per snapshot: K1 exactly as doa_root_pipeline_work_dev runs it (fused gains, sc16
+ * input and overlap honoured; the covariance is bit-identical), then ONE eigen launch that also estimates the count (K =
+ * snapshot_size, max_sources = the handle's num_targets, `method` DOA_SOURCE_COUNT_MDL or _AIC) and writes each item's
+ * record for the noise set that count gives, then the counted root kernel: three launches (four on a smoothed handle),
+ * asynchronous on hip_stream.  d_count_out (int32 per item) is required; d_cov_out, d_eig_out (num_ant_ele floats per item)
+ * and d_status_out may be NULL.  d_angles_out stays num_targets floats per item, filled as
+ * doa_rootMUSIC_linear_array_work_dev_counts fills it: count 0: all NaN, status 0; count -1: all NaN, status 2.  The outputs
+ * are bit-identical to the chain source_count -> rootMUSIC_linear_array_work_dev_counts on the covariance written.  One
+ * batch of at most max_batch items; internal precision 32: DOA_ERR_UNSUPPORTED. */
+DOA_HIP_API int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int noutput_items,
+                                                const void *const *d_input_items, int method, void *d_cov_out,
+                                                void *d_angles_out, void *d_count_out, void *d_eig_out,
+                                                int *d_status_out, void *hip_stream);
+/* root_pipeline with spatial smoothing between K1 and the eigen stage; the contract of
+ * doa_music_pipeline_set_spatial_smoothing: a per-handle setting, taking effect from the next work call, honoured by
+ * work_dev, work_dev_batches, work and work_dev_auto.  subarray_size == 0 switches it off (the default).  Otherwise
+ * 2 <= subarray_size <= inputs, num_targets < subarray_size, forward_backward 0 or 1; a bad call returns
+ * DOA_ERR_INVALID_ARG and leaves the handle as it was.  When it is on, K1 runs exactly as before and d_cov_out stays the
+ * inputs x inputs covariance, bit-identical to an unsmoothed handle's; ONE more launch writes the smoothed items to a
+ * workspace (one per lane), and eigen stage and root finder run for subarray_size elements: the outputs are those of the
+ * chain autocorrelate -> spatial_smooth(inputs, subarray_size, forward_backward) -> rootMUSIC_linear_array(norm_spacing,
+ * num_targets, subarray_size), bit for bit.  work_dev_auto: K in the criterion stays snapshot_size, and d_eig_out is
+ * subarray_size floats per item.  Choose subarray_size >= num_targets + 2 (with one noise vector the
+ * smoothed polynomial's roots lie ON the unit circle). */
+DOA_HIP_API int doa_root_pipeline_set_spatial_smoothing(doa_root_pipeline_t *h, int subarray_size, int forward_backward);
 
 /* ---------------------------------------------------------------------------------------------
  * compass_mean — blocks.vector_to_streams(float, num_streams) + the averaging of doa.compass

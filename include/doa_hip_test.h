@@ -41,6 +41,14 @@ DOA_HIP_API int doa_rootMUSIC_linear_array_select_debug(doa_rootMUSIC_linear_arr
                                                         const void *roots_in, void *output_items0,
                                                         int *status_out);
 
+/* The counted selection stage on caller-supplied roots, the counterpart of select_debug for
+ * doa_rootMUSIC_linear_array_work_counts: counts = one int32 per item (host memory), output items num_targets floats wide,
+ * status_out (may be NULL) 0 / 1 / 2 as that entry defines them.  An item with count m is bit-identical to the select_debug
+ * row of a num_targets = m handle on the same roots; the roots of an item with count 0 or no usable count are not read. */
+DOA_HIP_API int doa_rootMUSIC_linear_array_select_counts_debug(doa_rootMUSIC_linear_array_t *h, int noutput_items,
+                                                               const void *roots_in, const void *counts,
+                                                               void *output_items0, int *status_out);
+
 /* Profiling aid: which stages later work_dev calls on this handle launch (bit 0 = K1 covariance, bit 1 = K2+K3
  * EVD, bit 2 = K4+K5 scan + peak pick; default 7).  A dropped stage leaves its outputs as the previous call
  * wrote them, so a profiler can time one kernel on valid intermediates; not for production use. */
