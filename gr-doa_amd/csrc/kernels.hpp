@@ -96,6 +96,25 @@ int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, v
 int launch_spatial_smooth(int N, int S, int fb, int n_items, const void *d_R, void *d_Rs, hipStream_t st);
 inline bool music_uses_cheb(int N, int bits) { return N <= 4 && bits == 64; }
 constexpr int kChebRecord = 8;      // doubles per item
+// Q(psi) = u0 + 2 sum_l (x_l cos(l psi) - y_l sin(l psi)), u_l = x_l + j y_l, in powers of c = cos psi and s = sin psi
+// (cos 2x = 2c^2 - 1, cos 3x = 4c^3 - 3c, sin 2x = 2sc, sin 3x = s(4c^2 - 1)):  Q = A(c) + s B(c),
+// A = (u0 - 2x2) + (2x1 - 6x3) c + 4x2 c^2 + 8x3 c^3,  B = (2y3 - 2y1) - 4y2 c - 8y3 c^2   (music_scan_impl.hpp: ChebQ)
+// ux[l], uy[l]: u_l for l = 0..3 (zero beyond the array size)
+__device__ __forceinline__ void write_cheb_record(double *__restrict__ o, const double (&ux)[4], const double (&uy)[4])
+{
+    o[0] = ux[0] - 2 * ux[2]; o[1] = 2 * ux[1] - 6 * ux[3]; o[2] = 4 * ux[2]; o[3] = 8 * ux[3];
+    o[4] = 2 * uy[3] - 2 * uy[1]; o[5] = -4 * uy[2]; o[6] = -8 * uy[3]; o[7] = 0.0;
+}
+// Capon (capon.hip; definition in include/doa_hip.h): the records of W = (H / mu + loading I)^-1 per item, in place of the
+// eigen stage's -- u_l = sum_r W[r+l, r] in the double coefficient record (d_coef_d, required) and, for N <= 4, the
+// Chebyshev record (d_cheb, required there).  d_w_out (optional, diagnostics): W as N x N float2, column-major.  d_status
+// (optional): int32 per item, 0 ok / 1 not positive definite enough or non-finite; such an item's records (and W) are NaN.
+int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, void *d_coef_d, void *d_cheb, void *d_w_out,
+                         void *d_status, hipStream_t st);
+// after scan and peak pick of a Capon call: for items with status != 0 the spectrum row (P floats; d_spec may be NULL) and the
+// M peak values / locations (d_max / d_argmax may be NULL) become NaN (the scan kernels write 0.0 dB for a NaN record)
+int launch_capon_invalid_rows(int P, int M, int n_items, const void *d_status, void *d_spec, void *d_max, void *d_argmax,
+                              hipStream_t st);
 // diagnostics: items that left the signal-subspace fast path of K2+K3 for the Jacobi fall-back since the last reset
 long long evd_fallback_count(bool reset);
 // the calling thread's current device's counter (allocated on first use; nullptr if that fails) and, for the tests, the device

@@ -22,16 +22,6 @@ namespace doa {
 #include "evd_subspace.hpp"
 namespace doa {
 
-// Q(psi) = u0 + 2 sum_l (x_l cos(l psi) - y_l sin(l psi)), u_l = x_l + j y_l, in powers of c = cos psi and s = sin psi
-// (cos 2x = 2c^2 - 1, cos 3x = 4c^3 - 3c, sin 2x = 2sc, sin 3x = s(4c^2 - 1)):  Q = A(c) + s B(c),
-// A = (u0 - 2x2) + (2x1 - 6x3) c + 4x2 c^2 + 8x3 c^3,  B = (2y3 - 2y1) - 4y2 c - 8y3 c^2   (music_scan_impl.hpp: ChebQ)
-// ux[l], uy[l]: u_l for l = 0..3 (zero beyond the array size)
-__device__ __forceinline__ void write_cheb_record(double *__restrict__ o, const double (&ux)[4], const double (&uy)[4])
-{
-    o[0] = ux[0] - 2 * ux[2]; o[1] = 2 * ux[1] - 6 * ux[3]; o[2] = 4 * ux[2]; o[3] = 8 * ux[3];
-    o[4] = 2 * uy[3] - 2 * uy[1]; o[5] = -4 * uy[2]; o[6] = -8 * uy[3]; o[7] = 0.0;
-}
-
 // Where item g's covariance matrix lives: one array (EvdOne), or the arrays of a group of batches (EvdGroup: kernels.hpp,
 // BatchGroup; item g = batch * n + local).  With n not a multiple of 64 the lanes of a wave sit in different batches, so the
 // batch's pointer is picked per lane: a chain of selects over the table's entries (compile-time indices -- a per-lane

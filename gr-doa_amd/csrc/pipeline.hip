@@ -9,6 +9,7 @@
 #include "kernels.hpp"
 #include "pipeline_lanes.hpp"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -35,6 +36,9 @@ struct doa_music_pipeline {
     float scale = 1.0f;
     int S = 0, fb = 0;              // doa_music_pipeline_set_spatial_smoothing: subarray size (0 = off), forward-backward
     doa::DevBuf d_smooth;           // the smoothed items (S * S per item) between K1 and the eigen stage
+    int estimator = DOA_ESTIMATOR_MUSIC;    // doa_music_pipeline_set_estimator
+    double loading = 0.0;           // Capon: the diagonal loading
+    doa::DevBuf d_status;           // Capon: int32 per item between the inverse launch and the NaN follow-up
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     doa::DevBuf d_in[2], d_res;
@@ -42,7 +46,7 @@ struct doa_music_pipeline {
     doa::PinnedBuf h_stage;         // scheduler-sized calls: one page-locked staging buffer, one copy each way
     int fail_chunk = -1;            // doa_music_pipeline_inject_failure, host-pointer entry: one-shot, cleared by every call (tests)
     // doa_music_pipeline_work_dev_batches: the library's own overlap lanes (pipeline_lanes.hpp); a lane's buffers:
-    enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch, kSmooth };
+    enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch, kSmooth, kStatus };
     doa::PipeLanes lanes;
 };
 
@@ -53,6 +57,7 @@ struct PipeWs {
     void *spec_scratch;     // P floats per item, used when the caller does not want the spectrum
     void *work;             // K1's piece sums (overlapping windows), or NULL
     void *smooth;           // spatial smoothing on: S * S gr_complex per item (else unused)
+    void *status;           // Capon: int32 per item (else unused)
     doa::DevBuf *scratch;   // grown on demand: the serial peak pick of unusual vector lengths
     size_t scratch_item_off;
 };
@@ -81,22 +86,36 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
         if (rc != DOA_OK) return rc;
         cov = ws.smooth;
     }
-    if (!(skip & 2))
-        rc = doa::launch_music_evd(evd_elements(h), h->music.M, n, cov, dbl ? nullptr : coef, dbl ? coef : nullptr, nullptr, h->bits, st, ws.cheb);
+    const bool capon = (h->estimator == DOA_ESTIMATOR_CAPON);
+    if (capon && !dbl) {
+        doa::set_error("music_pipeline: the Capon estimator needs internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (!(skip & 2)) {
+        if (capon)
+            rc = doa::launch_capon_inverse(evd_elements(h), n, cov, h->loading, coef, ws.cheb, nullptr, ws.status, st);
+        else
+            rc = doa::launch_music_evd(evd_elements(h), h->music.M, n, cov, dbl ? nullptr : coef, dbl ? coef : nullptr, nullptr, h->bits, st, ws.cheb);
+    }
     if (rc != DOA_OK) return rc;
     bool peaks_done = false;
     if (skip & 4) return n;
     rc = doa::launch_music_scan(h->music, h->bits, n, coef, spec, nullptr, st, &h->peaks, mx, am, &peaks_done, store_spec, ws.cheb);
     if (rc != DOA_OK) return rc;
-    if (peaks_done) return n;
-    if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
-        rc = doa::launch_find_local_max(h->peaks, n, spec, mx, am, st);
-    } else {
-        rc = ws.scratch->reserve((size_t)h->max_batch * h->peaks.L);
-        if (rc == DOA_OK)
-            rc = doa::launch_find_local_max_serial(h->peaks, n, spec, mx, am,
-                                                   static_cast<char *>(ws.scratch->p) + ws.scratch_item_off * h->peaks.L, st);
+    if (!peaks_done) {
+        if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
+            rc = doa::launch_find_local_max(h->peaks, n, spec, mx, am, st);
+        } else {
+            rc = ws.scratch->reserve((size_t)h->max_batch * h->peaks.L);
+            if (rc == DOA_OK)
+                rc = doa::launch_find_local_max_serial(h->peaks, n, spec, mx, am,
+                                                       static_cast<char *>(ws.scratch->p) + ws.scratch_item_off * h->peaks.L, st);
+        }
     }
+    // Capon: the scan wrote 0.0 dB rows (and the peak pick their peaks) for the NaN records of status-1 items (with the
+    // inverse launch dropped by set_stages there is no status of this call to act on)
+    if (rc == DOA_OK && capon && !(skip & 2))
+        rc = doa::launch_capon_invalid_rows(h->peaks.L, h->peaks.M, n, ws.status, store_spec ? spec : nullptr, mx, am, st);
     return rc == DOA_OK ? n : rc;
 }
 static int run_ws(doa_music_pipeline *h, int n, const void *const *d_in, void *cov, void *spec, void *mx, void *am,
@@ -118,6 +137,7 @@ static int run_dev(doa_music_pipeline *h, int n, const void *const *d_in, void *
     ws.spec_scratch = static_cast<char *>(h->d_spec.p) + item_off * h->peaks.L * sizeof(float);
     ws.work = h->d_work[lane].p;
     ws.smooth = h->S ? h->d_smooth.as<float2>() + item_off * h->S * h->S : nullptr;
+    ws.status = h->d_status.p ? h->d_status.as<int>() + item_off : nullptr;
     ws.scratch = &h->d_scratch;
     ws.scratch_item_off = item_off;
     return run_ws(h, n, d_in, cov, spec, mx, am, ws, st);
@@ -170,7 +190,7 @@ void doa_music_pipeline_destroy(doa_music_pipeline_t *h)
     h->music.release();
     h->peaks.release();
     h->d_cov.release(); h->d_coef.release(); h->d_cheb.release(); h->d_spec.release(); h->d_scratch.release(); h->d_gain.release();
-    h->d_smooth.release();
+    h->d_smooth.release(); h->d_status.release();
     h->d_res.release(); h->h_stage.release();
     for (auto &b : h->d_work) b.release();
     for (auto &b : h->d_in) b.release();
@@ -241,6 +261,27 @@ int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarr
     return DOA_OK;
 }
 
+int doa_music_pipeline_set_estimator(doa_music_pipeline_t *h, int estimator, float diagonal_loading)
+{
+    doa::clear_error();
+    if (!h) { doa::set_error("music_pipeline_set_estimator: bad arguments"); return DOA_ERR_INVALID_ARG; }
+    if (estimator != DOA_ESTIMATOR_MUSIC && estimator != DOA_ESTIMATOR_CAPON) {
+        doa::set_error("music_pipeline_set_estimator: unknown estimator %d (DOA_ESTIMATOR_MUSIC or DOA_ESTIMATOR_CAPON)", estimator);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (estimator == DOA_ESTIMATOR_CAPON) {
+        if (!std::isfinite(diagonal_loading) || diagonal_loading < 0.0f) {
+            doa::set_error("music_pipeline_set_estimator: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
+            return DOA_ERR_INVALID_ARG;
+        }
+        if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+        if (int rc = h->d_status.reserve((size_t)h->max_batch * sizeof(int)); rc != DOA_OK) return rc;
+        h->loading = (double)diagonal_loading;
+    }
+    h->estimator = estimator;
+    return DOA_OK;
+}
+
 int doa_music_pipeline_work_dev(doa_music_pipeline_t *h, int noutput_items, const void *const *d_input_items,
                                 void *d_cov_out, void *d_spectrum_out, void *d_max_out, void *d_argmax_out,
                                 void *hip_stream)
@@ -281,6 +322,10 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     }
     if (h->bits != 64) {
         doa::set_error("music_pipeline_work_dev_auto: per-item counts need internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (h->estimator != DOA_ESTIMATOR_MUSIC) {
+        doa::set_error("music_pipeline_work_dev_auto: the source count needs eigenvalues, which the Capon estimator does not form");
         return DOA_ERR_UNSUPPORTED;
     }
     if (h->K < 2) {
@@ -409,7 +454,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     const bool dbl = (h->bits == 64);
 
     // ---- the plan: groups of consecutive batches and their lanes ----
-    const bool lean_shape = h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
+    const bool lean_shape = h->estimator == DOA_ESTIMATOR_MUSIC && h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
                             (long long)doa::kMaxGroup * n <= (1 << 28);
     const int L_all = solo ? 1 : h->lanes.n_lanes;
     const int L = (lean_shape && group_lanes() < L_all) ? group_lanes() : L_all;
@@ -487,9 +532,10 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     using H = doa_music_pipeline;
     // a lane's buffers hold a whole group: records and covariances are 64-128 B per item; the angles-only scratch rows are bounded (G_angles)
     auto reserve = [&](doa::DevBuf &coef, doa::DevBuf &cheb, doa::DevBuf &cov, doa::DevBuf &spec, doa::DevBuf &work,
-                       doa::DevBuf &smooth) -> int {
+                       doa::DevBuf &smooth, doa::DevBuf &status) -> int {
         int rc = coef.reserve((size_t)h->max_batch * doa::coef_stride(N) * (dbl ? sizeof(double) : sizeof(float)));
         if (rc == DOA_OK && h->S) rc = smooth.reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
+        if (rc == DOA_OK && h->estimator == DOA_ESTIMATOR_CAPON) rc = status.reserve((size_t)h->max_batch * sizeof(int));
         if (rc == DOA_OK && doa::music_uses_cheb(evd_elements(h), h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
         if (rc == DOA_OK && need_cov) rc = cov.reserve((size_t)G * h->max_batch * N * N * sizeof(float2));
         if (rc == DOA_OK && need_spec) rc = spec.reserve((size_t)G_angles * h->max_batch * P * sizeof(float));
@@ -524,11 +570,11 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     };
     if (solo) {
         hipStream_t caller = static_cast<hipStream_t>(hip_stream);
-        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0], h->d_smooth);
+        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0], h->d_smooth, h->d_status);
         if (rc != DOA_OK) return rc;
         PipeWs ws;
         ws.coef = h->d_coef.p; ws.cheb = h->d_cheb.p; ws.spec_scratch = h->d_spec.p; ws.work = h->d_work[0].p;
-        ws.smooth = h->d_smooth.p;
+        ws.smooth = h->d_smooth.p; ws.status = h->d_status.p;
         ws.scratch = &h->d_scratch; ws.scratch_item_off = 0;
         for (size_t u = 0; u < plan.size() && rc >= 0; u++) rc = launch(plan[u], ws, h->d_cov.p, caller);
         if (rc >= 0 && injected) {
@@ -544,7 +590,8 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         return n_batches * n;
     }
     auto prepare = [&](doa::PipeLane &ln) -> int {
-        return reserve(ln.buf[H::kCoef], ln.buf[H::kCheb], ln.buf[H::kCov], ln.buf[H::kSpec], ln.buf[H::kWork], ln.buf[H::kSmooth]);
+        return reserve(ln.buf[H::kCoef], ln.buf[H::kCheb], ln.buf[H::kCov], ln.buf[H::kSpec], ln.buf[H::kWork], ln.buf[H::kSmooth],
+                       ln.buf[H::kStatus]);
     };
     auto launch_unit = [&](int u, doa::PipeLane &ln) -> int {
         const PlanGroup &g = plan[u];
@@ -552,7 +599,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
             if (const int rc = h->lanes.synchronize(); rc != DOA_OK) return rc;
         PipeWs ws;
         ws.coef = ln.buf[H::kCoef].p; ws.cheb = ln.buf[H::kCheb].p; ws.spec_scratch = ln.buf[H::kSpec].p; ws.work = ln.buf[H::kWork].p;
-        ws.smooth = ln.buf[H::kSmooth].p;
+        ws.smooth = ln.buf[H::kSmooth].p; ws.status = ln.buf[H::kStatus].p;
         ws.scratch = &ln.buf[H::kScratch]; ws.scratch_item_off = 0;
         return launch(g, ws, ln.buf[H::kCov].p, ln.st);
     };

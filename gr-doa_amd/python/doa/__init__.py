@@ -15,6 +15,10 @@ spatial smoothing of the covariance items for coherent sources (also `music_pipe
 
     blk = doa.spatial_smooth(num_ant_ele, subarray_size, forward_backward=True)
 
+the Capon (MVDR) spectrum, which needs no source count and no eigendecomposition (also `music_pipeline.set_estimator("capon")`):
+
+    blk = doa.capon_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0)
+
 and the calibration chain that produces the files phase_correct_hier and antenna_correction read
 (python/twinrx_phase_offset_est.py, findmax_and_save.py, average_and_save.py, save_antenna_calib.py):
 
@@ -25,7 +29,7 @@ Importing fails if gr-doa_amd/lib/libdoa_hip.so has not been built; constructing
 no HIP device is usable.  There is no CPU fallback.
 """
 from ._lib import DoaError, LIB_PATH, last_error  # noqa: F401
-from .blocks import (autocorrelate, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, rootMUSIC_linear_array,  # noqa: F401
+from .blocks import (autocorrelate, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, rootMUSIC_linear_array,  # noqa: F401
                      music_pipeline, root_pipeline, root_music_pipeline, autocorrelate_sc16, music_pipeline_sc16,
                      root_music_pipeline_sc16, compass_mean, sim_source, set_internal_precision, get_internal_precision, device_count,
                      evd_fallback_count, DETACHED,

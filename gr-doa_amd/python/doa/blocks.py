@@ -44,6 +44,9 @@ def _count_method(method) -> int:
 def _opt_ptr(p) -> C.c_void_p:
     return C.c_void_p(0 if p is None else int(p))
 
+# estimators of music_pipeline (DOA_ESTIMATOR_MUSIC / DOA_ESTIMATOR_CAPON, include/doa_hip.h)
+_ESTIMATORS = {"music": 0, "capon": 1}
+
 # input sample formats of the stream-input blocks (DOA_SAMPLE_FC32 / DOA_SAMPLE_SC16, include/doa_hip.h)
 SC16_DEFAULT_SCALE = 2.0 ** -15
 _FORMATS = {"fc32": 0, "sc16": 1}
@@ -452,6 +455,55 @@ class spatial_smooth(_Block):
                                                      C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
 
 
+class capon_lin_array(_Block):
+    """doa.capon_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0) — the Capon (minimum-variance, MVDR)
+    spectrum 1 / (a^H R^-1 a) of each covariance item on MUSIC_lin_array's angle grid, in its output format (dB against the
+    row maximum): no source count, no eigendecomposition, a run time that does not depend on the data (definition:
+    include/doa_hip.h).  diagonal_loading is relative to the mean diagonal entry; fewer snapshots than antennas need it > 0.
+    Port 0: the spectrum; port 1 (optional): int32 status, 1 = not positive definite enough (that item's row is NaN).
+    Not a block of the reference."""
+
+    _destroy = staticmethod(lib.doa_capon_lin_array_destroy)
+
+    def __init__(self, norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0):
+        super().__init__()
+        self.norm_spacing, self.num_ant_ele = float(norm_spacing), int(inputs)
+        self.pspectrum_len, self.diagonal_loading = int(pspectrum_len), float(diagonal_loading)
+        self._h = check_handle(lib.doa_capon_lin_array_create(self.norm_spacing, self.num_ant_ele, self.pspectrum_len,
+                                                              self.diagonal_loading), "capon_lin_array")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_F32, self.pspectrum_len), (_I32, 1)]
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        """output_items = [spectrum float32 [n, P]] or [spectrum, status int32 [n]]."""
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        out = output_items[0]
+        status = output_items[1] if len(output_items) > 1 else None
+        assert a.size >= n * self.num_ant_ele ** 2
+        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
+        if status is not None:
+            assert status.dtype == _I32 and status.flags.c_contiguous and status.size >= n
+        return check(lib.doa_capon_lin_array_work(self._h, n, _vp(a), _vp(out),
+                                                  _vp(status) if status is not None else C.c_void_p(0)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
+        return check(lib.doa_capon_lin_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+                                                      _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+    def debug(self, R_items: np.ndarray):
+        """(W [n, N*N] complex64 column-major items, Q [n, P] float32) for the tests."""
+        a = np.ascontiguousarray(R_items, dtype=_C64).reshape(-1, self.num_ant_ele ** 2)
+        n = a.shape[0]
+        w = np.empty((n, self.num_ant_ele ** 2), dtype=_C64)
+        q = np.empty((n, self.pspectrum_len), dtype=_F32)
+        check(lib.doa_capon_lin_array_debug(self._h, n, _vp(a), _vp(w), _vp(q)))
+        return w, q
+
+    def nout_items_total(self) -> int:
+        return int(lib.doa_capon_lin_array_items_total(self._h))
+
+
 class rootMUSIC_linear_array(_Block):
     """doa.rootMUSIC_linear_array(norm_spacing, num_targets, inputs) — gr::sync_block
     (reference lib/rootMUSIC_linear_array_impl.cc:46-59)."""
@@ -577,6 +629,7 @@ class music_pipeline(_StreamInput, _Block):
         self.avg_method, self.norm_spacing = int(avg_method), float(norm_spacing)
         self.num_targets, self.pspectrum_len, self.max_batch = int(num_targets), int(pspectrum_len), int(max_batch)
         self.subarray_size, self.forward_backward = 0, 0            # set_spatial_smoothing
+        self.estimator, self.diagonal_loading = "music", 0.0        # set_estimator
         self._h = check_handle(lib.doa_music_pipeline_create(self.inputs, self.snapshot_size, self.overlap_size,
                                                              self.avg_method, self.norm_spacing, self.num_targets,
                                                              self.pspectrum_len, self.max_batch), "music_pipeline")
@@ -615,6 +668,17 @@ class music_pipeline(_StreamInput, _Block):
         check(lib.doa_music_pipeline_set_spatial_smoothing(self._h, int(subarray_size), int(forward_backward)))
         self.subarray_size = int(subarray_size)
         self.forward_backward = int(forward_backward) if self.subarray_size else 0
+
+    def set_estimator(self, estimator, diagonal_loading=0.0) -> None:
+        """ "music" (the default) or "capon": from the next work call on, the eigen launch is replaced by the Capon inverse
+        launch (capon_lin_array's; diagonal_loading as there) and num_targets only means "how many peaks"; an item that is
+        not positive definite enough gets NaN peaks and a NaN row.  work_dev_auto is not available in Capon mode
+        (doa_music_pipeline_set_estimator)."""
+        if not isinstance(estimator, str) or estimator.lower() not in _ESTIMATORS:
+            raise ValueError(f"unknown estimator {estimator!r} (music or capon)")
+        check(lib.doa_music_pipeline_set_estimator(self._h, _ESTIMATORS[estimator.lower()], float(diagonal_loading)))
+        self.estimator = estimator.lower()
+        self.diagonal_loading = float(diagonal_loading) if self.estimator == "capon" else 0.0
 
     def set_stages(self, cov=True, evd=True, scan=True) -> None:
         """Profiling aid: drop stages from later work_dev calls (their outputs keep the previous call's values)."""

@@ -480,6 +480,60 @@ DOA_HIP_API int doa_spatial_smooth_work_dev(doa_spatial_smooth_t *h, int noutput
  *   work_dev_auto: K in the criterion stays snapshot_size, and d_eig_out is subarray_size floats per item. */
 DOA_HIP_API int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarray_size, int forward_backward);
 
+/* ---------------------------------------------------------------------------------------------
+ * capon_lin_array — the Capon (minimum-variance, MVDR) spectrum of a uniform linear array,
+ *       P(theta) = 1 / (a(theta)^H R^-1 a(theta)),
+ *   on the angle grid and in the output format of MUSIC_lin_array (pspectrum_len floats, dB against the row maximum).  It
+ *   needs no source count and no eigendecomposition: one Cholesky factorisation and one triangular inverse per item, no
+ *   iteration, so its time does not depend on the data.  The companion to MUSIC when the number of sources is uncertain.
+ *   Not a block of the reference.
+ * The definition, one for every entry (tests/capon_ref.py restates it in numpy):
+ *   input item   column-major N x N gr_complex (N = num_ant_ele), as MUSIC_lin_array and spatial_smooth take it; ONLY THE
+ *                UPPER TRIANGLE IS READ, and of the diagonal the real part: H = the Hermitian matrix these define.  All
+ *                arithmetic is in double.
+ *     mu  = (sum_i H[i,i]) / N
+ *     A   = H / mu + delta I              delta = (double) diagonal_loading  (float argument, >= 0)
+ *     W   = A^-1                          via Cholesky A = L L^H, W = L^-H L^-1
+ *     u_l = sum_r W[r+l, r]               l = 0 .. N-1: the coefficient record of the scan kernels (csrc/kernels.hpp)
+ *     Q_i = u_0 + 2 Re sum_l u_l z_i^l = a_i^H W a_i;  out = 1 / Q;  spectrum = 10 log10(out / max out)
+ *   (the kernel multiplies by 1 / mu formed once, within one double rounding of the quotient; the normalisation by the row
+ *   maximum cancels the scale of W, and an item multiplied by a power of two gives the same bits.)
+ *   status per item (int32): 0 ok; 1 = "not positive definite enough":
+ *     mu > 0 does not hold (a zero item; a negative trace, for which H / mu would change sign), or
+ *     some Cholesky pivot s_j = A[j,j] - sum_{k<j} |L[j,k]|^2 fails s_j > DOA_CAPON_PIVOT_MIN * A[j,j], or
+ *     any quantity is not finite (NaN / Inf entries).
+ *   At the threshold 2^-44 the double result no longer carries float accuracy.  A status-1 item gets an all-NaN spectrum
+ *   row (and all-NaN peaks where peaks are produced); the other items of the call are not affected.
+ *   diagonal_loading: with fewer snapshots than antennas the sample covariance is singular and delta > 0 is required;
+ *   delta is relative to the mean diagonal entry.
+ * Internal precision 64 only: a handle created while the process default is 32 returns DOA_ERR_UNSUPPORTED from its work
+ * entries.  create validates before the device is touched: 2 <= num_ant_ele <= DOA_MAX_ANT_ELE, 0 < norm_spacing <= 0.5,
+ * pspectrum_len > 0, diagonal_loading finite and >= 0.  status_out / d_status_out (one int32 per item) may be NULL.
+ * --------------------------------------------------------------------------------------------- */
+#define DOA_CAPON_PIVOT_MIN (1.0 / 17592186044416.0)   /* 2^-44, exact */
+typedef struct doa_capon_lin_array doa_capon_lin_array_t;
+
+DOA_HIP_API doa_capon_lin_array_t *doa_capon_lin_array_create(float norm_spacing, int num_ant_ele, int pspectrum_len,
+                                                              float diagonal_loading);
+DOA_HIP_API void doa_capon_lin_array_destroy(doa_capon_lin_array_t *h);
+DOA_HIP_API int doa_capon_lin_array_work(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items,
+                                         void *spectrum_out, void *status_out);
+DOA_HIP_API int doa_capon_lin_array_work_dev(doa_capon_lin_array_t *h, int noutput_items, const void *d_cov_items,
+                                             void *d_spectrum_out, void *d_status_out, void *hip_stream);
+DOA_HIP_API long long doa_capon_lin_array_items_total(const doa_capon_lin_array_t *h);
+/* music_pipeline with the Capon spectrum in place of the MUSIC one: a per-handle setting, taking effect from the next work
+ * call.  DOA_ESTIMATOR_MUSIC (the default) is the path described above, unchanged.  DOA_ESTIMATOR_CAPON: the eigen launch
+ * is replaced by the inverse launch above (diagonal_loading as in doa_capon_lin_array_create; ignored for MUSIC), on the
+ * subarray_size x subarray_size items when spatial smoothing is on; scan and peak pick run as before, so num_targets only
+ * means "how many peaks", and one small launch after them turns the spectrum row and the peaks of status-1 items into NaN.
+ * The outputs are bit-identical to the chain autocorrelate -> capon_lin_array -> find_local_max.  In Capon mode
+ * work_dev_batches runs one chain of launches per batch (no grouped launches), work_dev_auto returns DOA_ERR_UNSUPPORTED
+ * (it needs eigenvalues), and so does every work entry of a handle at internal precision 32.  A bad call returns
+ * DOA_ERR_INVALID_ARG and leaves the handle as it was. */
+#define DOA_ESTIMATOR_MUSIC 0
+#define DOA_ESTIMATOR_CAPON 1
+DOA_HIP_API int doa_music_pipeline_set_estimator(doa_music_pipeline_t *h, int estimator, float diagonal_loading);
+
 /* rootMUSIC_linear_array with a count per item: counts = one int32 m_i per item, used in place of the handle's num_targets
  * W.  Items stay W floats wide.  With top = min(W, num_ant_ele - 1):
  *   1 <= m_i <= top   the first m_i slots are what rootMUSIC_linear_array(norm_spacing, m_i, num_ant_ele) writes for the

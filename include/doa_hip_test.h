@@ -49,6 +49,12 @@ DOA_HIP_API int doa_rootMUSIC_linear_array_select_counts_debug(doa_rootMUSIC_lin
                                                                const void *roots_in, const void *counts,
                                                                void *output_items0, int *status_out);
 
+/* Diagnostics of capon_lin_array (host buffers, synchronous): the inverse W of each item (inverse_out: column-major
+ * num_ant_ele^2 gr_complex; NaN for a status-1 item) and the un-normalised null spectrum Q_i = a_i^H W a_i
+ * (null_spectrum_out: pspectrum_len floats per item).  Either output pointer may be NULL. */
+DOA_HIP_API int doa_capon_lin_array_debug(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items,
+                                          void *inverse_out, void *null_spectrum_out);
+
 /* Profiling aid: which stages later work_dev calls on this handle launch (bit 0 = K1 covariance, bit 1 = K2+K3
  * EVD, bit 2 = K4+K5 scan + peak pick; default 7).  A dropped stage leaves its outputs as the previous call
  * wrote them, so a profiler can time one kernel on valid intermediates; not for production use. */
