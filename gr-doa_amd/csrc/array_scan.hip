@@ -1,0 +1,539 @@
+// array_scan.hip — spectra for an ARBITRARY array geometry on gfx950: the steering-table scan kernel, the host-built table,
+// doa_planar_steering_table and the C ABI of doa_MUSIC_array / doa_capon_array.  Not blocks of the reference; the definition
+// is stated once in include/doa_hip.h.
+//
+// The ULA scans (music_scan_impl.hpp) never see a matrix, only its 2N-1 diagonal sums, which summarise a^H X a only for
+// a_n = z^n.  Here the stage in front (the Jacobi forms of the eigen stage, the Capon inverse) writes the FULL RECORD of its
+// Hermitian matrix X (kernels.hpp: N^2 doubles, X packed into a real square) and the handle carries a table T[k][i] built
+// once from the steering rows, so that
+//     Q_i = Re(a_i^H X a_i) = sum_k record[k] T[k][i]                       (k over N^2 real components, i over P directions):
+// a batch is an [items x N^2] . [N^2 x P] real product, then a reciprocal, a maximum and a logarithm per row.
+//
+// Structure: "wave over angles".  A workgroup of 256 threads owns IT items and every direction: thread t takes the
+// directions t + 256 m.  The table row k is loaded coalesced, once per thread, and used for all IT items; the records are
+// workgroup-uniform, so record[k] travels through scalar loads and reaches the FMA as a scalar operand.  q = (float) Q is
+// parked in LDS (IT rows of P floats) until the row minimum is known; the second pass turns the row into dB with the
+// normalisation of the ULA scans (LeanNorm / db_from_ratio) and writes it to memory ONCE.  The sum over k runs in index
+// order for every direction of every item, whatever IT, the batch size or the item's neighbours are.
+//   P <= 1024   8 items per workgroup, 2 directions per thread and step     (32 KiB of LDS)
+//   P <= 4096   4 items, 4 directions                                        (64 KiB)
+//   P <= 16384  1 item, 4 directions                                         (64 KiB)
+//   longer      4 items, 4 directions, no row in LDS: the second pass forms Q again (the same sum, the same bits)
+// The matrix instruction v_mfma_f64_16x16x4_f64 (items as M, directions as N) was the alternative: it needs the records
+// transposed into its operand layout and pays for 16 items per tile whatever the batch; at N = 4 the kernel is bound by
+// the store of the spectrum either way, so the plain form came first.
+#include "kernels.hpp"
+#include "music_scan_impl.hpp"
+
+#include <cmath>
+#include <vector>
+
+namespace doa {
+namespace {
+
+constexpr int kScanThreads = 256;
+
+template <int IT, int A, int PMAX>
+__global__ __launch_bounds__(kScanThreads) void array_scan_kernel(const double *__restrict__ full, const double *__restrict__ tab,
+                                                                  float *__restrict__ spec, float *__restrict__ qout, int P, int NN,
+                                                                  int n_items)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "array_scan_kernel keeps up to 64 KiB of rows plus its reduction slots in LDS: gfx950 (MI355X) only"
+#endif
+    constexpr bool ROWS = PMAX > 0;
+    __shared__ float rows[ROWS ? IT * PMAX : 1];           // item it, direction p at [it * P + p]
+    __shared__ float red[2][kScanThreads / kWave][IT];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wib = tid / kWave;
+    const int item0 = blockIdx.x * IT;
+    const double *x[IT];
+#pragma unroll
+    for (int it = 0; it < IT; it++) x[it] = full + (size_t)min(item0 + it, n_items - 1) * NN;   // idle slots shadow the last item
+    // Q at one direction: the sum in index order (the second pass of the row-less form)
+    auto q_at = [&](int it, int p) -> float {
+        double acc = 0.0;
+        for (int k = 0; k < NN; k++) acc = fma(x[it][k], tab[(size_t)k * P + p], acc);
+        return (float)acc;
+    };
+    float mn[IT];
+#pragma unroll
+    for (int it = 0; it < IT; it++) mn[it] = INFINITY;
+    // pass 1: Q, its float image into the LDS row, the row minimum
+    for (int p0 = 0; p0 < P; p0 += kScanThreads * A) {
+        int pa[A];
+#pragma unroll
+        for (int a = 0; a < A; a++) pa[a] = min(p0 + a * kScanThreads + tid, P - 1);      // clamped: every load is in the table
+        double acc[IT][A];
+#pragma unroll
+        for (int it = 0; it < IT; it++)
+#pragma unroll
+            for (int a = 0; a < A; a++) acc[it][a] = 0.0;
+        const double *trow = tab;
+#pragma unroll 2
+        for (int k = 0; k < NN; k++, trow += P) {
+            double t[A];
+#pragma unroll
+            for (int a = 0; a < A; a++) t[a] = trow[pa[a]];
+#pragma unroll
+            for (int it = 0; it < IT; it++) {
+                const double xv = x[it][k];
+#pragma unroll
+                for (int a = 0; a < A; a++) acc[it][a] = fma(xv, t[a], acc[it][a]);
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < A; a++) {
+            const int p = p0 + a * kScanThreads + tid;
+            if (p < P) {
+#pragma unroll
+                for (int it = 0; it < IT; it++) {
+                    const float q = (float)acc[it][a];
+                    mn[it] = fminf(mn[it], q);
+                    if constexpr (ROWS) rows[it * P + p] = q;
+                    if (qout && item0 + it < n_items) qout[(size_t)(item0 + it) * P + p] = q;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        const float m = wave_allreduce_min(mn[it]);
+        if (lane == 0) red[0][wib][it] = m;
+    }
+    __syncthreads();                                        // the rows and the wave minima are in LDS
+    // pass 2: dB, one write of the row.  Every branch below is workgroup-uniform (mn, the item index).
+#pragma unroll
+    for (int it = 0; it < IT; it++) {
+        if (item0 + it >= n_items) break;
+        const float m = fminf(fminf(red[0][0][it], red[0][1][it]), fminf(red[0][2][it], red[0][3][it]));
+        float *grow = spec + (size_t)(item0 + it) * P;
+        auto q_of = [&](int p) -> float {
+            if constexpr (ROWS) return rows[it * P + p];
+            else return q_at(it, p);
+        };
+        if (lean_norm_ok(m)) {
+            const LeanNorm nrm(m);
+            for (int p = tid; p < P; p += kScanThreads) {
+                bool tie;
+                __builtin_nontemporal_store(nrm.db(q_of(p), tie), grow + p);
+            }
+        } else {
+            // rows whose minimum of Q is not a positive normal number: the general semantics (db_from_ratio)
+            float mx = -INFINITY;
+            for (int p = tid; p < P; p += kScanThreads) mx = fmaxf(mx, 1.0f / q_of(p));
+            mx = wave_allreduce_max(mx);
+            if (lane == 0) red[1][wib][it] = mx;
+            __syncthreads();
+            mx = fmaxf(fmaxf(red[1][0][it], red[1][1][it]), fmaxf(red[1][2][it], red[1][3][it]));
+            const float inv_mx = __builtin_amdgcn_rcpf(mx);
+            for (int p = tid; p < P; p += kScanThreads)
+                __builtin_nontemporal_store(db_from_ratio(1.0f / q_of(p), mx, inv_mx), grow + p);
+        }
+    }
+}
+
+template <int IT, int A, int PMAX>
+void launch_array_scan_form(const ArrayTable &t, int n_items, const void *d_full, void *d_spec, void *d_q, hipStream_t st)
+{
+    hipLaunchKernelGGL((array_scan_kernel<IT, A, PMAX>), dim3((n_items + IT - 1) / IT), dim3(kScanThreads), 0, st,
+                       (const double *)d_full, t.d_t.as<double>(), (float *)d_spec, (float *)d_q, t.P, t.N * t.N, n_items);
+}
+
+}  // namespace
+
+bool steering_table_finite(const double *steering, int N, int P)
+{
+    if (!steering) return false;
+    const size_t n = 2 * (size_t)N * (size_t)P;
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(steering[i])) return false;
+    return true;
+}
+
+int ArrayTable::build(int num_ant_ele, int pspectrum_len, const double *steering)
+{
+    N = num_ant_ele; P = pspectrum_len;
+    const size_t NN = (size_t)N * N;
+    std::vector<double> T(NN * (size_t)P);
+    for (int i = 0; i < P; i++) {
+        const double *a = steering + 2 * (size_t)i * N;
+        for (int c = 0; c < N; c++) {
+            const double cr = a[2 * c], ci = a[2 * c + 1];
+            T[((size_t)c + (size_t)c * N) * P + i] = cr * cr + ci * ci;
+            for (int r = 0; r < c; r++) {
+                const double rr = a[2 * r], ri = a[2 * r + 1];
+                // w = conj(a_r) a_c:  conj(a_r) X[r][c] a_c + its conjugate = 2 (Re X Re w - Im X Im w)
+                const double wr = rr * cr + ri * ci, wi = rr * ci - ri * cr;
+                T[((size_t)r + (size_t)c * N) * P + i] = 2.0 * wr;
+                T[((size_t)c + (size_t)r * N) * P + i] = -2.0 * wi;
+            }
+        }
+    }
+    const size_t bytes = T.size() * sizeof(double);
+    if (int rc = d_t.reserve(bytes); rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpy(d_t.p, T.data(), bytes, hipMemcpyHostToDevice));
+    return DOA_OK;
+}
+
+int launch_array_scan(const ArrayTable &t, int n_items, const void *d_full, void *d_spec, void *d_q, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    if (t.N < 2 || t.N > DOA_MAX_ANT_ELE || t.P < 1 || !t.d_t.p || !d_full || !d_spec) {
+        set_error("array scan: bad arguments (N=%d, P=%d)", t.N, t.P);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (t.P <= 1024) launch_array_scan_form<8, 2, 1024>(t, n_items, d_full, d_spec, d_q, st);
+    else if (t.P <= 4096) launch_array_scan_form<4, 4, 4096>(t, n_items, d_full, d_spec, d_q, st);
+    else if (t.P <= 16384) launch_array_scan_form<1, 4, 16384>(t, n_items, d_full, d_spec, d_q, st);
+    else launch_array_scan_form<4, 4, 0>(t, n_items, d_full, d_spec, d_q, st);
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+}  // namespace doa
+
+// ---------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------
+struct doa_MUSIC_array {
+    doa::ArrayTable tab;
+    int M = 0;
+    int bits = 64;   // the process default at create; the work entries need 64
+    int device = 0;
+    long long items_total = 0;
+    hipStream_t stream = nullptr;
+    doa::DevBuf d_in, d_out, d_full, d_q;
+};
+
+struct doa_capon_array {
+    doa::ArrayTable tab;
+    double loading = 0.0;
+    int bits = 64;
+    int device = 0;
+    long long items_total = 0;
+    hipStream_t stream = nullptr;
+    doa::DevBuf d_in, d_out, d_full, d_q, d_status;
+};
+
+namespace {
+
+int array_validate(const char *who, int num_ant_ele, int pspectrum_len, const double *steering)
+{
+    if (num_ant_ele < 2 || num_ant_ele > DOA_MAX_ANT_ELE) {
+        doa::set_error("%s: need 2 <= num_ant_ele <= %d (got %d)", who, DOA_MAX_ANT_ELE, num_ant_ele);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (pspectrum_len < 1) {
+        doa::set_error("%s: pspectrum_len must be > 0 (got %d)", who, pspectrum_len);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (!steering) {
+        doa::set_error("%s: the steering table is NULL", who);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (!doa::steering_table_finite(steering, num_ant_ele, pspectrum_len)) {
+        doa::set_error("%s: the steering table holds a value that is not finite", who);
+        return DOA_ERR_INVALID_ARG;
+    }
+    return DOA_OK;
+}
+
+template <class H> int array_work_args(const char *who, H *h, int n, const void *in, const void *out)
+{
+    if (!h || n < 0 || (n > 0 && (!in || !out))) {
+        doa::set_error("%s: bad arguments", who);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("%s: the steering-table scan needs internal precision 64 (handle is at %d)", who, h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    return DOA_OK;
+}
+
+int capon_array_reserve(doa_capon_array *h, int n)
+{
+    return h->d_full.reserve((size_t)n * doa::full_record_len(h->tab.N) * sizeof(double));
+}
+
+// full records (host) -> N x N complex128, column-major
+void unpack_full_records(const std::vector<double> &rec, int N, int n, double *out)
+{
+    const size_t NN = (size_t)N * N;
+    for (int it = 0; it < n; it++) {
+        const double *f = rec.data() + (size_t)it * NN;
+        double *o = out + 2 * (size_t)it * NN;
+        for (int c = 0; c < N; c++) {
+            o[2 * (c + c * N)] = f[c + c * N]; o[2 * (c + c * N) + 1] = 0.0;
+            for (int r = 0; r < c; r++) {
+                const double re = f[r + c * N], im = f[c + r * N];
+                o[2 * (r + c * N)] = re; o[2 * (r + c * N) + 1] = im;
+                o[2 * (c + r * N)] = re; o[2 * (c + r * N) + 1] = -im;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int doa_planar_steering_table(int num_ant_ele, const double *xy, int pspectrum_len, double az_min_deg, double az_max_deg,
+                              double elevation_deg, double *table_out)
+{
+    doa::clear_error();
+    if (num_ant_ele < 2 || num_ant_ele > DOA_MAX_ANT_ELE || pspectrum_len < 1 || !xy || !table_out) {
+        doa::set_error("planar_steering_table: need 2 <= num_ant_ele <= %d, pspectrum_len > 0 and non-NULL pointers (got %d, %d)",
+                       DOA_MAX_ANT_ELE, num_ant_ele, pspectrum_len);
+        return DOA_ERR_INVALID_ARG;
+    }
+    bool finite = std::isfinite(az_min_deg) && std::isfinite(az_max_deg) && std::isfinite(elevation_deg);
+    for (int k = 0; k < 2 * num_ant_ele; k++) finite = finite && std::isfinite(xy[k]);
+    if (!finite) {
+        doa::set_error("planar_steering_table: positions, azimuth limits and elevation must be finite");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (!(az_max_deg > az_min_deg)) {
+        doa::set_error("planar_steering_table: need az_max > az_min (got %g, %g)", az_min_deg, az_max_deg);
+        return DOA_ERR_INVALID_ARG;
+    }
+    const double se = std::sin(elevation_deg * M_PI / 180.0);
+    for (int i = 0; i < pspectrum_len; i++) {
+        const double az = (az_min_deg + (double)i * (az_max_deg - az_min_deg) / (double)pspectrum_len) * M_PI / 180.0;
+        const double ca = std::cos(az), sa = std::sin(az);
+        for (int n = 0; n < num_ant_ele; n++) {
+            const double ph = 2.0 * M_PI * se * (xy[2 * n] * ca + xy[2 * n + 1] * sa);
+            table_out[2 * ((size_t)i * num_ant_ele + n)] = std::cos(ph);
+            table_out[2 * ((size_t)i * num_ant_ele + n) + 1] = std::sin(ph);
+        }
+    }
+    return DOA_OK;
+}
+
+// ---- MUSIC_array --------------------------------------------------------------------------------------------------------
+doa_MUSIC_array_t *doa_MUSIC_array_create(int num_targets, int num_ant_ele, int pspectrum_len, const double *steering)
+{
+    doa::clear_error();
+    if (array_validate("MUSIC_array", num_ant_ele, pspectrum_len, steering) != DOA_OK) return nullptr;
+    if (num_targets < 1 || num_targets >= num_ant_ele) {
+        doa::set_error("MUSIC_array: need 0 < num_targets < num_ant_ele (got %d, %d)", num_targets, num_ant_ele);
+        return nullptr;
+    }
+    int dev = 0;
+    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
+    auto *h = new (std::nothrow) doa_MUSIC_array();
+    if (!h) { doa::set_error("out of memory"); return nullptr; }
+    h->device = dev;
+    h->M = num_targets;
+    h->bits = doa::internal_precision_bits();
+    if (h->tab.build(num_ant_ele, pspectrum_len, steering) != DOA_OK ||
+        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+        if (!*doa_last_error()) doa::set_error("MUSIC_array: device setup failed");
+        doa_MUSIC_array_destroy(h);
+        return nullptr;
+    }
+    return h;
+}
+
+void doa_MUSIC_array_destroy(doa_MUSIC_array_t *h)
+{
+    if (!h) return;
+    h->tab.release();
+    h->d_in.release(); h->d_out.release(); h->d_full.release(); h->d_q.release();
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+long long doa_MUSIC_array_items_total(const doa_MUSIC_array_t *h) { return h ? h->items_total : 0; }
+
+int doa_MUSIC_array_set_internal_precision(doa_MUSIC_array_t *h, int bits)
+{
+    doa::clear_error();
+    if (!h || (bits != 32 && bits != 64)) { doa::set_error("MUSIC_array_set_internal_precision: need a handle and bits = 32 or 64"); return DOA_ERR_INVALID_ARG; }
+    h->bits = bits;
+    return DOA_OK;
+}
+
+int doa_MUSIC_array_work_dev(doa_MUSIC_array_t *h, int noutput_items, const void *d_cov_items, void *d_spectrum_out, void *hip_stream)
+{
+    doa::clear_error();
+    if (int rc = array_work_args("MUSIC_array_work_dev", h, noutput_items, d_cov_items, d_spectrum_out); rc != DOA_OK) return rc;
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int N = h->tab.N, n = noutput_items;
+    int rc = h->d_full.reserve((size_t)n * doa::full_record_len(N) * sizeof(double));
+    if (rc == DOA_OK) rc = doa::launch_music_evd_full(N, h->M, n, d_cov_items, h->d_full.p, nullptr, st);
+    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, d_spectrum_out, nullptr, st);
+    if (rc != DOA_OK) return rc;
+    h->items_total += n;
+    return n;
+}
+
+int doa_MUSIC_array_work(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out)
+{
+    doa::clear_error();
+    if (int rc = array_work_args("MUSIC_array_work", h, noutput_items, cov_items, spectrum_out); rc != DOA_OK) return rc;
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const int N = h->tab.N, P = h->tab.P;
+    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
+    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
+    int rc = h->d_in.reserve(in_bytes);
+    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa_MUSIC_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
+    if (rc < 0) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(spectrum_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    return noutput_items;
+}
+
+int doa_MUSIC_array_debug(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *projector_out, void *null_spectrum_out)
+{
+    doa::clear_error();
+    if (!h || noutput_items <= 0 || !cov_items) {
+        doa::set_error("MUSIC_array_debug: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("MUSIC_array_debug: the steering-table scan needs internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const int N = h->tab.N, P = h->tab.P, n = noutput_items;
+    const size_t in_bytes = (size_t)n * N * N * sizeof(float2);
+    const size_t sp_bytes = (size_t)n * P * sizeof(float);
+    const size_t full_bytes = (size_t)n * doa::full_record_len(N) * sizeof(double);
+    int rc = h->d_in.reserve(in_bytes);
+    if (rc == DOA_OK) rc = h->d_out.reserve(sp_bytes);
+    if (rc == DOA_OK) rc = h->d_q.reserve(sp_bytes);
+    if (rc == DOA_OK) rc = h->d_full.reserve(full_bytes);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa::launch_music_evd_full(N, h->M, n, h->d_in.p, h->d_full.p, nullptr, h->stream);
+    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, h->d_out.p, h->d_q.p, h->stream);
+    if (rc != DOA_OK) return rc;
+    std::vector<double> rec(projector_out ? full_bytes / sizeof(double) : 0);
+    if (projector_out) DOA_HIP_TRY(hipMemcpyAsync(rec.data(), h->d_full.p, full_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (null_spectrum_out) DOA_HIP_TRY(hipMemcpyAsync(null_spectrum_out, h->d_q.p, sp_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    if (projector_out) unpack_full_records(rec, N, n, static_cast<double *>(projector_out));
+    return n;
+}
+
+// ---- capon_array --------------------------------------------------------------------------------------------------------
+doa_capon_array_t *doa_capon_array_create(int num_ant_ele, int pspectrum_len, const double *steering, float diagonal_loading)
+{
+    doa::clear_error();
+    if (array_validate("capon_array", num_ant_ele, pspectrum_len, steering) != DOA_OK) return nullptr;
+    if (!std::isfinite(diagonal_loading) || diagonal_loading < 0.0f) {
+        doa::set_error("capon_array: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
+        return nullptr;
+    }
+    int dev = 0;
+    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
+    auto *h = new (std::nothrow) doa_capon_array();
+    if (!h) { doa::set_error("out of memory"); return nullptr; }
+    h->device = dev;
+    h->loading = (double)diagonal_loading;
+    h->bits = doa::internal_precision_bits();
+    if (h->tab.build(num_ant_ele, pspectrum_len, steering) != DOA_OK ||
+        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+        if (!*doa_last_error()) doa::set_error("capon_array: device setup failed");
+        doa_capon_array_destroy(h);
+        return nullptr;
+    }
+    return h;
+}
+
+void doa_capon_array_destroy(doa_capon_array_t *h)
+{
+    if (!h) return;
+    h->tab.release();
+    h->d_in.release(); h->d_out.release(); h->d_full.release(); h->d_q.release(); h->d_status.release();
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+long long doa_capon_array_items_total(const doa_capon_array_t *h) { return h ? h->items_total : 0; }
+
+int doa_capon_array_work_dev(doa_capon_array_t *h, int noutput_items, const void *d_cov_items, void *d_spectrum_out,
+                             void *d_status_out, void *hip_stream)
+{
+    doa::clear_error();
+    if (int rc = array_work_args("capon_array_work_dev", h, noutput_items, d_cov_items, d_spectrum_out); rc != DOA_OK) return rc;
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int N = h->tab.N, n = noutput_items;
+    int rc = capon_array_reserve(h, n);
+    if (rc == DOA_OK && !d_status_out) rc = h->d_status.reserve((size_t)n * sizeof(int));
+    if (rc != DOA_OK) return rc;
+    void *status = d_status_out ? d_status_out : h->d_status.p;
+    rc = doa::launch_capon_inverse(N, n, d_cov_items, h->loading, nullptr, nullptr, nullptr, status, st, h->d_full.p);
+    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, d_spectrum_out, nullptr, st);
+    if (rc == DOA_OK) rc = doa::launch_capon_invalid_rows(h->tab.P, 0, n, status, d_spectrum_out, nullptr, nullptr, st);
+    if (rc != DOA_OK) return rc;
+    h->items_total += n;
+    return n;
+}
+
+int doa_capon_array_work(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out, void *status_out)
+{
+    doa::clear_error();
+    if (int rc = array_work_args("capon_array_work", h, noutput_items, cov_items, spectrum_out); rc != DOA_OK) return rc;
+    if (noutput_items == 0) return 0;
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const int N = h->tab.N, P = h->tab.P;
+    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
+    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
+    const size_t st_bytes = (size_t)noutput_items * sizeof(int);
+    int rc = h->d_in.reserve(in_bytes);
+    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
+    if (rc == DOA_OK) rc = h->d_status.reserve(st_bytes);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa_capon_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->d_status.p, h->stream);
+    if (rc < 0) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(spectrum_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (status_out) DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, st_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    return noutput_items;
+}
+
+int doa_capon_array_debug(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *inverse_out, void *null_spectrum_out)
+{
+    doa::clear_error();
+    if (!h || noutput_items <= 0 || !cov_items) {
+        doa::set_error("capon_array_debug: bad arguments");
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->bits != 64) {
+        doa::set_error("capon_array_debug: the steering-table scan needs internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    const int N = h->tab.N, P = h->tab.P, n = noutput_items;
+    const size_t in_bytes = (size_t)n * N * N * sizeof(float2);
+    const size_t sp_bytes = (size_t)n * P * sizeof(float);
+    const size_t full_bytes = (size_t)n * doa::full_record_len(N) * sizeof(double);
+    int rc = h->d_in.reserve(in_bytes);
+    if (rc == DOA_OK) rc = h->d_out.reserve(sp_bytes);
+    if (rc == DOA_OK) rc = h->d_q.reserve(sp_bytes);
+    if (rc == DOA_OK) rc = capon_array_reserve(h, n);
+    if (rc != DOA_OK) return rc;
+    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = doa::launch_capon_inverse(N, n, h->d_in.p, h->loading, nullptr, nullptr, nullptr, nullptr, h->stream, h->d_full.p);
+    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, h->d_out.p, h->d_q.p, h->stream);
+    if (rc != DOA_OK) return rc;
+    std::vector<double> rec(inverse_out ? full_bytes / sizeof(double) : 0);
+    if (inverse_out) DOA_HIP_TRY(hipMemcpyAsync(rec.data(), h->d_full.p, full_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (null_spectrum_out) DOA_HIP_TRY(hipMemcpyAsync(null_spectrum_out, h->d_q.p, sp_bytes, hipMemcpyDeviceToHost, h->stream));
+    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+    if (inverse_out) unpack_full_records(rec, N, n, static_cast<double *>(inverse_out));
+    return n;
+}
+
+}  // extern "C"

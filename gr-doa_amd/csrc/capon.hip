@@ -38,7 +38,8 @@ template <int G> __device__ __forceinline__ double group_sum_d(double v, int lan
 template <int N, bool WOUT>
 __global__ __launch_bounds__(64) void capon_inverse_lane_kernel(const float2 *__restrict__ R, double loading,
                                                                 double *__restrict__ coef_d, double *__restrict__ cheb_d,
-                                                                float2 *__restrict__ w_out, int *__restrict__ status, int n_items)
+                                                                float2 *__restrict__ w_out, int *__restrict__ status, int n_items,
+                                                                double *__restrict__ full_out)
 {
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= n_items) return;
@@ -125,14 +126,16 @@ __global__ __launch_bounds__(64) void capon_inverse_lane_kernel(const float2 *__
         for (int l = 0; l < 4; l++) { ux[l] = (l < N) ? (double)NAN : 0.0; uy[l] = (l < N && l > 0) ? (double)NAN : 0.0; }
     }
     if (status) status[item] = bad ? 1 : 0;
-    double *cd = coef_d + (size_t)item * (2 * N);
-    cd[0] = ux[0];
+    if (coef_d) {                                        // (NULL on a steering-table handle: its scan reads the full record)
+        double *cd = coef_d + (size_t)item * (2 * N);
+        cd[0] = ux[0];
 #pragma unroll
-    for (int l = 1; l < N; l++) { cd[2 * l - 1] = ux[l]; cd[2 * l] = uy[l]; }
-    cd[2 * N - 1] = 0.0;
+        for (int l = 1; l < N; l++) { cd[2 * l - 1] = ux[l]; cd[2 * l] = uy[l]; }
+        cd[2 * N - 1] = 0.0;
+    }
     if (cheb_d) write_cheb_record(cheb_d + (size_t)item * kChebRecord, ux, uy);
     if constexpr (WOUT) {
-        float2 *wo = w_out + (size_t)item * (N * N);
+        const size_t off = (size_t)item * (N * N);
 #pragma unroll
         for (int i = 0; i < N; i++) {
 #pragma unroll
@@ -144,8 +147,16 @@ __global__ __launch_bounds__(64) void capon_inverse_lane_kernel(const float2 *__
                     wi = fma(mr[k][i], mi[k][j], fma(-mi[k][i], mr[k][j], wi));
                 }
                 if (bad) { wr = (double)NAN; wi = (double)NAN; }
-                wo[i + j * N] = make_float2((float)wr, (float)((i == j) ? 0.0 : wi));
-                if (i != j) wo[j + i * N] = make_float2((float)wr, (float)-wi);
+                if (w_out) {
+                    float2 *wo = w_out + off;
+                    wo[i + j * N] = make_float2((float)wr, (float)((i == j) ? 0.0 : wi));
+                    if (i != j) wo[j + i * N] = make_float2((float)wr, (float)-wi);
+                }
+                if (full_out) {                        // the full record (kernels.hpp), before any rounding
+                    double *fo = full_out + off;
+                    fo[i + j * N] = wr;
+                    if (i != j) fo[j + i * N] = wi;
+                }
             }
         }
     }
@@ -160,7 +171,8 @@ __global__ __launch_bounds__(64) void capon_inverse_lane_kernel(const float2 *__
 template <int G, bool WOUT>
 __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *__restrict__ R, double loading,
                                                                  double *__restrict__ coef_d, float2 *__restrict__ w_out,
-                                                                 int *__restrict__ status, int n_items, int N)
+                                                                 int *__restrict__ status, int n_items, int N,
+                                                                 double *__restrict__ full_out)
 {
     constexpr int IPW = kWave / G;                       // items per wave
     const int lane = threadIdx.x & (kWave - 1);
@@ -264,17 +276,17 @@ __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *_
         bad = b != 0;
     }
     if (bad) { ur = (double)NAN; ui = (double)NAN; }
-    if (real_item && row) {
+    if (real_item && r == 0 && status) status[item] = bad ? 1 : 0;
+    if (real_item && row && coef_d) {                    // (NULL on a steering-table handle: its scan reads the full record)
         double *cd = coef_d + (size_t)item * (2 * N);
         if (r == 0) {
             cd[0] = ur; cd[2 * N - 1] = 0.0;
-            if (status) status[item] = bad ? 1 : 0;
         } else {
             cd[2 * r - 1] = ur; cd[2 * r] = ui;
         }
     }
     if constexpr (WOUT) {
-        float2 *wo = w_out + (size_t)item * (N * N);
+        const size_t off = (size_t)item * (N * N);
 #pragma unroll
         for (int i = 0; i < G; i++) {
 #pragma unroll
@@ -285,9 +297,16 @@ __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *_
                     wr = group_sum_d<G>(wr, lane);
                     wi = group_sum_d<G>(wi, lane);
                     if (bad) { wr = (double)NAN; wi = (double)NAN; }
-                    if (real_item && r == 0) {
+                    if (real_item && r == 0 && w_out) {
+                        float2 *wo = w_out + off;
                         wo[i + j * N] = make_float2((float)wr, (float)((i == j) ? 0.0 : wi));
                         if (i != j) wo[j + i * N] = make_float2((float)wr, (float)-wi);
+                    }
+                    // the full record (kernels.hpp), before any rounding: every lane holds the sums, lane j stores column j
+                    if (real_item && r == j && full_out) {
+                        double *fo = full_out + off;
+                        fo[i + j * N] = wr;
+                        if (i != j) fo[j + i * N] = wi;
                     }
                 }
             }
@@ -312,49 +331,51 @@ __global__ __launch_bounds__(256) void capon_invalid_rows_kernel(const int *__re
 }
 
 template <int N> void launch_capon_lane(int n_items, const void *d_R, double loading, void *d_coef_d, void *d_cheb, void *d_w_out,
-                                        void *d_status, hipStream_t st)
+                                        void *d_status, hipStream_t st, void *d_full)
 {
     const dim3 grid((n_items + 63) / 64), block(64);
-    if (d_w_out)
+    if (d_w_out || d_full)
         hipLaunchKernelGGL((capon_inverse_lane_kernel<N, true>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (double *)d_cheb, (float2 *)d_w_out, (int *)d_status, n_items);
+                           (double *)d_cheb, (float2 *)d_w_out, (int *)d_status, n_items, (double *)d_full);
     else
         hipLaunchKernelGGL((capon_inverse_lane_kernel<N, false>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (double *)d_cheb, (float2 *)nullptr, (int *)d_status, n_items);
+                           (double *)d_cheb, (float2 *)nullptr, (int *)d_status, n_items, (double *)nullptr);
 }
 
 template <int G> void launch_capon_group(int N, int n_items, const void *d_R, double loading, void *d_coef_d, void *d_w_out,
-                                         void *d_status, hipStream_t st)
+                                         void *d_status, hipStream_t st, void *d_full)
 {
     constexpr int IPW = kWave / G;
     const dim3 grid((n_items + IPW - 1) / IPW), block(64);
-    if (d_w_out)
+    if (d_w_out || d_full)
         hipLaunchKernelGGL((capon_inverse_group_kernel<G, true>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (float2 *)d_w_out, (int *)d_status, n_items, N);
+                           (float2 *)d_w_out, (int *)d_status, n_items, N, (double *)d_full);
     else
         hipLaunchKernelGGL((capon_inverse_group_kernel<G, false>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (float2 *)nullptr, (int *)d_status, n_items, N);
+                           (float2 *)nullptr, (int *)d_status, n_items, N, (double *)nullptr);
 }
 
 }  // namespace
 
 int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, void *d_coef_d, void *d_cheb, void *d_w_out,
-                         void *d_status, hipStream_t st)
+                         void *d_status, hipStream_t st, void *d_full)
 {
     if (n_items <= 0) return DOA_OK;
     if (N < 2 || N > DOA_MAX_ANT_ELE) {
         set_error("Capon: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
         return DOA_ERR_UNSUPPORTED;
     }
-    if (!d_R || !d_coef_d || (music_uses_cheb(N, 64) && !d_cheb) || !(loading >= 0.0) || !std::isfinite(loading)) {
+    // the diagonal-sum records are what the ULA scans read; a caller that asks for full records may leave them out
+    const bool need_records = !d_full;
+    if (!d_R || (need_records && (!d_coef_d || (music_uses_cheb(N, 64) && !d_cheb))) || !(loading >= 0.0) || !std::isfinite(loading)) {
         set_error("Capon: bad arguments of the inverse launch (N=%d, loading=%g)", N, loading);
         return DOA_ERR_INVALID_ARG;
     }
-    if (N > 8) launch_capon_group<16>(N, n_items, d_R, loading, d_coef_d, d_w_out, d_status, st);
-    else if (N > 4) launch_capon_group<8>(N, n_items, d_R, loading, d_coef_d, d_w_out, d_status, st);
-    else if (N == 4) launch_capon_lane<4>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st);
-    else if (N == 3) launch_capon_lane<3>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st);
-    else launch_capon_lane<2>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st);
+    if (N > 8) launch_capon_group<16>(N, n_items, d_R, loading, d_coef_d, d_w_out, d_status, st, d_full);
+    else if (N > 4) launch_capon_group<8>(N, n_items, d_R, loading, d_coef_d, d_w_out, d_status, st, d_full);
+    else if (N == 4) launch_capon_lane<4>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st, d_full);
+    else if (N == 3) launch_capon_lane<3>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st, d_full);
+    else launch_capon_lane<2>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st, d_full);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }

@@ -109,12 +109,39 @@ __device__ __forceinline__ void write_cheb_record(double *__restrict__ o, const 
 // eigen stage's -- u_l = sum_r W[r+l, r] in the double coefficient record (d_coef_d, required) and, for N <= 4, the
 // Chebyshev record (d_cheb, required there).  d_w_out (optional, diagnostics): W as N x N float2, column-major.  d_status
 // (optional): int32 per item, 0 ok / 1 not positive definite enough or non-finite; such an item's records (and W) are NaN.
+// d_full (optional): W as a full record for launch_array_scan (below), from the same double values as d_w_out; with it
+// d_coef_d and d_cheb may be NULL (the records of the ULA scans are then not written).
 int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, void *d_coef_d, void *d_cheb, void *d_w_out,
-                         void *d_status, hipStream_t st);
+                         void *d_status, hipStream_t st, void *d_full = nullptr);
 // after scan and peak pick of a Capon call: for items with status != 0 the spectrum row (P floats; d_spec may be NULL) and the
 // M peak values / locations (d_max / d_argmax may be NULL) become NaN (the scan kernels write 0.0 dB for a NaN record)
 int launch_capon_invalid_rows(int P, int M, int n_items, const void *d_status, void *d_spec, void *d_max, void *d_argmax,
                               hipStream_t st);
+// ---- arbitrary array geometry (array_scan.hip; definition in include/doa_hip.h) -------------------------------------------
+// FULL RECORD of a Hermitian N x N matrix X: N^2 doubles per item, X packed into a real square (column-major index
+// r + c N):   [r + r N] = X[r][r];   for r < c:  [r + c N] = Re X[r][c],  [c + r N] = Im X[r][c].
+// With the table T built from the steering rows in the same order (ArrayTable), a^H X a = sum_k record[k] T[k]: a real dot
+// product of length N^2.
+inline int full_record_len(int N) { return N * N; }
+// The eigen stage writing the full record of P_N (always the double Jacobi forms: 4 lanes per item for N <= 4, 8 lanes for
+// N <= 8, one wave for N <= 16; the subspace iterations never form P_N outside their diagnostics).  d_pn (optional): P_N as
+// float2, as launch_music_evd writes it.
+int launch_music_evd_full(int N, int M, int n_items, const void *d_R, void *d_full, void *d_pn, hipStream_t st);
+// The steering table of a handle in the scan's form: T[k][i], k over the full record's N^2 components, i over the P
+// directions (doubles, row k contiguous in i):  |a_r|^2 on the diagonal components, 2 Re(conj(a_r) a_c) against Re X[r][c]
+// and -2 Im(conj(a_r) a_c) against Im X[r][c].
+struct ArrayTable {
+    int N = 0, P = 0;
+    DevBuf d_t;   // N^2 x P doubles
+    // steering: HOST pointer, P rows of N complex doubles (a_i[n] at [2 (i N + n)], re then im)
+    int build(int num_ant_ele, int pspectrum_len, const double *steering);
+    void release() { d_t.release(); }
+};
+// validation shared by the create entries and doa_music_pipeline_set_steering_table: every entry finite
+bool steering_table_finite(const double *steering, int N, int P);
+// Q_i = sum_k record[k] T[k][i] in double, q = (float) Q, out = 1 / q, dB against the row maximum with the scan kernels' own
+// normalisation (music_scan_impl.hpp: LeanNorm / db_from_ratio).  d_q (optional): q, P floats per item.
+int launch_array_scan(const ArrayTable &t, int n_items, const void *d_full, void *d_spec, void *d_q, hipStream_t st);
 // diagnostics: items that left the signal-subspace fast path of K2+K3 for the Jacobi fall-back since the last reset
 long long evd_fallback_count(bool reset);
 // the calling thread's current device's counter (allocated on first use; nullptr if that fails) and, for the tests, the device

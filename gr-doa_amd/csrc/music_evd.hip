@@ -239,7 +239,7 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
                                                    double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                    const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
                                                    double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{},
-                                                   T inv_sc = (T)1, T poison = (T)0)
+                                                   T inv_sc = (T)1, T poison = (T)0, double *__restrict__ pn_d = nullptr)
 {
     // eigenvalue of lane r = A[r][r]; ascending rank inside the group; noise set = ranks < N-M
     int rank = 0;
@@ -314,8 +314,8 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
         const bool on = (sel >> i) & 1u;
         yr[i] = on ? vr[i] : (T)0; yi[i] = on ? vi[i] : (T)0;
     }
-    if (pn_out) {                                         // diagnostics: P_N[r][b] = sum_i Y[r][i] conj(V[b][i])
-        float2 *po = pn_out + (size_t)item * (N * N);
+    if (pn_out || pn_d) {                                 // diagnostics: P_N[r][b] = sum_i Y[r][i] conj(V[b][i])
+        const size_t off = (size_t)item * (N * N);
         for (int b = 0; b < N; b++) {
             T pr = 0, pi = 0;
 #pragma unroll
@@ -324,8 +324,13 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
                 pr = fma(yr[i], br, fma(yi[i], bi, pr));
                 pi = fma(yi[i], br, fma(-yr[i], bi, pi));
             }
-            if (real_item && r < N) po[r + b * N] = make_float2((float)pr, (float)pi);
+            if (pn_out && real_item && r < N) pn_out[off + r + b * N] = make_float2((float)pr, (float)pi);
+            if (pn_d && real_item && r <= b) {              // the full record (kernels.hpp), before any rounding
+                pn_d[off + r + b * N] = (double)pr;
+                if (r < b) pn_d[off + b + r * N] = (double)pi;
+            }
         }
+        if (pn_d && !coef && !coef_d) return;             // the table handles' launch: no diagonal sums
     }
     // u_l = sum_r P_N[r+l][r] = sum_r sum_i Y[r+l][i] conj(V[r][i]): fetch row r+l, dot with own row, reduce
     float *co = (coef && real_item) ? coef + (size_t)item * (2 * N) : nullptr;
@@ -387,7 +392,8 @@ template <int G, typename T, class Cnt = EvdFixedM>
 __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, int item, bool real_item, int N, int M,
                                                float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                               double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{});
+                                               double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{},
+                                               double *__restrict__ pn_d = nullptr);
 
 template <int G, typename T>
 __global__ __launch_bounds__(64) void music_evd_group_kernel(const float2 *__restrict__ R, float *__restrict__ coef,
@@ -407,7 +413,7 @@ template <int G, typename T, class Cnt>
 __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, int item, bool real_item, int N, int M,
                                                float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                               double *__restrict__ cheb_d, const Cnt &cnt)
+                                               double *__restrict__ cheb_d, const Cnt &cnt, double *__restrict__ pn_d)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int r = lane % G, base = lane - r;
@@ -472,7 +478,8 @@ __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, in
         evd_group_epilogue<G, T, Cnt>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out,
                                       cheb_d, cnt, (T)1 / sc, poison);
     else
-    evd_group_epilogue<G, T>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out, cheb_d);
+    evd_group_epilogue<G, T>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out, cheb_d,
+                             EvdFixedM{}, (T)1, (T)0, pn_d);
 }
 
 // the group Jacobi with a count per item (launch_music_evd_counts; double)
@@ -879,7 +886,7 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
                                                  double *__restrict__ coef_d, float2 *__restrict__ pn_out, int N, int M,
                                                  const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
                                                  T *__restrict__ sVr, T *__restrict__ sVi, T *__restrict__ sLam,
-                                                 const Cnt &cnt = Cnt{})
+                                                 const Cnt &cnt = Cnt{}, double *__restrict__ pn_d = nullptr)
 {
     constexpr int G = 16;
     const int lane = threadIdx.x & (kWave - 1);
@@ -1089,7 +1096,7 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
 #pragma unroll
         for (int k = 0; k < G; k++) { er[k] = sVr[lane * G + k]; ei[k] = sVi[lane * G + k]; }
         evd_group_epilogue<G, T>(er, ei, sLam[lane], !((pad >> lane) & 1u), lane, 0, lane, item, true, N, M, coef, coef_d,
-                                 pn_out, pilot, cal_out);
+                                 pn_out, pilot, cal_out, nullptr, EvdFixedM{}, (T)1, (T)0, pn_d);
     }
 }
 
@@ -1340,6 +1347,54 @@ int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_c
         default: launch_evd_counts_n<4>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
         }
     }
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+// The Jacobi forms writing P_N itself as a full record (kernels.hpp) for the steering-table scan: the row-per-lane epilogue
+// holds P_N in double where it writes the float2 diagnostics, and the record is stored from those values.  No diagonal sums.
+template <int G>
+__global__ __launch_bounds__(64) void music_evd_group_full_kernel(const float2 *__restrict__ R, double *__restrict__ full,
+                                                                  float2 *__restrict__ pn_out, int n_items, int N, int M)
+{
+    constexpr int IPW = kWave / G;                       // items per wave
+    const int lane = threadIdx.x & (kWave - 1);
+    int item = blockIdx.x * IPW + lane / G;
+    const bool real_item = item < n_items;
+    if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
+    evd_group_wave<G, double>(R + (size_t)item * (N * N), item, real_item, N, M, nullptr, nullptr, pn_out, nullptr, nullptr, nullptr,
+                              EvdFixedM{}, full);
+}
+
+__global__ __launch_bounds__(64) void music_evd_block16_full_kernel(const float2 *__restrict__ R, double *__restrict__ full,
+                                                                    float2 *__restrict__ pn_out, int n_items, int N, int M)
+{
+    __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
+    const int item = blockIdx.x;                         // grid = n_items
+    evd_block16_item<double, false>(R + (size_t)item * (N * N), item, nullptr, nullptr, pn_out, N, M, nullptr, nullptr, sVr, sVi, sLam,
+                                    EvdFixedM{}, full);
+}
+
+int launch_music_evd_full(int N, int M, int n_items, const void *d_R, void *d_full, void *d_pn, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    if (N < 2 || N > DOA_MAX_ANT_ELE) {
+        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (!d_R || !d_full || M < 1 || M >= N) {
+        set_error("MUSIC: bad arguments of the full-record eigen launch (N=%d, M=%d)", N, M);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (N > 8)
+        hipLaunchKernelGGL(music_evd_block16_full_kernel, dim3(n_items), dim3(64), 0, st, (const float2 *)d_R, (double *)d_full,
+                           (float2 *)d_pn, n_items, N, M);
+    else if (N > 4)
+        hipLaunchKernelGGL((music_evd_group_full_kernel<8>), dim3((n_items + 7) / 8), dim3(64), 0, st, (const float2 *)d_R,
+                           (double *)d_full, (float2 *)d_pn, n_items, N, M);
+    else
+        hipLaunchKernelGGL((music_evd_group_full_kernel<4>), dim3((n_items + 15) / 16), dim3(64), 0, st, (const float2 *)d_R,
+                           (double *)d_full, (float2 *)d_pn, n_items, N, M);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }

@@ -39,6 +39,9 @@ struct doa_music_pipeline {
     int estimator = DOA_ESTIMATOR_MUSIC;    // doa_music_pipeline_set_estimator
     double loading = 0.0;           // Capon: the diagonal loading
     doa::DevBuf d_status;           // Capon: int32 per item between the inverse launch and the NaN follow-up
+    bool has_table = false;         // doa_music_pipeline_set_steering_table: an arbitrary array geometry
+    doa::ArrayTable array;          // its table in the scan's form (array_scan.hip)
+    doa::DevBuf d_full;             // the full records (N * N doubles per item) between the stage in front and the scan
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     doa::DevBuf d_in[2], d_res;
@@ -46,7 +49,7 @@ struct doa_music_pipeline {
     doa::PinnedBuf h_stage;         // scheduler-sized calls: one page-locked staging buffer, one copy each way
     int fail_chunk = -1;            // doa_music_pipeline_inject_failure, host-pointer entry: one-shot, cleared by every call (tests)
     // doa_music_pipeline_work_dev_batches: the library's own overlap lanes (pipeline_lanes.hpp); a lane's buffers:
-    enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch, kSmooth, kStatus };
+    enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch, kSmooth, kStatus, kFull };
     doa::PipeLanes lanes;
 };
 
@@ -58,6 +61,7 @@ struct PipeWs {
     void *work;             // K1's piece sums (overlapping windows), or NULL
     void *smooth;           // spatial smoothing on: S * S gr_complex per item (else unused)
     void *status;           // Capon: int32 per item (else unused)
+    void *full;             // steering-table handle: N * N doubles per item (else unused)
     doa::DevBuf *scratch;   // grown on demand: the serial peak pick of unusual vector lengths
     size_t scratch_item_off;
 };
@@ -90,6 +94,36 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
     if (capon && !dbl) {
         doa::set_error("music_pipeline: the Capon estimator needs internal precision 64 (handle is at %d)", h->bits);
         return DOA_ERR_UNSUPPORTED;
+    }
+    if (h->has_table) {
+        // an arbitrary array geometry: the stage in front writes full records, launch_array_scan replaces launch_music_scan,
+        // and the peak pick is a launch of its own on the table's axis -- the launches of the blocks MUSIC_array /
+        // capon_array and find_local_max
+        if (!dbl) {
+            doa::set_error("music_pipeline: a steering table needs internal precision 64 (handle is at %d)", h->bits);
+            return DOA_ERR_UNSUPPORTED;
+        }
+        if (!(skip & 2)) {
+            if (capon)
+                rc = doa::launch_capon_inverse(h->N, n, cov, h->loading, nullptr, nullptr, nullptr, ws.status, st, ws.full);
+            else
+                rc = doa::launch_music_evd_full(h->N, h->music.M, n, cov, ws.full, nullptr, st);
+        }
+        if (rc != DOA_OK) return rc;
+        if (skip & 4) return n;
+        rc = doa::launch_array_scan(h->array, n, ws.full, spec, nullptr, st);
+        if (rc != DOA_OK) return rc;
+        if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
+            rc = doa::launch_find_local_max(h->peaks, n, spec, mx, am, st);
+        } else {
+            rc = ws.scratch->reserve((size_t)h->max_batch * h->peaks.L);
+            if (rc == DOA_OK)
+                rc = doa::launch_find_local_max_serial(h->peaks, n, spec, mx, am,
+                                                       static_cast<char *>(ws.scratch->p) + ws.scratch_item_off * h->peaks.L, st);
+        }
+        if (rc == DOA_OK && capon && !(skip & 2))
+            rc = doa::launch_capon_invalid_rows(h->peaks.L, h->peaks.M, n, ws.status, store_spec ? spec : nullptr, mx, am, st);
+        return rc == DOA_OK ? n : rc;
     }
     if (!(skip & 2)) {
         if (capon)
@@ -138,6 +172,7 @@ static int run_dev(doa_music_pipeline *h, int n, const void *const *d_in, void *
     ws.work = h->d_work[lane].p;
     ws.smooth = h->S ? h->d_smooth.as<float2>() + item_off * h->S * h->S : nullptr;
     ws.status = h->d_status.p ? h->d_status.as<int>() + item_off : nullptr;
+    ws.full = h->d_full.p ? h->d_full.as<double>() + item_off * doa::full_record_len(h->N) : nullptr;
     ws.scratch = &h->d_scratch;
     ws.scratch_item_off = item_off;
     return run_ws(h, n, d_in, cov, spec, mx, am, ws, st);
@@ -191,6 +226,7 @@ void doa_music_pipeline_destroy(doa_music_pipeline_t *h)
     h->peaks.release();
     h->d_cov.release(); h->d_coef.release(); h->d_cheb.release(); h->d_spec.release(); h->d_scratch.release(); h->d_gain.release();
     h->d_smooth.release(); h->d_status.release();
+    h->array.release(); h->d_full.release();
     h->d_res.release(); h->h_stage.release();
     for (auto &b : h->d_work) b.release();
     for (auto &b : h->d_in) b.release();
@@ -247,6 +283,11 @@ int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarr
                        forward_backward, h->N, h->music.M);
         return DOA_ERR_INVALID_ARG;
     }
+    if (S != 0 && h->has_table) {
+        doa::set_error("music_pipeline_set_spatial_smoothing: smoothing assumes a translation-invariant (uniform linear) array; "
+                       "this handle has a steering table");
+        return DOA_ERR_UNSUPPORTED;
+    }
     if (S == h->S && fb == h->fb) return DOA_OK;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const int elements = S ? S : h->N;
@@ -279,6 +320,48 @@ int doa_music_pipeline_set_estimator(doa_music_pipeline_t *h, int estimator, flo
         h->loading = (double)diagonal_loading;
     }
     h->estimator = estimator;
+    return DOA_OK;
+}
+
+int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double *steering, float x_min, float x_max)
+{
+    doa::clear_error();
+    if (!h) { doa::set_error("music_pipeline_set_steering_table: bad arguments"); return DOA_ERR_INVALID_ARG; }
+    const int N = h->N, P = h->music.P, M = h->peaks.M;
+    if (!steering) {                                     // back to the uniform linear array and its 0 .. 180 axis
+        if (!h->has_table) return DOA_OK;
+        if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+        doa::PeakTables axis;
+        if (int rc = axis.build(M, P, 0.0f, 180.0f); rc != DOA_OK) { axis.release(); return rc; }
+        h->peaks.release();
+        h->peaks = axis;
+        h->has_table = false;
+        return DOA_OK;
+    }
+    if (!std::isfinite(x_min) || !std::isfinite(x_max) || !(x_max > x_min)) {
+        doa::set_error("music_pipeline_set_steering_table: need finite x_min < x_max (got %g, %g)", (double)x_min, (double)x_max);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (!doa::steering_table_finite(steering, N, P)) {
+        doa::set_error("music_pipeline_set_steering_table: the table (%d rows of %d complex doubles) holds a value that is not finite", P, N);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->S) {
+        doa::set_error("music_pipeline_set_steering_table: spatial smoothing is on, and it assumes a translation-invariant "
+                       "(uniform linear) array");
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    // everything is built aside and swapped in at the end: a failure leaves the handle as it was
+    doa::ArrayTable table;
+    doa::PeakTables axis;
+    int rc = table.build(N, P, steering);
+    if (rc == DOA_OK) rc = axis.build(M, P, x_min, x_max);
+    if (rc == DOA_OK) rc = h->d_full.reserve((size_t)h->max_batch * doa::full_record_len(N) * sizeof(double));
+    if (rc != DOA_OK) { table.release(); axis.release(); return rc; }
+    h->array.release(); h->peaks.release();
+    h->array = table; h->peaks = axis;
+    h->has_table = true;
     return DOA_OK;
 }
 
@@ -326,6 +409,10 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     }
     if (h->estimator != DOA_ESTIMATOR_MUSIC) {
         doa::set_error("music_pipeline_work_dev_auto: the source count needs eigenvalues, which the Capon estimator does not form");
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (h->has_table) {
+        doa::set_error("music_pipeline_work_dev_auto: a count per item is not available on a handle with a steering table");
         return DOA_ERR_UNSUPPORTED;
     }
     if (h->K < 2) {
@@ -454,7 +541,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     const bool dbl = (h->bits == 64);
 
     // ---- the plan: groups of consecutive batches and their lanes ----
-    const bool lean_shape = h->estimator == DOA_ESTIMATOR_MUSIC && h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
+    const bool lean_shape = h->estimator == DOA_ESTIMATOR_MUSIC && !h->has_table && h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
                             (long long)doa::kMaxGroup * n <= (1 << 28);
     const int L_all = solo ? 1 : h->lanes.n_lanes;
     const int L = (lean_shape && group_lanes() < L_all) ? group_lanes() : L_all;
@@ -532,10 +619,11 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     using H = doa_music_pipeline;
     // a lane's buffers hold a whole group: records and covariances are 64-128 B per item; the angles-only scratch rows are bounded (G_angles)
     auto reserve = [&](doa::DevBuf &coef, doa::DevBuf &cheb, doa::DevBuf &cov, doa::DevBuf &spec, doa::DevBuf &work,
-                       doa::DevBuf &smooth, doa::DevBuf &status) -> int {
+                       doa::DevBuf &smooth, doa::DevBuf &status, doa::DevBuf &full) -> int {
         int rc = coef.reserve((size_t)h->max_batch * doa::coef_stride(N) * (dbl ? sizeof(double) : sizeof(float)));
         if (rc == DOA_OK && h->S) rc = smooth.reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
         if (rc == DOA_OK && h->estimator == DOA_ESTIMATOR_CAPON) rc = status.reserve((size_t)h->max_batch * sizeof(int));
+        if (rc == DOA_OK && h->has_table) rc = full.reserve((size_t)h->max_batch * doa::full_record_len(N) * sizeof(double));
         if (rc == DOA_OK && doa::music_uses_cheb(evd_elements(h), h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
         if (rc == DOA_OK && need_cov) rc = cov.reserve((size_t)G * h->max_batch * N * N * sizeof(float2));
         if (rc == DOA_OK && need_spec) rc = spec.reserve((size_t)G_angles * h->max_batch * P * sizeof(float));
@@ -570,11 +658,11 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     };
     if (solo) {
         hipStream_t caller = static_cast<hipStream_t>(hip_stream);
-        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0], h->d_smooth, h->d_status);
+        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0], h->d_smooth, h->d_status, h->d_full);
         if (rc != DOA_OK) return rc;
         PipeWs ws;
         ws.coef = h->d_coef.p; ws.cheb = h->d_cheb.p; ws.spec_scratch = h->d_spec.p; ws.work = h->d_work[0].p;
-        ws.smooth = h->d_smooth.p; ws.status = h->d_status.p;
+        ws.smooth = h->d_smooth.p; ws.status = h->d_status.p; ws.full = h->d_full.p;
         ws.scratch = &h->d_scratch; ws.scratch_item_off = 0;
         for (size_t u = 0; u < plan.size() && rc >= 0; u++) rc = launch(plan[u], ws, h->d_cov.p, caller);
         if (rc >= 0 && injected) {
@@ -591,7 +679,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     }
     auto prepare = [&](doa::PipeLane &ln) -> int {
         return reserve(ln.buf[H::kCoef], ln.buf[H::kCheb], ln.buf[H::kCov], ln.buf[H::kSpec], ln.buf[H::kWork], ln.buf[H::kSmooth],
-                       ln.buf[H::kStatus]);
+                       ln.buf[H::kStatus], ln.buf[H::kFull]);
     };
     auto launch_unit = [&](int u, doa::PipeLane &ln) -> int {
         const PlanGroup &g = plan[u];
@@ -599,7 +687,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
             if (const int rc = h->lanes.synchronize(); rc != DOA_OK) return rc;
         PipeWs ws;
         ws.coef = ln.buf[H::kCoef].p; ws.cheb = ln.buf[H::kCheb].p; ws.spec_scratch = ln.buf[H::kSpec].p; ws.work = ln.buf[H::kWork].p;
-        ws.smooth = ln.buf[H::kSmooth].p; ws.status = ln.buf[H::kStatus].p;
+        ws.smooth = ln.buf[H::kSmooth].p; ws.status = ln.buf[H::kStatus].p; ws.full = ln.buf[H::kFull].p;
         ws.scratch = &ln.buf[H::kScratch]; ws.scratch_item_off = 0;
         return launch(g, ws, ln.buf[H::kCov].p, ln.st);
     };

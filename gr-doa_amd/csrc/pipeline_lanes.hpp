@@ -26,7 +26,7 @@ struct PipeLane {
     hipStream_t st = nullptr;
     bool own_stream = true;         // false: adopted from the caller (doa_*_pipeline_set_lane_streams)
     hipEvent_t done = nullptr;
-    static constexpr int kBufs = 8;
+    static constexpr int kBufs = 9;
     DevBuf buf[kBufs];              // what they hold is the owning pipeline's business
 };
 

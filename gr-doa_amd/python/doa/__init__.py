@@ -19,6 +19,13 @@ the Capon (MVDR) spectrum, which needs no source count and no eigendecomposition
 
     blk = doa.capon_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0)
 
+the two spectra for an arbitrary array geometry (a uniform circular array, a measured manifold), given as a steering table
+(also `music_pipeline.set_steering_table`):
+
+    table = doa.planar_steering_table(doa.uca_positions(5, 0.425), 720)      # [720, 5] complex128, azimuth 0..360
+    blk = doa.MUSIC_array(num_targets, table)
+    blk = doa.capon_array(table, diagonal_loading=0.0)
+
 and the calibration chain that produces the files phase_correct_hier and antenna_correction read
 (python/twinrx_phase_offset_est.py, findmax_and_save.py, average_and_save.py, save_antenna_calib.py):
 
@@ -30,6 +37,7 @@ no HIP device is usable.  There is no CPU fallback.
 """
 from ._lib import DoaError, LIB_PATH, last_error  # noqa: F401
 from .blocks import (autocorrelate, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, rootMUSIC_linear_array,  # noqa: F401
+                     MUSIC_array, capon_array, planar_steering_table, uca_positions,
                      music_pipeline, root_pipeline, root_music_pipeline, autocorrelate_sc16, music_pipeline_sc16,
                      root_music_pipeline_sc16, compass_mean, sim_source, set_internal_precision, get_internal_precision, device_count,
                      evd_fallback_count, DETACHED,

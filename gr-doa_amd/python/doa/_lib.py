@@ -176,8 +176,23 @@ SIGNATURES = {
     "doa_capon_lin_array_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_capon_lin_array_items_total": (C.c_longlong, [_vp]),
     "doa_music_pipeline_set_estimator": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "doa_planar_steering_table": (C.c_int, [C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp]),
+    "doa_MUSIC_array_create": (_vp, [C.c_int, C.c_int, C.c_int, _vp]),
+    "doa_MUSIC_array_destroy": (None, [_vp]),
+    "doa_MUSIC_array_work": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "doa_MUSIC_array_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_MUSIC_array_items_total": (C.c_longlong, [_vp]),
+    "doa_MUSIC_array_set_internal_precision": (C.c_int, [_vp, C.c_int]),
+    "doa_capon_array_create": (_vp, [C.c_int, C.c_int, _vp, C.c_float]),
+    "doa_capon_array_destroy": (None, [_vp]),
+    "doa_capon_array_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_capon_array_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_capon_array_items_total": (C.c_longlong, [_vp]),
+    "doa_music_pipeline_set_steering_table": (C.c_int, [_vp, _vp, C.c_float, C.c_float]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_capon_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_root_pipeline_inject_failure": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_lanes_idle": (C.c_int, [_vp]),
     "doa_hip_evd_fallback_counter_device_debug": (C.c_int, []),

@@ -504,6 +504,125 @@ class capon_lin_array(_Block):
         return int(lib.doa_capon_lin_array_items_total(self._h))
 
 
+def _steering(table) -> np.ndarray:
+    """[P, N] complex128, C-contiguous (the layout doa_MUSIC_array_create / doa_capon_array_create read)."""
+    a = np.ascontiguousarray(table, dtype=np.complex128)
+    if a.ndim != 2:
+        raise ValueError("a steering table is a [pspectrum_len, inputs] complex array")
+    return a
+
+
+def uca_positions(num_ant_ele, radius) -> np.ndarray:
+    """[N, 2] element positions (x, y, in wavelengths) of a uniform circular array: element n at angle 2 pi n / N."""
+    ang = 2.0 * np.pi * np.arange(int(num_ant_ele), dtype=np.float64) / int(num_ant_ele)
+    return np.stack([float(radius) * np.cos(ang), float(radius) * np.sin(ang)], axis=1)
+
+
+def planar_steering_table(positions, pspectrum_len, az_min=0.0, az_max=360.0, elevation=90.0) -> np.ndarray:
+    """The [pspectrum_len, N] complex128 steering table of a planar array (positions: [N, 2] in wavelengths) on the azimuth
+    grid az_i = az_min + i (az_max - az_min) / pspectrum_len at one elevation (degrees from the array normal; 90 = in the
+    array's plane): a_i[n] = exp(+j 2 pi sin(elevation) (x_n cos az_i + y_n sin az_i))  (doa_planar_steering_table; host
+    only, no device needed)."""
+    xy = np.ascontiguousarray(positions, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError("positions is an [inputs, 2] array of (x, y) in wavelengths")
+    n, p = xy.shape[0], int(pspectrum_len)
+    out = np.empty((max(p, 0), n), dtype=np.complex128)
+    check(lib.doa_planar_steering_table(n, _vp(xy), p, float(az_min), float(az_max), float(elevation), _vp(out)))
+    return out
+
+
+class MUSIC_array(_Block):
+    """doa.MUSIC_array(num_targets, steering) — the MUSIC spectrum for an arbitrary array geometry: steering is a
+    [pspectrum_len, inputs] complex table (row i = the array response towards direction i; planar_steering_table builds one
+    for a planar array, a measured manifold works as well), Q_i = Re(a_i^H P_N a_i) in double, output as MUSIC_lin_array's
+    (dB against the row maximum; definition: include/doa_hip.h).  Internal precision 64 only.  Not a block of the reference."""
+
+    _destroy = staticmethod(lib.doa_MUSIC_array_destroy)
+    _set_precision = staticmethod(lib.doa_MUSIC_array_set_internal_precision)
+
+    def __init__(self, num_targets, steering):
+        super().__init__()
+        a = _steering(steering)
+        self.num_targets, self.pspectrum_len, self.num_ant_ele = int(num_targets), int(a.shape[0]), int(a.shape[1])
+        self._h = check_handle(lib.doa_MUSIC_array_create(self.num_targets, self.num_ant_ele, self.pspectrum_len, _vp(a)),
+                               "MUSIC_array")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_F32, self.pspectrum_len)]
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        out = output_items[0]
+        assert a.size >= n * self.num_ant_ele ** 2
+        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
+        return check(lib.doa_MUSIC_array_work(self._h, n, _vp(a), _vp(out)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
+        return check(lib.doa_MUSIC_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+                                                  _stream_ptr(stream)))
+
+    def debug(self, R_items: np.ndarray):
+        """(P_N [n, N*N] complex128 column-major items, Q [n, P] float32) for the tests."""
+        a = np.ascontiguousarray(R_items, dtype=_C64).reshape(-1, self.num_ant_ele ** 2)
+        n = a.shape[0]
+        pn = np.empty((n, self.num_ant_ele ** 2), dtype=np.complex128)
+        q = np.empty((n, self.pspectrum_len), dtype=_F32)
+        check(lib.doa_MUSIC_array_debug(self._h, n, _vp(a), _vp(pn), _vp(q)))
+        return pn, q
+
+    def nout_items_total(self) -> int:
+        return int(lib.doa_MUSIC_array_items_total(self._h))
+
+
+class capon_array(_Block):
+    """doa.capon_array(steering, diagonal_loading=0.0) — the Capon (MVDR) spectrum 1 / (a^H R^-1 a) for an arbitrary array
+    geometry: steering as for MUSIC_array, the inverse, its status and diagonal_loading exactly as capon_lin_array's
+    (definition: include/doa_hip.h).  Port 0: the spectrum; port 1 (optional): int32 status, 1 = not positive definite enough
+    (that item's row is NaN).  Internal precision 64 only.  Not a block of the reference."""
+
+    _destroy = staticmethod(lib.doa_capon_array_destroy)
+
+    def __init__(self, steering, diagonal_loading=0.0):
+        super().__init__()
+        a = _steering(steering)
+        self.pspectrum_len, self.num_ant_ele = int(a.shape[0]), int(a.shape[1])
+        self.diagonal_loading = float(diagonal_loading)
+        self._h = check_handle(lib.doa_capon_array_create(self.num_ant_ele, self.pspectrum_len, _vp(a), self.diagonal_loading),
+                               "capon_array")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_F32, self.pspectrum_len), (_I32, 1)]
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        """output_items = [spectrum float32 [n, P]] or [spectrum, status int32 [n]]."""
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        out = output_items[0]
+        status = output_items[1] if len(output_items) > 1 else None
+        assert a.size >= n * self.num_ant_ele ** 2
+        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
+        if status is not None:
+            assert status.dtype == _I32 and status.flags.c_contiguous and status.size >= n
+        return check(lib.doa_capon_array_work(self._h, n, _vp(a), _vp(out),
+                                              _vp(status) if status is not None else C.c_void_p(0)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
+        return check(lib.doa_capon_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+                                                  _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+    def debug(self, R_items: np.ndarray):
+        """(W [n, N*N] complex128 column-major items, Q [n, P] float32) for the tests."""
+        a = np.ascontiguousarray(R_items, dtype=_C64).reshape(-1, self.num_ant_ele ** 2)
+        n = a.shape[0]
+        w = np.empty((n, self.num_ant_ele ** 2), dtype=np.complex128)
+        q = np.empty((n, self.pspectrum_len), dtype=_F32)
+        check(lib.doa_capon_array_debug(self._h, n, _vp(a), _vp(w), _vp(q)))
+        return w, q
+
+    def nout_items_total(self) -> int:
+        return int(lib.doa_capon_array_items_total(self._h))
+
+
 class rootMUSIC_linear_array(_Block):
     """doa.rootMUSIC_linear_array(norm_spacing, num_targets, inputs) — gr::sync_block
     (reference lib/rootMUSIC_linear_array_impl.cc:46-59)."""
@@ -630,6 +749,7 @@ class music_pipeline(_StreamInput, _Block):
         self.num_targets, self.pspectrum_len, self.max_batch = int(num_targets), int(pspectrum_len), int(max_batch)
         self.subarray_size, self.forward_backward = 0, 0            # set_spatial_smoothing
         self.estimator, self.diagonal_loading = "music", 0.0        # set_estimator
+        self.steering_table = None                                  # set_steering_table
         self._h = check_handle(lib.doa_music_pipeline_create(self.inputs, self.snapshot_size, self.overlap_size,
                                                              self.avg_method, self.norm_spacing, self.num_targets,
                                                              self.pspectrum_len, self.max_batch), "music_pipeline")
@@ -679,6 +799,22 @@ class music_pipeline(_StreamInput, _Block):
         check(lib.doa_music_pipeline_set_estimator(self._h, _ESTIMATORS[estimator.lower()], float(diagonal_loading)))
         self.estimator = estimator.lower()
         self.diagonal_loading = float(diagonal_loading) if self.estimator == "capon" else 0.0
+
+    def set_steering_table(self, table, x_min=0.0, x_max=360.0) -> None:
+        """An arbitrary array geometry, from the next work call on: table is a [pspectrum_len, inputs] complex steering table
+        (planar_steering_table builds one; MUSIC_array / capon_array define its use), (x_min, x_max) the peak pick's axis for its
+        directions.  The outputs are those of autocorrelate -> MUSIC_array | capon_array -> find_local_max, bit for bit.  None
+        restores the uniform linear array and the 0..180 axis.  Not available together with spatial smoothing or
+        work_dev_auto (doa_music_pipeline_set_steering_table)."""
+        if table is None:
+            check(lib.doa_music_pipeline_set_steering_table(self._h, C.c_void_p(0), 0.0, 180.0))
+            self.steering_table = None
+            return
+        a = _steering(table)
+        if a.shape != (self.pspectrum_len, self.inputs):
+            raise ValueError(f"the steering table must be [pspectrum_len, inputs] = [{self.pspectrum_len}, {self.inputs}], got {list(a.shape)}")
+        check(lib.doa_music_pipeline_set_steering_table(self._h, _vp(a), float(x_min), float(x_max)))
+        self.steering_table = a
 
     def set_stages(self, cov=True, evd=True, scan=True) -> None:
         """Profiling aid: drop stages from later work_dev calls (their outputs keep the previous call's values)."""

@@ -534,6 +534,82 @@ DOA_HIP_API long long doa_capon_lin_array_items_total(const doa_capon_lin_array_
 #define DOA_ESTIMATOR_CAPON 1
 DOA_HIP_API int doa_music_pipeline_set_estimator(doa_music_pipeline_t *h, int estimator, float diagonal_loading);
 
+/* ---------------------------------------------------------------------------------------------
+ * Arbitrary array geometry: MUSIC_array and capon_array — the two spectra for an array given by a STEERING TABLE instead of
+ *   a uniform linear array: a uniform circular array, any planar layout, or a measured (calibrated) manifold of a linear one.
+ *   Every other estimator of this library assumes a_n = z^n and hands its scan the 2N-1 diagonal sums of the projector, which
+ *   summarise a^H X a for that manifold only.  Not blocks of the reference.
+ * The definition, one for every entry (tests/array_ref.py restates it in numpy):
+ *   steering table  P rows of N complex doubles (N = num_ant_ele, P = pspectrum_len), a_i[n] at [i*N + n] (re, im); a HOST
+ *                   pointer at create, copied to the device once.  Rows need not have unit modulus (a calibrated manifold
+ *                   carries gains); every value must be finite.  Row i is direction i of the output; what the directions are
+ *                   is the caller's business (doa_planar_steering_table below builds an azimuth grid).
+ *   input item      column-major N x N gr_complex, upper triangle read, as MUSIC_lin_array / capon_lin_array take it.
+ *   X               MUSIC_array: the noise projector P_N = U_N U_N^H of the item (U_N = the eigenvectors of the N - num_targets
+ *                   smallest eigenvalues), as MUSIC_lin_array forms it; capon_array: W = (H / mu + delta I)^-1 EXACTLY as
+ *                   capon_lin_array defines it above (status, pivot rule DOA_CAPON_PIVOT_MIN and the all-NaN row included).
+ *   All arithmetic in double:
+ *       Q_i = Re(a_i^H X a_i)        out_i = 1 / Q_i        spectrum_i = 10 log10(out_i / max out)
+ *   with the dB normalisation of the ULA scans: Q is rounded to float, the row maximum is exactly 0.0 dB, and where several
+ *   directions tie the first one is the maximum find_local_max reports.
+ * Internal precision 64 only: a handle whose process default (at create) or handle precision is 32 returns
+ * DOA_ERR_UNSUPPORTED from its work entries.  create validates before the device is touched: 2 <= num_ant_ele <=
+ * DOA_MAX_ANT_ELE, 1 <= num_targets < num_ant_ele, pspectrum_len >= 1, a non-NULL finite table, diagonal_loading finite and
+ * >= 0.  An item's result depends on the item and the table alone (not on the batch size or its position in the batch).
+ * Peaks: find_local_max(num_max_vals, pspectrum_len, x_min, x_max) on the output, with the axis of the table's directions;
+ * it does not wrap around, so put az_min away from the sector of interest.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct doa_MUSIC_array doa_MUSIC_array_t;
+typedef struct doa_capon_array doa_capon_array_t;
+
+/* Host helper, no device needed: the steering table of a planar array for an azimuth grid at one elevation.
+ *   xy            2 * num_ant_ele doubles: element positions in wavelengths, x_n at [2n], y_n at [2n + 1]
+ *   az_i        = az_min_deg + i (az_max_deg - az_min_deg) / pspectrum_len,  i = 0 .. pspectrum_len - 1  (double; the end point
+ *                 is excluded, as in the grids of MUSIC_lin_array and find_local_max)
+ *   elevation     theta, measured from the array normal: 90 degrees is in the array's plane
+ *   a_i[n]      = exp(+j 2 pi sin(theta) (x_n cos(az_i) + y_n sin(az_i)))      -> table_out[i * num_ant_ele + n] (re, im)
+ * With x_n = d (n - (N-1)/2), y_n = 0 this is the ULA manifold of doa.sim.  DOA_OK, or DOA_ERR_INVALID_ARG unless
+ * 2 <= num_ant_ele <= DOA_MAX_ANT_ELE, pspectrum_len >= 1, everything finite, az_max_deg > az_min_deg, pointers non-NULL. */
+DOA_HIP_API int doa_planar_steering_table(int num_ant_ele, const double *xy, int pspectrum_len, double az_min_deg,
+                                          double az_max_deg, double elevation_deg, double *table_out);
+
+/* MUSIC_array: work / work_dev as doa_MUSIC_lin_array_work / _work_dev (items in, pspectrum_len floats per item out). */
+DOA_HIP_API doa_MUSIC_array_t *doa_MUSIC_array_create(int num_targets, int num_ant_ele, int pspectrum_len,
+                                                      const double *steering);
+DOA_HIP_API void doa_MUSIC_array_destroy(doa_MUSIC_array_t *h);
+DOA_HIP_API int doa_MUSIC_array_work(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out);
+DOA_HIP_API int doa_MUSIC_array_work_dev(doa_MUSIC_array_t *h, int noutput_items, const void *d_cov_items,
+                                         void *d_spectrum_out, void *hip_stream);
+DOA_HIP_API long long doa_MUSIC_array_items_total(const doa_MUSIC_array_t *h);
+/* bits = 32 or 64; a handle at 32 returns DOA_ERR_UNSUPPORTED from its work entries (there is no float form of this scan) */
+DOA_HIP_API int doa_MUSIC_array_set_internal_precision(doa_MUSIC_array_t *h, int bits);
+
+/* capon_array: work / work_dev as doa_capon_lin_array_work / _work_dev, the status output included (one int32 per item,
+ * may be NULL; a status-1 item gets an all-NaN row and does not disturb its neighbours). */
+DOA_HIP_API doa_capon_array_t *doa_capon_array_create(int num_ant_ele, int pspectrum_len, const double *steering,
+                                                      float diagonal_loading);
+DOA_HIP_API void doa_capon_array_destroy(doa_capon_array_t *h);
+DOA_HIP_API int doa_capon_array_work(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out,
+                                     void *status_out);
+DOA_HIP_API int doa_capon_array_work_dev(doa_capon_array_t *h, int noutput_items, const void *d_cov_items,
+                                         void *d_spectrum_out, void *d_status_out, void *hip_stream);
+DOA_HIP_API long long doa_capon_array_items_total(const doa_capon_array_t *h);
+/* music_pipeline for an arbitrary array geometry: a per-handle setting, taking effect from the next work call.  steering is a
+ * HOST pointer to pspectrum_len rows of `inputs` complex doubles (the table defined above; copied to the device once);
+ * (x_min, x_max) is the axis of find_local_max for the table's directions (float, x_max > x_min, both finite).  With a table
+ * the stage in front (the eigen launch, or the Capon inverse when the estimator is DOA_ESTIMATOR_CAPON) writes full records
+ * into a workspace of the handle (one per lane in work_dev_batches), the steering-table scan replaces the ULA scan, and the
+ * peak pick runs as its own launch on the axis rebuilt for (x_min, x_max):  the outputs are bit-identical to the chain
+ * autocorrelate -> MUSIC_array | capon_array -> find_local_max(num_targets, pspectrum_len, x_min, x_max).  steering == NULL
+ * restores the uniform linear array of create and the 0 .. 180 axis (outputs bit-identical to a fresh handle's).
+ * On a table handle: work_dev_batches runs one chain of launches per batch (no grouped launches); work_dev_auto returns
+ * DOA_ERR_UNSUPPORTED (no count per item); switching spatial smoothing on -- or setting a table while it is on -- returns
+ * DOA_ERR_UNSUPPORTED (smoothing assumes a translation-invariant array); every work entry of a handle at internal precision
+ * 32 returns DOA_ERR_UNSUPPORTED.  A bad table or axis returns DOA_ERR_INVALID_ARG.  A refused call leaves the handle as it
+ * was.  Call it, like every setter, when no work of the handle is in flight. */
+DOA_HIP_API int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double *steering, float x_min,
+                                                      float x_max);
+
 /* rootMUSIC_linear_array with a count per item: counts = one int32 m_i per item, used in place of the handle's num_targets
  * W.  Items stay W floats wide.  With top = min(W, num_ant_ele - 1):
  *   1 <= m_i <= top   the first m_i slots are what rootMUSIC_linear_array(norm_spacing, m_i, num_ant_ele) writes for the

@@ -55,6 +55,15 @@ DOA_HIP_API int doa_rootMUSIC_linear_array_select_counts_debug(doa_rootMUSIC_lin
 DOA_HIP_API int doa_capon_lin_array_debug(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items,
                                           void *inverse_out, void *null_spectrum_out);
 
+/* Diagnostics of MUSIC_array and capon_array (host buffers, synchronous): per item the matrix X the scan read (projector_out /
+ * inverse_out: N x N complex128, column-major, unpacked from the double full record; NaN for a status-1 Capon item) and
+ * the un-normalised null spectrum Q_i = Re(a_i^H X a_i) (null_spectrum_out: pspectrum_len floats).  Either output pointer may
+ * be NULL. */
+DOA_HIP_API int doa_MUSIC_array_debug(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *projector_out,
+                                      void *null_spectrum_out);
+DOA_HIP_API int doa_capon_array_debug(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *inverse_out,
+                                      void *null_spectrum_out);
+
 /* Profiling aid: which stages later work_dev calls on this handle launch (bit 0 = K1 covariance, bit 1 = K2+K3
  * EVD, bit 2 = K4+K5 scan + peak pick; default 7).  A dropped stage leaves its outputs as the previous call
  * wrote them, so a profiler can time one kernel on valid intermediates; not for production use. */
