@@ -85,8 +85,25 @@ int launch_music_evd(int N, int M, int n_items, const void *d_R, void *d_coef, v
 // (int32).  Forced mode: the count is read from d_counts_in (int32).  d_eig_out (optional): N floats per item, ascending, at
 // the item's scale.  d_coef_d (double records) and d_cheb (N <= 4) may be NULL (count / eigenvalues only).  Count 0: the
 // record of P_N = I; a count outside 0..N-1: a NaN record.
+// d_rec (optional): the signal-subspace record (below); with it the launch is the group form at every N (4 lanes per item
+// for N <= 4: the form that holds the eigenvectors by rows) and d_coef_d may be NULL.
 int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_counts_in, void *d_count_out, void *d_eig_out,
-                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st);
+                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st, void *d_rec = nullptr);
+// ---- ESPRIT (esprit.hip; definition in include/doa_hip.h) -----------------------------------------------------------------
+// SIGNAL-SUBSPACE RECORD of an item: all N eigenvectors of H as columns ordered by DESCENDING eigenvalue (the eig_sym
+// ranking reversed), 2 N^2 doubles: [2 (k N + row)] = Re V[row][k], [2 (k N + row) + 1] = Im V[row][k].  A consumer takes
+// the first M columns, whatever M is for that item.  A non-finite item's record is UNSPECIFIED (its eigenvalues do not rank, so
+// columns may stay unwritten): a consumer decides from the item itself, as esprit_kernel does for status 1.
+__host__ __device__ inline size_t subspace_record_len(int N) { return (size_t)2 * N * N; }
+// The eigen stage writing the record only (always the double Jacobi forms: 4 lanes per item for N <= 4, 8 lanes for N <= 8,
+// one wave for N <= 16).  The record does not depend on a source count.
+int launch_music_evd_record(int N, int n_items, const void *d_R, void *d_rec, hipStream_t st);
+// esprit_kernel: W floats per item from the first m columns of its record; d_R (the items the record came from) supplies
+// the trace test.  d_counts == NULL: m = W for every item.  Otherwise m_i = d_counts[i] (int32): 1 <= m_i <= min(W, N-1):
+// the first m_i slots as the fixed launch writes them for W = m_i, the others NaN; 0: all NaN, status 0; else all NaN,
+// status 2.  d_status (optional): int32 per item, 0 ok / 1 not solvable / 2 no usable count / 3 iteration cap.
+int launch_esprit(int N, int W, float norm_spacing, int n_items, const void *d_R, const void *d_rec, const void *d_counts,
+                  void *d_out, void *d_status, hipStream_t st);
 // after the scan of a per-item-count call: rows (P floats) of items whose count is outside 0..N-1 become NaN (the scan kernels
 // themselves write 0.0 dB for a NaN record)
 int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, void *d_spec, hipStream_t st);

@@ -239,7 +239,8 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
                                                    double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                    const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
                                                    double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{},
-                                                   T inv_sc = (T)1, T poison = (T)0, double *__restrict__ pn_d = nullptr)
+                                                   T inv_sc = (T)1, T poison = (T)0, double *__restrict__ pn_d = nullptr,
+                                                   double *__restrict__ es_rec = nullptr)
 {
     // eigenvalue of lane r = A[r][r]; ascending rank inside the group; noise set = ranks < N-M
     int rank = 0;
@@ -247,6 +248,22 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
     for (int j = 0; j < G; j++) {
         const T lj = lane_fetch<T>(lam, base + j);
         rank += ((lj < lam) || (lj == lam && j < r)) ? 1 : 0;
+    }
+    if (es_rec) {
+        // the signal-subspace record (kernels.hpp): slot i is column N-1-rank_i; lane r stores its row of every real slot
+        double *rc = es_rec + (size_t)item * (2 * N * N);
+#pragma unroll
+        for (int i = 0; i < G; i++) {
+            const int ri = __shfl(rank, base + i, kWave);
+            const bool slot = __shfl(real_col ? 1 : 0, base + i, kWave) != 0;
+            if (real_item && slot && ri < N && r < N) {      // (ri < N fails only for a non-finite item)
+                double *o = rc + 2 * ((size_t)(N - 1 - ri) * N + r);
+                o[0] = (double)vr[i]; o[1] = (double)vi[i];
+            }
+        }
+        if constexpr (!kPerItemCounts<Cnt>) {
+            if (!coef && !coef_d && !pn_out && !pn_d && !cal_out) return;       // the record-only launch
+        }
     }
     if (cal_out) {
         // calibrate_lin_array (reference lib/calibrate_lin_array_impl.cc:98-134): U_S = eigenvector of the
@@ -393,7 +410,7 @@ __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, in
                                                float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
                                                double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{},
-                                               double *__restrict__ pn_d = nullptr);
+                                               double *__restrict__ pn_d = nullptr, double *__restrict__ es_rec = nullptr);
 
 template <int G, typename T>
 __global__ __launch_bounds__(64) void music_evd_group_kernel(const float2 *__restrict__ R, float *__restrict__ coef,
@@ -413,7 +430,8 @@ template <int G, typename T, class Cnt>
 __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, int item, bool real_item, int N, int M,
                                                float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
                                                const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                               double *__restrict__ cheb_d, const Cnt &cnt, double *__restrict__ pn_d)
+                                               double *__restrict__ cheb_d, const Cnt &cnt, double *__restrict__ pn_d,
+                                               double *__restrict__ es_rec)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int r = lane % G, base = lane - r;
@@ -476,16 +494,17 @@ __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, in
     for (int k = 0; k < G; k++) vr[k] += poison;
     if constexpr (kPerItemCounts<Cnt>)
         evd_group_epilogue<G, T, Cnt>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out,
-                                      cheb_d, cnt, (T)1 / sc, poison);
+                                      cheb_d, cnt, (T)1 / sc, poison, nullptr, es_rec);
     else
     evd_group_epilogue<G, T>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out, cheb_d,
-                             EvdFixedM{}, (T)1, (T)0, pn_d);
+                             EvdFixedM{}, (T)1, (T)0, pn_d, es_rec);
 }
 
 // the group Jacobi with a count per item (launch_music_evd_counts; double)
 template <int G>
 __global__ __launch_bounds__(64) void music_evd_group_counts_kernel(const float2 *__restrict__ R, double *__restrict__ coef_d,
-                                                                    int n_items, int N, EvdCounts cnt)
+                                                                    int n_items, int N, EvdCounts cnt,
+                                                                    double *__restrict__ es_rec)
 {
     constexpr int IPW = kWave / G;
     const int lane = threadIdx.x & (kWave - 1);
@@ -493,7 +512,7 @@ __global__ __launch_bounds__(64) void music_evd_group_counts_kernel(const float2
     const bool real_item = item < n_items;
     if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
     evd_group_wave<G, double, EvdCounts>(R + (size_t)item * (N * N), item, real_item, N, 0, nullptr, coef_d, nullptr, nullptr,
-                                         nullptr, nullptr, cnt);
+                                         nullptr, nullptr, cnt, nullptr, es_rec);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -886,7 +905,8 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
                                                  double *__restrict__ coef_d, float2 *__restrict__ pn_out, int N, int M,
                                                  const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
                                                  T *__restrict__ sVr, T *__restrict__ sVi, T *__restrict__ sLam,
-                                                 const Cnt &cnt = Cnt{}, double *__restrict__ pn_d = nullptr)
+                                                 const Cnt &cnt = Cnt{}, double *__restrict__ pn_d = nullptr,
+                                                 double *__restrict__ es_rec = nullptr)
 {
     constexpr int G = 16;
     const int lane = threadIdx.x & (kWave - 1);
@@ -1036,6 +1056,21 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
                 rank += ((lj < lam) || (lj == lam && j < lane)) ? 1 : 0;
             }
         }
+        if (es_rec) {
+            // the signal-subspace record (kernels.hpp): slot i is column N-1-rank_i; lane r < N stores its row of every real slot
+            double *rc = es_rec + (size_t)item * (2 * N * N);
+#pragma unroll
+            for (int i = 0; i < G; i++) {
+                const int ri = __shfl(rank, i, kWave);
+                if (!((pad >> i) & 1u) && ri < N && lane < N) {      // (ri < N fails only for a non-finite item)
+                    double *o = rc + 2 * ((size_t)(N - 1 - ri) * N + lane);
+                    o[0] = (double)sVr[lane * G + i]; o[1] = (double)sVi[lane * G + i];
+                }
+            }
+            if constexpr (!kPerItemCounts<Cnt>) {
+                if (!coef && !coef_d) return;                // the record-only launch
+            }
+        }
         bool count_bad = false, count_zero = false;          // (EvdCounts only)
         if constexpr (kPerItemCounts<Cnt>) {
             // sLam <- the eigenvalues by rank (padding slots rank last), at the item's scale
@@ -1096,7 +1131,7 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
 #pragma unroll
         for (int k = 0; k < G; k++) { er[k] = sVr[lane * G + k]; ei[k] = sVi[lane * G + k]; }
         evd_group_epilogue<G, T>(er, ei, sLam[lane], !((pad >> lane) & 1u), lane, 0, lane, item, true, N, M, coef, coef_d,
-                                 pn_out, pilot, cal_out, nullptr, EvdFixedM{}, (T)1, (T)0, pn_d);
+                                 pn_out, pilot, cal_out, nullptr, EvdFixedM{}, (T)1, (T)0, pn_d);      // (the record: LEAN only)
     }
 }
 
@@ -1113,12 +1148,13 @@ __global__ __launch_bounds__(64) void music_evd_block16_kernel(const float2 *__r
 
 // the block Jacobi with a count per item (launch_music_evd_counts; double)
 __global__ __launch_bounds__(64) void music_evd_block16_counts_kernel(const float2 *__restrict__ R, double *__restrict__ coef_d,
-                                                                      int n_items, int N, EvdCounts cnt)
+                                                                      int n_items, int N, EvdCounts cnt,
+                                                                      double *__restrict__ es_rec)
 {
     __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
     const int item = blockIdx.x;                         // grid = n_items
     evd_block16_item<double, true, EvdCounts>(R + (size_t)item * (N * N), item, nullptr, coef_d, nullptr, N, 0, nullptr, nullptr,
-                                              sVr, sVi, sLam, cnt);
+                                              sVr, sVi, sLam, cnt, nullptr, es_rec);
 }
 
 // One wave per item: the signal-subspace iteration (evd_subspace.hpp) first; whatever it does not certify takes the
@@ -1320,7 +1356,7 @@ template <int N> static void launch_evd_counts_n(int n_items, const void *d_R, c
 }
 
 int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_counts_in, void *d_count_out, void *d_eig_out,
-                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st)
+                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st, void *d_rec)
 {
     if (n_items <= 0) return DOA_OK;
     if (N < 2 || N > DOA_MAX_ANT_ELE) {
@@ -1336,10 +1372,18 @@ int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_c
     // always the Jacobi forms (the subspace iterations never form the noise eigenvalues)
     if (N > 8) {
         hipLaunchKernelGGL(music_evd_block16_counts_kernel, dim3(n_items), dim3(64), 0, st, (const float2 *)d_R, (double *)d_coef_d,
-                           n_items, N, cnt);
+                           n_items, N, cnt, (double *)d_rec);
     } else if (N > 4) {
         hipLaunchKernelGGL((music_evd_group_counts_kernel<8>), dim3((n_items + 7) / 8), dim3(64), 0, st, (const float2 *)d_R,
-                           (double *)d_coef_d, n_items, N, cnt);
+                           (double *)d_coef_d, n_items, N, cnt, (double *)d_rec);
+    } else if (d_rec) {
+        // the record needs the eigenvectors by rows: four lanes per item (no Chebyshev record from this form's count mode)
+        if (d_cheb) {
+            set_error("MUSIC: the signal-subspace record and the Chebyshev record do not come from one launch");
+            return DOA_ERR_INVALID_ARG;
+        }
+        hipLaunchKernelGGL((music_evd_group_counts_kernel<4>), dim3((n_items + 15) / 16), dim3(64), 0, st, (const float2 *)d_R,
+                           (double *)d_coef_d, n_items, N, cnt, (double *)d_rec);
     } else {
         switch (N) {
         case 2: launch_evd_counts_n<2>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
@@ -1373,6 +1417,53 @@ __global__ __launch_bounds__(64) void music_evd_block16_full_kernel(const float2
     const int item = blockIdx.x;                         // grid = n_items
     evd_block16_item<double, false>(R + (size_t)item * (N * N), item, nullptr, nullptr, pn_out, N, M, nullptr, nullptr, sVr, sVi, sLam,
                                     EvdFixedM{}, full);
+}
+
+// The Jacobi forms writing the signal-subspace record only (kernels.hpp): ESPRIT's eigen launch.
+template <int G>
+__global__ __launch_bounds__(64) void music_evd_group_record_kernel(const float2 *__restrict__ R, double *__restrict__ es_rec,
+                                                                    int n_items, int N)
+{
+    constexpr int IPW = kWave / G;                       // items per wave
+    const int lane = threadIdx.x & (kWave - 1);
+    int item = blockIdx.x * IPW + lane / G;
+    const bool real_item = item < n_items;
+    if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
+    evd_group_wave<G, double>(R + (size_t)item * (N * N), item, real_item, N, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              EvdFixedM{}, nullptr, es_rec);
+}
+
+__global__ __launch_bounds__(64) void music_evd_block16_record_kernel(const float2 *__restrict__ R, double *__restrict__ es_rec,
+                                                                      int n_items, int N)
+{
+    __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
+    const int item = blockIdx.x;                         // grid = n_items
+    evd_block16_item<double, true>(R + (size_t)item * (N * N), item, nullptr, nullptr, nullptr, N, 1, nullptr, nullptr, sVr, sVi, sLam,
+                                   EvdFixedM{}, nullptr, es_rec);
+}
+
+int launch_music_evd_record(int N, int n_items, const void *d_R, void *d_rec, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    if (N < 2 || N > DOA_MAX_ANT_ELE) {
+        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (!d_R || !d_rec) {
+        set_error("MUSIC: bad arguments of the record eigen launch (N=%d)", N);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (N > 8)
+        hipLaunchKernelGGL(music_evd_block16_record_kernel, dim3(n_items), dim3(64), 0, st, (const float2 *)d_R, (double *)d_rec,
+                           n_items, N);
+    else if (N > 4)
+        hipLaunchKernelGGL((music_evd_group_record_kernel<8>), dim3((n_items + 7) / 8), dim3(64), 0, st, (const float2 *)d_R,
+                           (double *)d_rec, n_items, N);
+    else
+        hipLaunchKernelGGL((music_evd_group_record_kernel<4>), dim3((n_items + 15) / 16), dim3(64), 0, st, (const float2 *)d_R,
+                           (double *)d_rec, n_items, N);
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
 }
 
 int launch_music_evd_full(int N, int M, int n_items, const void *d_R, void *d_full, void *d_pn, hipStream_t st)

@@ -23,13 +23,15 @@ struct doa_root_pipeline {
     float scale = 1.0f;
     int S = 0, fb = 0;              // doa_root_pipeline_set_spatial_smoothing: subarray size (0 = off), forward-backward
     doa::DevBuf d_smooth;           // the smoothed items (S * S per item) between K1 and the eigen stage (max_batch items)
+    int estimator = DOA_GRIDFREE_ROOT_MUSIC;    // doa_root_pipeline_set_estimator
+    doa::DevBuf d_rec;              // ESPRIT mode: the signal-subspace records between the eigen launch and esprit_kernel
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     doa::DevBuf d_in[2], d_res;
     doa::DevBuf d_work[2];
     doa::PinnedBuf h_stage, h_status;
     int fail_chunk = -1;
-    enum { kCoef = 0, kCov, kStatus, kWork, kSmooth };
+    enum { kCoef = 0, kCov, kStatus, kWork, kSmooth, kRec };
     doa::PipeLanes lanes;
 };
 
@@ -39,10 +41,20 @@ struct RootWs {
     void *status;     // one int per item (1 = no root strictly inside the unit circle), or the caller's buffer
     void *work;       // K1's piece sums (overlapping windows), or NULL
     void *smooth;     // spatial smoothing on: S * S gr_complex per item (else unused)
+    void *rec;        // ESPRIT mode: signal-subspace records of the chain's items (else unused)
 };
 // the array the eigen stage and the root finder see: the subarray of a smoothed handle
 int evd_elements(const doa_root_pipeline *h) { return h->S ? h->S : h->N; }
 size_t coef_bytes(const doa_root_pipeline *h, size_t items) { return items * doa::coef_stride(h->N) * sizeof(double); }
+// (sized for the full array: a later set_spatial_smoothing only makes the records smaller)
+size_t rec_bytes(const doa_root_pipeline *h, size_t items) { return items * doa::subspace_record_len(h->N) * sizeof(double); }
+bool esprit_mode(const doa_root_pipeline *h) { return h->estimator == DOA_GRIDFREE_ESPRIT; }
+int esprit_precision(const char *who, const doa_root_pipeline *h)
+{
+    if (!esprit_mode(h) || h->bits == 64) return DOA_OK;
+    doa::set_error("%s: ESPRIT needs internal precision 64 (handle is at %d)", who, h->bits);
+    return DOA_ERR_UNSUPPORTED;
+}
 
 // K1 -> EVD -> roots for n items on `st`
 int run_chain(doa_root_pipeline *h, int n, const void *const *d_in, void *cov, void *angles, const RootWs &ws, hipStream_t st)
@@ -56,6 +68,12 @@ int run_chain(doa_root_pipeline *h, int n, const void *const *d_in, void *cov, v
         cov = ws.smooth;
     }
     const int elements = evd_elements(h);
+    if (esprit_mode(h)) {                       // the eigen launch that writes the record, then esprit_kernel
+        rc = doa::launch_music_evd_record(elements, n, cov, ws.rec, st);
+        if (rc != DOA_OK) return rc;
+        rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, ws.rec, nullptr, angles, ws.status, st);
+        return rc == DOA_OK ? n : rc;
+    }
     rc = doa::launch_music_evd(elements, h->M, n, cov, nullptr, ws.coef, nullptr, h->bits, st);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_root_music(elements, h->M, h->norm_spacing, n, ws.coef, angles, ws.status, st);
@@ -68,8 +86,12 @@ int first_flagged(const int *status, int n)
         if (status[i] != 0) return i;
     return -1;
 }
-int numeric_error(int item)
+int numeric_error(const doa_root_pipeline *h, int item, int status)
 {
+    if (esprit_mode(h)) {
+        doa::set_error("root_pipeline: ESPRIT item %d has status %d (1 = not solvable, 3 = eigenvalue iteration cap)", item, status);
+        return DOA_ERR_NUMERIC;
+    }
     doa::set_error("root_pipeline: item %d has no root strictly inside the unit circle (the reference raises in "
                    "arma::index_min here, lib/rootMUSIC_linear_array_impl.cc:129)", item);
     return DOA_ERR_NUMERIC;
@@ -117,7 +139,7 @@ void doa_root_pipeline_destroy(doa_root_pipeline_t *h)
     if (!h) return;
     h->d_cov.release(); h->d_coef.release(); h->d_status.release(); h->d_gain.release(); h->d_res.release();
     h->h_stage.release(); h->h_status.release();
-    h->d_smooth.release();
+    h->d_smooth.release(); h->d_rec.release();
     for (auto &b : h->d_work) b.release();
     for (auto &b : h->d_in) b.release();
     for (auto st : h->hst)
@@ -176,6 +198,24 @@ int doa_root_pipeline_set_spatial_smoothing(doa_root_pipeline_t *h, int subarray
     return DOA_OK;
 }
 
+int doa_root_pipeline_set_estimator(doa_root_pipeline_t *h, int estimator)
+{
+    doa::clear_error();
+    if (!h || (estimator != DOA_GRIDFREE_ROOT_MUSIC && estimator != DOA_GRIDFREE_ESPRIT)) {
+        doa::set_error("root_pipeline_set_estimator: need a handle and DOA_GRIDFREE_ROOT_MUSIC or DOA_GRIDFREE_ESPRIT (got %d)", estimator);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (estimator == h->estimator) return DOA_OK;
+    if (estimator == DOA_GRIDFREE_ESPRIT) {
+        // work_dev / work_dev_auto and the host entry (whose chunks lie at their item offsets) share this one; the lanes of
+        // work_dev_batches have their own (kRec)
+        if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+        if (int rc = h->d_rec.reserve(rec_bytes(h, (size_t)h->max_batch)); rc != DOA_OK) return rc;
+    }
+    h->estimator = estimator;
+    return DOA_OK;
+}
+
 int doa_root_pipeline_work_dev(doa_root_pipeline_t *h, int noutput_items, const void *const *d_input_items, void *d_cov_out,
                                void *d_angles_out, int *d_status_out, void *hip_stream)
 {
@@ -188,9 +228,10 @@ int doa_root_pipeline_work_dev(doa_root_pipeline_t *h, int noutput_items, const 
         doa::set_error("root_pipeline_work_dev: noutput_items=%d exceeds max_batch=%d", noutput_items, h->max_batch);
         return DOA_ERR_INVALID_ARG;
     }
+    if (int prc = esprit_precision("root_pipeline_work_dev", h); prc != DOA_OK) return prc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    RootWs ws{h->d_coef.p, d_status_out ? (void *)d_status_out : h->d_status.p, h->d_work[0].p, h->d_smooth.p};
+    RootWs ws{h->d_coef.p, d_status_out ? (void *)d_status_out : h->d_status.p, h->d_work[0].p, h->d_smooth.p, h->d_rec.p};
     return run_chain(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : h->d_cov.p, d_angles_out, ws,
                      static_cast<hipStream_t>(hip_stream));
 }
@@ -230,6 +271,14 @@ int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int noutput_items, c
     if (rc == DOA_OK && h->S) {
         rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, n, cov, h->d_smooth.p, st);
         cov = h->d_smooth.p;
+    }
+    if (rc == DOA_OK && esprit_mode(h)) {       // one estimating eigen launch (counts, eigenvalues, record), the counted ESPRIT kernel
+        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, nullptr, nullptr, st,
+                                          h->d_rec.p);
+        if (rc == DOA_OK)
+            rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, h->d_rec.p, d_count_out, d_angles_out,
+                                    d_status_out ? (void *)d_status_out : h->d_status.p, st);
+        return rc == DOA_OK ? n : rc;
     }
     if (rc == DOA_OK)
         rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, h->d_coef.p, nullptr, st);
@@ -286,6 +335,7 @@ int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, in
             doa::set_error("root_pipeline_work_dev_batches: batch %d has no angle output pointer", b);
             return DOA_ERR_INVALID_ARG;
         }
+    if (int prc = esprit_precision("root_pipeline_work_dev_batches", h); prc != DOA_OK) return prc;
     if (n_batches == 0 || noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const int N = h->N;
@@ -301,7 +351,7 @@ int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, in
                 return DOA_ERR_HIP;
             }
             RootWs ws{h->d_coef.p, (d_status_out && d_status_out[b]) ? (void *)d_status_out[b] : h->d_status.p, h->d_work[0].p,
-                      h->d_smooth.p};
+                      h->d_smooth.p, h->d_rec.p};
             const int rc = run_chain(h, noutput_items, d_input_items + (size_t)b * N,
                                      (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : h->d_cov.p, d_angles_out[b], ws, caller);
             if (rc < 0) { (void)hipStreamSynchronize(caller); return rc; }
@@ -321,11 +371,12 @@ int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, in
         if (rc == DOA_OK && need_status) rc = ln.buf[H::kStatus].reserve((size_t)h->max_batch * sizeof(int));
         if (rc == DOA_OK && work_bytes) rc = ln.buf[H::kWork].reserve(work_bytes);
         if (rc == DOA_OK && h->S) rc = ln.buf[H::kSmooth].reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
+        if (rc == DOA_OK && esprit_mode(h)) rc = ln.buf[H::kRec].reserve(rec_bytes(h, (size_t)h->max_batch));
         return rc;
     };
     auto launch = [&](int b, doa::PipeLane &ln) -> int {
         RootWs ws{ln.buf[H::kCoef].p, (d_status_out && d_status_out[b]) ? (void *)d_status_out[b] : ln.buf[H::kStatus].p,
-                  ln.buf[H::kWork].p, ln.buf[H::kSmooth].p};
+                  ln.buf[H::kWork].p, ln.buf[H::kSmooth].p, ln.buf[H::kRec].p};
         return run_chain(h, noutput_items, d_input_items + (size_t)b * N,
                          (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : ln.buf[H::kCov].p, d_angles_out[b], ws, ln.st);
     };
@@ -345,6 +396,7 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
         doa::set_error("root_pipeline_work: noutput_items=%d exceeds max_batch=%d", noutput_items, h->max_batch);
         return DOA_ERR_INVALID_ARG;
     }
+    if (int prc = esprit_precision("root_pipeline_work", h); prc != DOA_OK) return prc;
     if (noutput_items == 0) return 0;
     const int N = h->N, M = h->M;
     for (int k = 0; k < N; k++)
@@ -385,7 +437,7 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
                 DOA_HIP_TRY(hipMemcpyAsync(h->d_in[0].p, hs, in_bytes, hipMemcpyHostToDevice, st));
                 char *dr = h->d_res.as<char>();
                 if (h->fail_chunk == 0) { doa::set_error("root_pipeline_work: injected failure"); return DOA_ERR_HIP; }
-                RootWs ws{h->d_coef.p, dr + off_st, h->d_work[0].p, h->d_smooth.p};
+                RootWs ws{h->d_coef.p, dr + off_st, h->d_work[0].p, h->d_smooth.p, h->d_rec.p};
                 const int rr = run_chain(h, noutput_items, d_ptrs, cov_out ? (void *)(dr + off_cov) : h->d_cov.p, dr, ws, st);
                 if (rr < 0) return rr;
                 DOA_HIP_TRY(hipMemcpyAsync(hs, dr, out_bytes, hipMemcpyDeviceToHost, st));
@@ -398,7 +450,8 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
             if (se != hipSuccess) { doa::set_error("root_pipeline_work: %s", hipGetErrorString(se)); return DOA_ERR_HIP; }
             memcpy(angles_out, hs, ang_b);
             if (cov_out) memcpy(cov_out, hs + off_cov, cov_b);
-            if (const int bad = first_flagged(reinterpret_cast<const int *>(hs + off_st), noutput_items); bad >= 0) return numeric_error(bad);
+            if (const int bad = first_flagged(reinterpret_cast<const int *>(hs + off_st), noutput_items); bad >= 0)
+                return numeric_error(h, bad, reinterpret_cast<const int *>(hs + off_st)[bad]);
             return noutput_items;
         }
     }
@@ -430,7 +483,8 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
         float2 *cov = h->d_cov.as<float2>() + s0 * N * N;
         // (the two copy/compute lanes write disjoint item ranges of the handle's records and smoothed items)
         RootWs ws{static_cast<char *>(h->d_coef.p) + coef_bytes(h, s0), d_st + s0, h->d_work[lane].p,
-                  h->S ? (void *)(h->d_smooth.as<float2>() + s0 * h->S * h->S) : nullptr};
+                  h->S ? (void *)(h->d_smooth.as<float2>() + s0 * h->S * h->S) : nullptr,
+                  esprit_mode(h) ? (void *)(h->d_rec.as<char>() + rec_bytes(h, s0)) : nullptr};
         const int rr = run_chain(h, (int)n, d_ptrs, cov, d_ang + s0 * M, ws, st);
         if (rr < 0) return rr;
         if (cov_out)
@@ -453,7 +507,7 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
         if (e != hipSuccess && rc >= 0) { doa::set_error("root_pipeline_work: %s", hipGetErrorString(e)); rc = DOA_ERR_HIP; }
     }
     if (rc < 0) return rc;
-    if (const int bad = first_flagged(h->h_status.as<int>(), noutput_items); bad >= 0) return numeric_error(bad);
+    if (const int bad = first_flagged(h->h_status.as<int>(), noutput_items); bad >= 0) return numeric_error(h, bad, h->h_status.as<int>()[bad]);
     return noutput_items;
 }
 

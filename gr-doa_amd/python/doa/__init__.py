@@ -19,6 +19,10 @@ the Capon (MVDR) spectrum, which needs no source count and no eigendecomposition
 
     blk = doa.capon_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0)
 
+least-squares ESPRIT, the grid-free estimate without a polynomial or a search (also `root_pipeline.set_estimator("esprit")`):
+
+    blk = doa.esprit_linear_array(norm_spacing, num_targets, inputs)
+
 the two spectra for an arbitrary array geometry (a uniform circular array, a measured manifold), given as a steering table
 (also `music_pipeline.set_steering_table`):
 
@@ -37,6 +41,7 @@ no HIP device is usable.  There is no CPU fallback.
 """
 from ._lib import DoaError, LIB_PATH, last_error  # noqa: F401
 from .blocks import (autocorrelate, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, rootMUSIC_linear_array,  # noqa: F401
+                     esprit_linear_array,
                      MUSIC_array, capon_array, planar_steering_table, uca_positions,
                      music_pipeline, root_pipeline, root_music_pipeline, autocorrelate_sc16, music_pipeline_sc16,
                      root_music_pipeline_sc16, compass_mean, sim_source, set_internal_precision, get_internal_precision, device_count,

@@ -189,6 +189,13 @@ SIGNATURES = {
     "doa_capon_array_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_capon_array_items_total": (C.c_longlong, [_vp]),
     "doa_music_pipeline_set_steering_table": (C.c_int, [_vp, _vp, C.c_float, C.c_float]),
+    "doa_esprit_linear_array_create": (_vp, [C.c_float, C.c_int, C.c_int]),
+    "doa_esprit_linear_array_destroy": (None, [_vp]),
+    "doa_esprit_linear_array_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_esprit_linear_array_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_esprit_linear_array_work_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_esprit_linear_array_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_root_pipeline_set_estimator": (C.c_int, [_vp, C.c_int]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

@@ -46,6 +46,7 @@ def _opt_ptr(p) -> C.c_void_p:
 
 # estimators of music_pipeline (DOA_ESTIMATOR_MUSIC / DOA_ESTIMATOR_CAPON, include/doa_hip.h)
 _ESTIMATORS = {"music": 0, "capon": 1}
+_GRIDFREE = {"root_music": 0, "esprit": 1}
 
 # input sample formats of the stream-input blocks (DOA_SAMPLE_FC32 / DOA_SAMPLE_SC16, include/doa_hip.h)
 SC16_DEFAULT_SCALE = 2.0 ** -15
@@ -704,6 +705,60 @@ class rootMUSIC_linear_array(_Block):
         return ang, status
 
 
+class esprit_linear_array(_Block):
+    """doa.esprit_linear_array(norm_spacing, num_targets, inputs) — least-squares ESPRIT for a uniform linear array: the
+    angles from the eigenvalues of the num_targets x num_targets matrix that maps the signal subspace of rows 0..N-2 onto rows
+    1..N-1; no polynomial, no search, no unit-circle filter (definition: include/doa_hip.h).  Port 0: num_targets angles in
+    degrees, ascending, NaN last; port 1 (optional): int32 status, 0 = ok, 1 = not solvable, 2 = no usable count (counts
+    entries), 3 = the eigenvalue iteration reached its cap; a non-zero status gives an all-NaN item.
+    Not a block of the reference."""
+
+    _destroy = staticmethod(lib.doa_esprit_linear_array_destroy)
+
+    def __init__(self, norm_spacing, num_targets, inputs):
+        super().__init__()
+        self.norm_spacing, self.num_targets, self.num_ant_ele = float(norm_spacing), int(num_targets), int(inputs)
+        self._h = check_handle(lib.doa_esprit_linear_array_create(self.norm_spacing, self.num_targets, self.num_ant_ele),
+                               "esprit_linear_array")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_F32, self.num_targets), (_I32, 1)]
+
+    def _host_args(self, noutput_items, input_items, output_items):
+        n = int(noutput_items)
+        a = np.ascontiguousarray(input_items[0], dtype=_C64)
+        out = output_items[0]
+        status = output_items[1] if len(output_items) > 1 else None
+        assert a.size >= n * self.num_ant_ele ** 2
+        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.num_targets
+        if status is not None:
+            assert status.dtype == _I32 and status.flags.c_contiguous and status.size >= n
+        return n, a, out, _vp(status) if status is not None else C.c_void_p(0)
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        """output_items = [angles float32 [n, num_targets]] or [angles, status int32 [n]]."""
+        n, a, out, st = self._host_args(noutput_items, input_items, output_items)
+        return check(lib.doa_esprit_linear_array_work(self._h, n, _vp(a), _vp(out), st))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
+        return check(lib.doa_esprit_linear_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+                                                          _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+    def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
+        """work with a source count PER ITEM (int32 array) in place of num_targets, with the semantics of
+        rootMUSIC_linear_array.work_counts: items stay num_targets floats wide, the first count slots are
+        esprit_linear_array(norm_spacing, count, inputs)'s and the rest NaN; count 0: all NaN, status 0; a count outside
+        0..min(num_targets, inputs-1) (source_count's -1 included): all NaN, status 2."""
+        n, a, out, st = self._host_args(noutput_items, input_items, output_items)
+        c = np.ascontiguousarray(counts, dtype=_I32)
+        assert c.size >= n
+        return check(lib.doa_esprit_linear_array_work_counts(self._h, n, _vp(a), _vp(c), _vp(out), st))
+
+    def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
+        return check(lib.doa_esprit_linear_array_work_dev_counts(self._h, int(noutput_items), _opt_ptr(d_in_ptr),
+                                                                 _opt_ptr(d_counts_ptr), _opt_ptr(d_out_ptr),
+                                                                 _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+
 class calibrate_lin_array(_Block):
     """doa.calibrate_lin_array(norm_spacing, num_ant_ele, pilot_angle) — gr::sync_block, vlen N^2
     complex in, vlen N complex out (reference lib/calibrate_lin_array_impl.cc:46-75)."""
@@ -924,6 +979,7 @@ class root_pipeline(_StreamInput, _Block):
         self._h = check_handle(lib.doa_root_pipeline_create(self.inputs, self.snapshot_size, self.overlap_size, self.avg_method,
                                                             self.norm_spacing, self.num_targets, self.max_batch), "root_pipeline")
         self.subarray_size, self.forward_backward = 0, 0            # set_spatial_smoothing
+        self.estimator = "root_music"                               # set_estimator
         # as a flowgraph block (gr::doa::root_music_pipeline of the C++ shells): N complex streams in; out0 = angles
         self.in_sig = [(_C64, 1)] * self.inputs
         self.out_sig = [(_F32, self.num_targets)]
@@ -958,6 +1014,16 @@ class root_pipeline(_StreamInput, _Block):
         check(lib.doa_root_pipeline_set_spatial_smoothing(self._h, int(subarray_size), int(forward_backward)))
         self.subarray_size = int(subarray_size)
         self.forward_backward = int(forward_backward) if self.subarray_size else 0
+
+    def set_estimator(self, estimator) -> None:
+        """ "root_music" (the default) or "esprit": from the next work call on, in every entry, the eigen launch writes the
+        signal-subspace record and esprit_kernel takes the root finder's place (esprit_linear_array's definition and status
+        codes; work() raises DoaError(DOA_ERR_NUMERIC) for any non-zero status).  K1 and the covariance output are unchanged
+        (doa_root_pipeline_set_estimator)."""
+        if not isinstance(estimator, str) or estimator.lower() not in _GRIDFREE:
+            raise ValueError(f"unknown estimator {estimator!r} (root_music or esprit)")
+        check(lib.doa_root_pipeline_set_estimator(self._h, _GRIDFREE[estimator.lower()]))
+        self.estimator = estimator.lower()
 
     def inject_failure(self, chunk_index: int) -> None:
         """Test aid: the next work() / work_dev_batches() call fails in chunk / batch `chunk_index` (one-shot; -1 disarms)."""

@@ -698,6 +698,77 @@ DOA_HIP_API int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int nout
 DOA_HIP_API int doa_root_pipeline_set_spatial_smoothing(doa_root_pipeline_t *h, int subarray_size, int forward_backward);
 
 /* ---------------------------------------------------------------------------------------------
+ * esprit_linear_array — least-squares ESPRIT for a uniform linear array: the grid-free estimate
+ *   from the rotational invariance of the signal subspace; no polynomial, no search.  Not a block of the reference.
+ *
+ * The definition, one for every entry (tests/esprit_ref.py restates it in numpy):
+ *   input item      column-major N x N gr_complex; only the upper triangle is read, of the diagonal only the real part, as
+ *                   capon_lin_array reads it.  H = the Hermitian matrix these define.  All arithmetic in double;
+ *                   d = (double)(float)norm_spacing.
+ *   (w, V) = eigh(H), ascending, ranked by the eig_sym rule of the Jacobi kernels (ties: lower index first)
+ *   Es     = the eigenvectors of the M largest eigenvalues                            (N x M, orthonormal)
+ *   Es1    = rows 0 .. N-2 of Es,   Es2 = rows 1 .. N-1
+ *   gamma  = 1 - sum_k |Es[N-1, k]|^2                (the smallest eigenvalue of Es1^H Es1 = I - e e^H, e = Es[N-1, :]^H)
+ *   Psi    = (Es1^H Es1)^-1 Es1^H Es2                (M x M; evaluated as F + e (e^H F) / gamma, F = Es1^H Es2)
+ *   lambda_k = the eigenvalues of Psi                (M = 1: Psi itself; M = 2: the stable quadratic; M >= 3: Householder
+ *                                                     reduction to Hessenberg form, Wilkinson-shifted QR with deflation)
+ *   c_k    = atan2(Im lambda_k, Re lambda_k) / (2 pi d)
+ *   angle_k = (float)(180 / pi * acos(c_k)),  NaN when |c_k| > 1
+ *   output item     M floats, ascending, NaN last.  There is no unit-circle filter (ESPRIT's eigenvalues straddle the circle).
+ *                   With the steering a_n = exp(j 2 pi d cos(theta) (n - (N-1)/2)), a_{n+1} / a_n = exp(j 2 pi d cos(theta)):
+ *                   the angle map of rootMUSIC_linear_array.
+ *   status          int32 per item.  0 ok.  1 not solvable: trace(H) > 0 does not hold, an entry is not finite, or
+ *                   gamma > DOA_ESPRIT_GAMMA_MIN does not hold (the relative error of Psi grows like eps / gamma: at 2^-30 a
+ *                   double is left with float accuracy).  2 (counts entries): no usable count.  3: the eigenvalue iteration
+ *                   reached its cap of 30 M QR steps.  A non-zero status gives an all-NaN item; other items are not affected.
+ *   An item multiplied by a power of two gives the same bits (the Jacobi prescale is exact).  The result does not depend on
+ *   the basis of the signal subspace, so the device and numpy agree to rounding, not bit for bit.
+ *
+ * Two launches: the double Jacobi eigen stage (4 lanes per item for N <= 4, 8 for N <= 8, one wave for N <= 16) writes the
+ * SIGNAL-SUBSPACE RECORD -- all N eigenvectors as columns by descending eigenvalue, 2 N^2 doubles per item,
+ * [2 (k N + row)] = Re, [.. + 1] = Im of component `row` of the k-th vector -- and esprit_kernel reads its first M columns.
+ * Internal precision 64 only: a handle created while the process default is 32 returns DOA_ERR_UNSUPPORTED from its work
+ * entries.  create validates before the device is touched: 2 <= num_ant_ele <= DOA_MAX_ANT_ELE, 1 <= num_targets <
+ * num_ant_ele, 0 < norm_spacing <= 0.5.  status_out / d_status_out may be NULL.
+ * The _counts entries take one int32 m_i per item in place of num_targets W; items stay W floats wide, with the semantics
+ * of doa_rootMUSIC_linear_array_work_counts: 1 <= m_i <= min(W, num_ant_ele - 1): the first m_i slots are what
+ * esprit_linear_array(norm_spacing, m_i, num_ant_ele) writes, bit for bit, the others NaN; m_i == 0: all NaN, status 0; any
+ * other value (the -1 of source_count included): all NaN, status 2.  NULL counts: DOA_ERR_INVALID_ARG.
+ * --------------------------------------------------------------------------------------------- */
+#define DOA_ESPRIT_GAMMA_MIN (1.0 / 1073741824.0)   /* 2^-30, exact */
+typedef struct doa_esprit_linear_array doa_esprit_linear_array_t;
+
+DOA_HIP_API doa_esprit_linear_array_t *doa_esprit_linear_array_create(float norm_spacing, int num_targets, int num_ant_ele);
+DOA_HIP_API void doa_esprit_linear_array_destroy(doa_esprit_linear_array_t *h);
+DOA_HIP_API int doa_esprit_linear_array_work(doa_esprit_linear_array_t *h, int noutput_items, const void *cov_items,
+                                             void *angles_out, void *status_out);
+DOA_HIP_API int doa_esprit_linear_array_work_dev(doa_esprit_linear_array_t *h, int noutput_items, const void *d_cov_items,
+                                                 void *d_angles_out, void *d_status_out, void *hip_stream);
+DOA_HIP_API int doa_esprit_linear_array_work_counts(doa_esprit_linear_array_t *h, int noutput_items, const void *cov_items,
+                                                    const void *counts, void *angles_out, void *status_out);
+DOA_HIP_API int doa_esprit_linear_array_work_dev_counts(doa_esprit_linear_array_t *h, int noutput_items,
+                                                        const void *d_cov_items, const void *d_counts, void *d_angles_out,
+                                                        void *d_status_out, void *hip_stream);
+/* root_pipeline with ESPRIT in place of Root-MUSIC: a per-handle setting, taking effect from the next work call, honoured by
+ * work_dev, work_dev_batches, work, work_dev_auto and set_spatial_smoothing.  DOA_GRIDFREE_ROOT_MUSIC (the default) is the
+ * path described above, unchanged.  DOA_GRIDFREE_ESPRIT: K1 runs exactly as before (d_cov_out is bit-identical), then the
+ * eigen launch that writes the signal-subspace record (into the handle's workspace, one per lane), then esprit_kernel;
+ * d_status_out carries the statuses of esprit_linear_array, and the host entry returns DOA_ERR_NUMERIC if any item has a
+ * non-zero status.  work_dev_auto: K1, ONE estimating eigen launch that writes counts, eigenvalues and the record, the
+ * counted ESPRIT kernel.  With smoothing on, eigen stage and ESPRIT run on subarray_size x subarray_size items.  The
+ * outputs are bit-identical to the blocks chained by hand: autocorrelate -> [spatial_smooth ->] [source_count ->]
+ * esprit_linear_array[_counts] -- with one limit: for num_ant_ele (or subarray_size) <= 4 work_dev_auto's estimating launch is
+ * the 4-lanes-per-item Jacobi form while source_count runs one lane per item, a different sweep order, so d_eig_out agrees
+ * with source_count's eigenvalues to one float rounding, not guaranteed bit for bit (the tested shape is bit-identical), and
+ * -- an untested possibility -- a count could differ where the criterion is tied to that rounding; given the counts, angles
+ * and status are bit-identical.  Above 4 elements both are the same launch.
+ * Internal precision 32: DOA_ERR_UNSUPPORTED from the work entries while the mode is ESPRIT.
+ * A bad value returns DOA_ERR_INVALID_ARG and leaves the handle as it was. */
+#define DOA_GRIDFREE_ROOT_MUSIC 0
+#define DOA_GRIDFREE_ESPRIT 1
+DOA_HIP_API int doa_root_pipeline_set_estimator(doa_root_pipeline_t *h, int estimator);
+
+/* ---------------------------------------------------------------------------------------------
  * compass_mean — blocks.vector_to_streams(float, num_streams) + the averaging of doa.compass
  *   (reference python/compass.py:134-136: next_angle = numpy.mean(input_items[0]) over the items of
  *   one work call; wiring apps/run_MUSIC_lin_array_simulation.py:199,236-239).
