@@ -195,24 +195,19 @@ int launch_array_scan(const ArrayTable &t, int n_items, const void *d_full, void
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_MUSIC_array {
+#include "block_host.hpp"
+
+// what the two steering-table handles share (bits: the work entries need 64)
+struct ArrayBlock : doa::BlockBase {
     doa::ArrayTable tab;
-    int M = 0;
-    int bits = 64;   // the process default at create; the work entries need 64
-    int device = 0;
-    long long items_total = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out, d_full, d_q;
 };
-
-struct doa_capon_array {
-    doa::ArrayTable tab;
+struct doa_MUSIC_array : ArrayBlock {
+    int M = 0;
+};
+struct doa_capon_array : ArrayBlock {
     double loading = 0.0;
-    int bits = 64;
-    int device = 0;
-    long long items_total = 0;
-    hipStream_t stream = nullptr;
-    doa::DevBuf d_in, d_out, d_full, d_q, d_status;
+    doa::DevBuf d_status;
 };
 
 namespace {
@@ -238,17 +233,10 @@ int array_validate(const char *who, int num_ant_ele, int pspectrum_len, const do
     return DOA_OK;
 }
 
-template <class H> int array_work_args(const char *who, H *h, int n, const void *in, const void *out)
+int array_work_args(const char *who, const ArrayBlock *h, int n, std::initializer_list<const void *> required, int min_n = 0)
 {
-    if (!h || n < 0 || (n > 0 && (!in || !out))) {
-        doa::set_error("%s: bad arguments", who);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("%s: the steering-table scan needs internal precision 64 (handle is at %d)", who, h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    return DOA_OK;
+    if (int rc = doa::work_args(who, h, n, required, min_n); rc != DOA_OK) return rc;
+    return doa::need_bits64(who, h->bits, "the steering-table scan");
 }
 
 int capon_array_reserve(doa_capon_array *h, int n)
@@ -272,6 +260,28 @@ void unpack_full_records(const std::vector<double> &rec, int N, int n, double *o
             }
         }
     }
+}
+
+// the two debug entries: items up, the block's full records (front), the scan with its null spectrum, then the records
+// unpacked into matrix_out and the null spectrum down; either output may be NULL
+template <class Front>
+int array_debug(ArrayBlock *h, int n, const void *cov_items, void *matrix_out, void *null_spectrum_out, Front &&front)
+{
+    const int N = h->tab.N, P = h->tab.P;
+    const size_t sp_bytes = (size_t)n * P * sizeof(float);
+    const size_t full_bytes = (size_t)n * doa::full_record_len(N) * sizeof(double);
+    std::vector<double> rec(matrix_out ? full_bytes / sizeof(double) : 0);
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov_items, (size_t)n * N * N * sizeof(float2));
+    io.out(h->d_out, nullptr, sp_bytes);
+    io.out(h->d_q, null_spectrum_out, sp_bytes);
+    io.out(h->d_full, matrix_out ? rec.data() : nullptr, full_bytes);
+    int rc = io.status();
+    if (rc == DOA_OK) rc = front(h->stream);
+    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, h->d_out.p, h->d_q.p, h->stream);
+    rc = io.finish(rc == DOA_OK ? n : rc);
+    if (rc >= 0 && matrix_out) unpack_full_records(rec, N, n, static_cast<double *>(matrix_out));
+    return rc;
 }
 
 }  // namespace
@@ -319,30 +329,13 @@ doa_MUSIC_array_t *doa_MUSIC_array_create(int num_targets, int num_ant_ele, int 
         doa::set_error("MUSIC_array: need 0 < num_targets < num_ant_ele (got %d, %d)", num_targets, num_ant_ele);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_MUSIC_array();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->device = dev;
-    h->M = num_targets;
-    h->bits = doa::internal_precision_bits();
-    if (h->tab.build(num_ant_ele, pspectrum_len, steering) != DOA_OK ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        if (!*doa_last_error()) doa::set_error("MUSIC_array: device setup failed");
-        doa_MUSIC_array_destroy(h);
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_MUSIC_array>("MUSIC_array", [&](doa_MUSIC_array &h) {
+        h.M = num_targets;
+        return h.tab.build(num_ant_ele, pspectrum_len, steering);
+    });
 }
 
-void doa_MUSIC_array_destroy(doa_MUSIC_array_t *h)
-{
-    if (!h) return;
-    h->tab.release();
-    h->d_in.release(); h->d_out.release(); h->d_full.release(); h->d_q.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_MUSIC_array_destroy(doa_MUSIC_array_t *h) { doa::destroy_block(h); }
 
 long long doa_MUSIC_array_items_total(const doa_MUSIC_array_t *h) { return h ? h->items_total : 0; }
 
@@ -357,7 +350,7 @@ int doa_MUSIC_array_set_internal_precision(doa_MUSIC_array_t *h, int bits)
 int doa_MUSIC_array_work_dev(doa_MUSIC_array_t *h, int noutput_items, const void *d_cov_items, void *d_spectrum_out, void *hip_stream)
 {
     doa::clear_error();
-    if (int rc = array_work_args("MUSIC_array_work_dev", h, noutput_items, d_cov_items, d_spectrum_out); rc != DOA_OK) return rc;
+    if (int rc = array_work_args("MUSIC_array_work_dev", h, noutput_items, {d_cov_items, d_spectrum_out}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -373,54 +366,23 @@ int doa_MUSIC_array_work_dev(doa_MUSIC_array_t *h, int noutput_items, const void
 int doa_MUSIC_array_work(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out)
 {
     doa::clear_error();
-    if (int rc = array_work_args("MUSIC_array_work", h, noutput_items, cov_items, spectrum_out); rc != DOA_OK) return rc;
+    if (int rc = array_work_args("MUSIC_array_work", h, noutput_items, {cov_items, spectrum_out}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->tab.N, P = h->tab.P;
-    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_MUSIC_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(spectrum_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
+    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = doa_MUSIC_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
+    return io.finish(rc);
 }
 
 int doa_MUSIC_array_debug(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *projector_out, void *null_spectrum_out)
 {
     doa::clear_error();
-    if (!h || noutput_items <= 0 || !cov_items) {
-        doa::set_error("MUSIC_array_debug: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("MUSIC_array_debug: the steering-table scan needs internal precision 64 (handle is at %d)", h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->tab.N, P = h->tab.P, n = noutput_items;
-    const size_t in_bytes = (size_t)n * N * N * sizeof(float2);
-    const size_t sp_bytes = (size_t)n * P * sizeof(float);
-    const size_t full_bytes = (size_t)n * doa::full_record_len(N) * sizeof(double);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = h->d_q.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = h->d_full.reserve(full_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa::launch_music_evd_full(N, h->M, n, h->d_in.p, h->d_full.p, nullptr, h->stream);
-    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, h->d_out.p, h->d_q.p, h->stream);
-    if (rc != DOA_OK) return rc;
-    std::vector<double> rec(projector_out ? full_bytes / sizeof(double) : 0);
-    if (projector_out) DOA_HIP_TRY(hipMemcpyAsync(rec.data(), h->d_full.p, full_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (null_spectrum_out) DOA_HIP_TRY(hipMemcpyAsync(null_spectrum_out, h->d_q.p, sp_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (projector_out) unpack_full_records(rec, N, n, static_cast<double *>(projector_out));
-    return n;
+    if (int rc = array_work_args("MUSIC_array_debug", h, noutput_items, {cov_items}, 1); rc != DOA_OK) return rc;
+    return array_debug(h, noutput_items, cov_items, projector_out, null_spectrum_out, [&](hipStream_t st) {
+        return doa::launch_music_evd_full(h->tab.N, h->M, noutput_items, h->d_in.p, h->d_full.p, nullptr, st);
+    });
 }
 
 // ---- capon_array --------------------------------------------------------------------------------------------------------
@@ -432,30 +394,13 @@ doa_capon_array_t *doa_capon_array_create(int num_ant_ele, int pspectrum_len, co
         doa::set_error("capon_array: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_capon_array();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->device = dev;
-    h->loading = (double)diagonal_loading;
-    h->bits = doa::internal_precision_bits();
-    if (h->tab.build(num_ant_ele, pspectrum_len, steering) != DOA_OK ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        if (!*doa_last_error()) doa::set_error("capon_array: device setup failed");
-        doa_capon_array_destroy(h);
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_capon_array>("capon_array", [&](doa_capon_array &h) {
+        h.loading = (double)diagonal_loading;
+        return h.tab.build(num_ant_ele, pspectrum_len, steering);
+    });
 }
 
-void doa_capon_array_destroy(doa_capon_array_t *h)
-{
-    if (!h) return;
-    h->tab.release();
-    h->d_in.release(); h->d_out.release(); h->d_full.release(); h->d_q.release(); h->d_status.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_capon_array_destroy(doa_capon_array_t *h) { doa::destroy_block(h); }
 
 long long doa_capon_array_items_total(const doa_capon_array_t *h) { return h ? h->items_total : 0; }
 
@@ -463,7 +408,7 @@ int doa_capon_array_work_dev(doa_capon_array_t *h, int noutput_items, const void
                              void *d_status_out, void *hip_stream)
 {
     doa::clear_error();
-    if (int rc = array_work_args("capon_array_work_dev", h, noutput_items, d_cov_items, d_spectrum_out); rc != DOA_OK) return rc;
+    if (int rc = array_work_args("capon_array_work_dev", h, noutput_items, {d_cov_items, d_spectrum_out}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -483,57 +428,24 @@ int doa_capon_array_work_dev(doa_capon_array_t *h, int noutput_items, const void
 int doa_capon_array_work(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out, void *status_out)
 {
     doa::clear_error();
-    if (int rc = array_work_args("capon_array_work", h, noutput_items, cov_items, spectrum_out); rc != DOA_OK) return rc;
+    if (int rc = array_work_args("capon_array_work", h, noutput_items, {cov_items, spectrum_out}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->tab.N, P = h->tab.P;
-    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
-    const size_t st_bytes = (size_t)noutput_items * sizeof(int);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_status.reserve(st_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_capon_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->d_status.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(spectrum_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (status_out) DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, st_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
+    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
+    io.out(h->d_status, status_out, (size_t)noutput_items * sizeof(int));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = doa_capon_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->d_status.p, h->stream);
+    return io.finish(rc);
 }
 
 int doa_capon_array_debug(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *inverse_out, void *null_spectrum_out)
 {
     doa::clear_error();
-    if (!h || noutput_items <= 0 || !cov_items) {
-        doa::set_error("capon_array_debug: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("capon_array_debug: the steering-table scan needs internal precision 64 (handle is at %d)", h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->tab.N, P = h->tab.P, n = noutput_items;
-    const size_t in_bytes = (size_t)n * N * N * sizeof(float2);
-    const size_t sp_bytes = (size_t)n * P * sizeof(float);
-    const size_t full_bytes = (size_t)n * doa::full_record_len(N) * sizeof(double);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = h->d_q.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = capon_array_reserve(h, n);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa::launch_capon_inverse(N, n, h->d_in.p, h->loading, nullptr, nullptr, nullptr, nullptr, h->stream, h->d_full.p);
-    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, h->d_out.p, h->d_q.p, h->stream);
-    if (rc != DOA_OK) return rc;
-    std::vector<double> rec(inverse_out ? full_bytes / sizeof(double) : 0);
-    if (inverse_out) DOA_HIP_TRY(hipMemcpyAsync(rec.data(), h->d_full.p, full_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (null_spectrum_out) DOA_HIP_TRY(hipMemcpyAsync(null_spectrum_out, h->d_q.p, sp_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (inverse_out) unpack_full_records(rec, N, n, static_cast<double *>(inverse_out));
-    return n;
+    if (int rc = array_work_args("capon_array_debug", h, noutput_items, {cov_items}, 1); rc != DOA_OK) return rc;
+    return array_debug(h, noutput_items, cov_items, inverse_out, null_spectrum_out, [&](hipStream_t st) {
+        return doa::launch_capon_inverse(h->tab.N, noutput_items, h->d_in.p, h->loading, nullptr, nullptr, nullptr, nullptr, st, h->d_full.p);
+    });
 }
 
 }  // extern "C"

@@ -394,27 +394,18 @@ int launch_capon_invalid_rows(int P, int M, int n_items, const void *d_status, v
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_capon_lin_array {
+#include "block_host.hpp"
+
+struct doa_capon_lin_array : doa::BlockBase {          // bits: the work entries need 64
     doa::MusicTables tab;
     double loading = 0.0;
-    int bits = 64;   // the process default at create; the work entries need 64
-    int device = 0;
-    long long items_total = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out, d_coef, d_cheb, d_status, d_w, d_q;
 };
 
-static int capon_work_args(const char *who, doa_capon_lin_array_t *h, int n, const void *in, const void *out)
+static int capon_work_args(const char *who, doa_capon_lin_array_t *h, int n, std::initializer_list<const void *> required, int min_n = 0)
 {
-    if (!h || n < 0 || (n > 0 && (!in || !out))) {
-        doa::set_error("%s: bad arguments", who);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("%s: the Capon inverse needs internal precision 64 (handle is at %d)", who, h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    return DOA_OK;
+    if (int rc = doa::work_args(who, h, n, required, min_n); rc != DOA_OK) return rc;
+    return doa::need_bits64(who, h->bits, "the Capon inverse");
 }
 
 static int capon_reserve_records(doa_capon_lin_array_t *h, int n)
@@ -446,31 +437,13 @@ doa_capon_lin_array_t *doa_capon_lin_array_create(float norm_spacing, int num_an
         doa::set_error("capon_lin_array: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_capon_lin_array();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->device = dev;
-    h->loading = (double)diagonal_loading;
-    h->bits = doa::internal_precision_bits();
-    // the scan's tables; their M is unused by the scan
-    if (h->tab.build(norm_spacing, 1, num_ant_ele, pspectrum_len) != DOA_OK ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        if (!*doa_last_error()) doa::set_error("capon_lin_array: device setup failed");
-        doa_capon_lin_array_destroy(h);
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_capon_lin_array>("capon_lin_array", [&](doa_capon_lin_array &h) {
+        h.loading = (double)diagonal_loading;
+        return h.tab.build(norm_spacing, 1, num_ant_ele, pspectrum_len);      // the scan's tables; their M is unused by the scan
+    });
 }
 
-void doa_capon_lin_array_destroy(doa_capon_lin_array_t *h)
-{
-    if (!h) return;
-    h->tab.release();
-    h->d_in.release(); h->d_out.release(); h->d_coef.release(); h->d_cheb.release(); h->d_status.release(); h->d_w.release(); h->d_q.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_capon_lin_array_destroy(doa_capon_lin_array_t *h) { doa::destroy_block(h); }
 
 long long doa_capon_lin_array_items_total(const doa_capon_lin_array_t *h) { return h ? h->items_total : 0; }
 
@@ -478,7 +451,7 @@ int doa_capon_lin_array_work_dev(doa_capon_lin_array_t *h, int noutput_items, co
                                  void *d_status_out, void *hip_stream)
 {
     doa::clear_error();
-    if (int rc = capon_work_args("capon_lin_array_work_dev", h, noutput_items, d_cov_items, d_spectrum_out); rc != DOA_OK) return rc;
+    if (int rc = capon_work_args("capon_lin_array_work_dev", h, noutput_items, {d_cov_items, d_spectrum_out}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -500,58 +473,37 @@ int doa_capon_lin_array_work_dev(doa_capon_lin_array_t *h, int noutput_items, co
 int doa_capon_lin_array_work(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out, void *status_out)
 {
     doa::clear_error();
-    if (int rc = capon_work_args("capon_lin_array_work", h, noutput_items, cov_items, spectrum_out); rc != DOA_OK) return rc;
+    if (int rc = capon_work_args("capon_lin_array_work", h, noutput_items, {cov_items, spectrum_out}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->tab.N, P = h->tab.P;
-    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
-    const size_t st_bytes = (size_t)noutput_items * sizeof(int);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_status.reserve(st_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_capon_lin_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->d_status.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(spectrum_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (status_out) DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, st_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
+    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
+    io.out(h->d_status, status_out, (size_t)noutput_items * sizeof(int));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = doa_capon_lin_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->d_status.p, h->stream);
+    return io.finish(rc);
 }
 
 int doa_capon_lin_array_debug(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items, void *inverse_out,
                               void *null_spectrum_out)
 {
     doa::clear_error();
-    if (!h || noutput_items <= 0 || !cov_items) {
-        doa::set_error("capon_lin_array_debug: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("capon_lin_array_debug: the Capon inverse needs internal precision 64 (handle is at %d)", h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    if (int rc = capon_work_args("capon_lin_array_debug", h, noutput_items, {cov_items}, 1); rc != DOA_OK) return rc;
     const int N = h->tab.N, P = h->tab.P, n = noutput_items;
     const size_t in_bytes = (size_t)n * N * N * sizeof(float2);
     const size_t sp_bytes = (size_t)n * P * sizeof(float);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = h->d_q.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = h->d_w.reserve(in_bytes);
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov_items, in_bytes);
+    io.out(h->d_out, nullptr, sp_bytes);
+    io.out(h->d_q, null_spectrum_out, sp_bytes);
+    io.out(h->d_w, inverse_out, in_bytes);
+    int rc = io.status();
     if (rc == DOA_OK) rc = capon_reserve_records(h, n);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa::launch_capon_inverse(N, n, h->d_in.p, h->loading, h->d_coef.p, doa::music_uses_cheb(N, 64) ? h->d_cheb.p : nullptr,
-                                   h->d_w.p, nullptr, h->stream);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_scan(h->tab, 64, n, h->d_coef.p, h->d_out.p, h->d_q.p, h->stream);
-    if (rc != DOA_OK) return rc;
-    if (inverse_out) DOA_HIP_TRY(hipMemcpyAsync(inverse_out, h->d_w.p, in_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (null_spectrum_out) DOA_HIP_TRY(hipMemcpyAsync(null_spectrum_out, h->d_q.p, sp_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return n;
+    if (rc == DOA_OK)
+        rc = doa::launch_capon_inverse(N, n, h->d_in.p, h->loading, h->d_coef.p, doa::music_uses_cheb(N, 64) ? h->d_cheb.p : nullptr,
+                                       h->d_w.p, nullptr, h->stream);
+    if (rc == DOA_OK) rc = doa::launch_music_scan(h->tab, 64, n, h->d_coef.p, h->d_out.p, h->d_q.p, h->stream);
+    return io.finish(rc == DOA_OK ? n : rc);
 }
 
 }  // extern "C"

@@ -39,9 +39,18 @@ int bind_device(int device);
 int cu_count();
 
 // ---- grow-only device / pinned-host buffers ----------------------------------------------------
+// Each owns its allocation: freed by release() (idempotent) or with the object; movable, not copyable.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int reserve(size_t bytes);  // DOA_OK or error; keeps contents only if no growth was needed
     void release();
     template <class T> T *as() const { return static_cast<T *>(p); }
@@ -49,6 +58,14 @@ struct DevBuf {
 struct PinnedBuf {
     void *p = nullptr;
     size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~PinnedBuf() { release(); }
     int reserve(size_t bytes);
     void release();
     template <class T> T *as() const { return static_cast<T *>(p); }

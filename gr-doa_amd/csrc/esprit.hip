@@ -346,27 +346,19 @@ int launch_esprit(int N, int W, float norm_spacing, int n_items, const void *d_R
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_esprit_linear_array {
+#include "block_host.hpp"
+
+struct doa_esprit_linear_array : doa::BlockBase {      // bits: the work entries need 64
     float norm_spacing = 0.f;
     int M = 0, N = 0;
-    int bits = 64;   // the process default at create; the work entries need 64
-    int device = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out, d_rec, d_status, d_counts;
 };
 
 static int esprit_work_args(const char *who, doa_esprit_linear_array_t *h, int n, const void *in, const void *out, bool counted,
                             const void *counts)
 {
-    if (!h || n < 0 || (n > 0 && (!in || !out || (counted && !counts)))) {
-        doa::set_error("%s: bad arguments", who);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("%s: ESPRIT needs internal precision 64 (handle is at %d)", who, h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    return DOA_OK;
+    if (int rc = doa::work_args(who, h, n, {in, out, counted ? counts : in}); rc != DOA_OK) return rc;
+    return doa::need_bits64(who, h->bits, "ESPRIT");
 }
 
 // eigen launch with the record, then esprit_kernel
@@ -383,23 +375,14 @@ static int esprit_run_dev(doa_esprit_linear_array_t *h, int n, const void *d_cov
 
 static int esprit_run_host(doa_esprit_linear_array_t *h, int n, const void *cov, const void *counts, void *angles, void *status)
 {
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t in_bytes = (size_t)n * h->N * h->N * sizeof(float2);
-    const size_t out_bytes = (size_t)n * h->M * sizeof(float);
-    const size_t st_bytes = (size_t)n * sizeof(int);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_status.reserve(st_bytes);
-    if (rc == DOA_OK && counts) rc = h->d_counts.reserve(st_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov, in_bytes, hipMemcpyHostToDevice, h->stream));
-    if (counts) DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, st_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = esprit_run_dev(h, n, h->d_in.p, counts ? h->d_counts.p : nullptr, h->d_out.p, h->d_status.p, h->stream);
-    if (rc < 0) { (void)hipStreamSynchronize(h->stream); return rc; }
-    DOA_HIP_TRY(hipMemcpyAsync(angles, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (status) DOA_HIP_TRY(hipMemcpyAsync(status, h->d_status.p, st_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return n;
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov, (size_t)n * h->N * h->N * sizeof(float2));
+    if (counts) io.in(h->d_counts, counts, (size_t)n * sizeof(int));
+    io.out(h->d_out, angles, (size_t)n * h->M * sizeof(float));
+    io.out(h->d_status, status, (size_t)n * sizeof(int));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = esprit_run_dev(h, n, h->d_in.p, counts ? h->d_counts.p : nullptr, h->d_out.p, h->d_status.p, h->stream);
+    return io.finish(rc);
 }
 
 extern "C" {
@@ -419,27 +402,13 @@ doa_esprit_linear_array_t *doa_esprit_linear_array_create(float norm_spacing, in
         doa::set_error("esprit_linear_array: need 0 < norm_spacing <= 0.5 (got %g)", (double)norm_spacing);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_esprit_linear_array();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->norm_spacing = norm_spacing; h->M = num_targets; h->N = num_ant_ele; h->device = dev;
-    h->bits = doa::internal_precision_bits();
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("esprit_linear_array: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_esprit_linear_array>("esprit_linear_array", [&](doa_esprit_linear_array &h) {
+        h.norm_spacing = norm_spacing; h.M = num_targets; h.N = num_ant_ele;
+        return DOA_OK;
+    });
 }
 
-void doa_esprit_linear_array_destroy(doa_esprit_linear_array_t *h)
-{
-    if (!h) return;
-    h->d_in.release(); h->d_out.release(); h->d_rec.release(); h->d_status.release(); h->d_counts.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_esprit_linear_array_destroy(doa_esprit_linear_array_t *h) { doa::destroy_block(h); }
 
 int doa_esprit_linear_array_work_dev(doa_esprit_linear_array_t *h, int noutput_items, const void *d_cov_items, void *d_angles_out,
                                      void *d_status_out, void *hip_stream)

@@ -368,12 +368,28 @@ bool find_local_max_fast_ok(int L, const void *d_in)
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_find_local_max {
+#include "block_host.hpp"
+
+struct doa_find_local_max : doa::BlockBase {
     doa::PeakTables tab;
-    int device = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out0, d_out1, d_scratch, d_counts;
 };
+
+// spectra (and per-item counts, or NULL) up, work_dev / work_dev_counts, both outputs down
+static int find_local_max_host(doa_find_local_max_t *h, int n, const void *in, const void *counts, void *out0, void *out1)
+{
+    const size_t out_bytes = (size_t)n * h->tab.M * sizeof(float);
+    doa::HostCall io(*h);
+    io.in(h->d_in, in, (size_t)n * h->tab.L * sizeof(float));
+    if (counts) io.in(h->d_counts, counts, (size_t)n * sizeof(int));
+    io.out(h->d_out0, out0, out_bytes);
+    io.out(h->d_out1, out1, out_bytes);
+    int rc = io.status();
+    if (rc == DOA_OK)
+        rc = counts ? doa_find_local_max_work_dev_counts(h, n, h->d_in.p, h->d_counts.p, h->d_out0.p, h->d_out1.p, h->stream)
+                    : doa_find_local_max_work_dev(h, n, h->d_in.p, h->d_out0.p, h->d_out1.p, h->stream);
+    return io.finish(rc);
+}
 
 extern "C" {
 
@@ -390,37 +406,19 @@ doa_find_local_max_t *doa_find_local_max_create(int num_max_vals, int vector_len
         doa::set_error("find_local_max: num_max_vals=%d exceeds DOA_MAX_PEAKS=%d", num_max_vals, DOA_MAX_PEAKS);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_find_local_max();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->device = dev;
-    if (h->tab.build(num_max_vals, vector_len, x_min, x_max) != DOA_OK ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        if (!*doa_last_error()) doa::set_error("find_local_max: device setup failed");
-        doa_find_local_max_destroy(h);
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_find_local_max>("find_local_max", [&](doa_find_local_max &h) {
+        return h.tab.build(num_max_vals, vector_len, x_min, x_max);
+    });
 }
 
-void doa_find_local_max_destroy(doa_find_local_max_t *h)
-{
-    if (!h) return;
-    h->tab.release();
-    h->d_in.release(); h->d_out0.release(); h->d_out1.release(); h->d_scratch.release(); h->d_counts.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_find_local_max_destroy(doa_find_local_max_t *h) { doa::destroy_block(h); }
 
 int doa_find_local_max_work_dev(doa_find_local_max_t *h, int noutput_items, const void *d_input_items0,
                                 void *d_output_items0, void *d_output_items1, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_input_items0 || !d_output_items0 || !d_output_items1))) {
-        doa::set_error("find_local_max_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("find_local_max_work_dev", h, noutput_items, {d_input_items0, d_output_items0, d_output_items1}); rc != DOA_OK)
+        return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -440,36 +438,18 @@ int doa_find_local_max_work(doa_find_local_max_t *h, int noutput_items, const vo
                             void *output_items1)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!input_items0 || !output_items0 || !output_items1))) {
-        doa::set_error("find_local_max_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("find_local_max_work", h, noutput_items, {input_items0, output_items0, output_items1}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t in_bytes = (size_t)noutput_items * h->tab.L * sizeof(float);
-    const size_t out_bytes = (size_t)noutput_items * h->tab.M * sizeof(float);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out0.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_out1.reserve(out_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_find_local_max_work_dev(h, noutput_items, h->d_in.p, h->d_out0.p, h->d_out1.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out0.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(output_items1, h->d_out1.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    return find_local_max_host(h, noutput_items, input_items0, nullptr, output_items0, output_items1);
 }
 
 int doa_find_local_max_work_dev_counts(doa_find_local_max_t *h, int noutput_items, const void *d_input_items0,
                                        const void *d_counts, void *d_output_items0, void *d_output_items1, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 ||
-        (noutput_items > 0 && (!d_input_items0 || !d_counts || !d_output_items0 || !d_output_items1))) {
-        doa::set_error("find_local_max_work_dev_counts: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("find_local_max_work_dev_counts", h, noutput_items, {d_input_items0, d_counts, d_output_items0, d_output_items1});
+        rc != DOA_OK)
+        return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -489,28 +469,10 @@ int doa_find_local_max_work_counts(doa_find_local_max_t *h, int noutput_items, c
                                    void *output_items0, void *output_items1)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!input_items0 || !counts || !output_items0 || !output_items1))) {
-        doa::set_error("find_local_max_work_counts: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("find_local_max_work_counts", h, noutput_items, {input_items0, counts, output_items0, output_items1}); rc != DOA_OK)
+        return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t in_bytes = (size_t)noutput_items * h->tab.L * sizeof(float);
-    const size_t out_bytes = (size_t)noutput_items * h->tab.M * sizeof(float);
-    const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out0.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_out1.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_find_local_max_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out0.p, h->d_out1.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out0.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(output_items1, h->d_out1.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    return find_local_max_host(h, noutput_items, input_items0, counts, output_items0, output_items1);
 }
 
 }  // extern "C"

@@ -142,12 +142,10 @@ int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, v
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_MUSIC_lin_array {
+#include "block_host.hpp"
+
+struct doa_MUSIC_lin_array : doa::BlockBase {
     doa::MusicTables tab;
-    int bits = 64;   // internal precision of EVD + scan (doa_set_internal_precision)
-    int device = 0;
-    long long items_total = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out, d_coef, d_pn, d_q, d_cheb, d_counts;
 };
 
@@ -170,6 +168,13 @@ static int music_validate(const char *who, float norm_spacing, int num_targets, 
     return DOA_OK;
 }
 
+// checks of the per-item-count entries
+static int music_counts_args(const char *who, doa_MUSIC_lin_array_t *h, int n, const void *cov, const void *counts, const void *out)
+{
+    if (int rc = doa::work_args(who, h, n, {cov, counts, out}); rc != DOA_OK) return rc;
+    return doa::need_bits64(who, h->bits, "per-item counts");
+}
+
 extern "C" {
 
 doa_MUSIC_lin_array_t *doa_MUSIC_lin_array_create(float norm_spacing, int num_targets, int num_ant_ele,
@@ -181,29 +186,12 @@ doa_MUSIC_lin_array_t *doa_MUSIC_lin_array_create(float norm_spacing, int num_ta
         doa::set_error("MUSIC_lin_array: pspectrum_len must be > 0 (got %d)", pspectrum_len);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_MUSIC_lin_array();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->device = dev;
-    h->bits = doa::internal_precision_bits();
-    if (h->tab.build(norm_spacing, num_targets, num_ant_ele, pspectrum_len) != DOA_OK ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        if (!*doa_last_error()) doa::set_error("MUSIC_lin_array: device setup failed");
-        doa_MUSIC_lin_array_destroy(h);
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_MUSIC_lin_array>("MUSIC_lin_array", [&](doa_MUSIC_lin_array &h) {
+        return h.tab.build(norm_spacing, num_targets, num_ant_ele, pspectrum_len);
+    });
 }
 
-void doa_MUSIC_lin_array_destroy(doa_MUSIC_lin_array_t *h)
-{
-    if (!h) return;
-    h->tab.release();
-    h->d_in.release(); h->d_out.release(); h->d_coef.release(); h->d_pn.release(); h->d_q.release(); h->d_cheb.release(); h->d_counts.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_MUSIC_lin_array_destroy(doa_MUSIC_lin_array_t *h) { doa::destroy_block(h); }
 
 long long doa_MUSIC_lin_array_items_total(const doa_MUSIC_lin_array_t *h) { return h ? h->items_total : 0; }
 
@@ -211,10 +199,7 @@ int doa_MUSIC_lin_array_work_dev(doa_MUSIC_lin_array_t *h, int noutput_items, co
                                  void *d_output_items0, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_input_items0 || !d_output_items0))) {
-        doa::set_error("MUSIC_lin_array_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("MUSIC_lin_array_work_dev", h, noutput_items, {d_input_items0, d_output_items0}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -238,38 +223,22 @@ int doa_MUSIC_lin_array_work(doa_MUSIC_lin_array_t *h, int noutput_items, const 
                              void *output_items0)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!input_items0 || !output_items0))) {
-        doa::set_error("MUSIC_lin_array_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("MUSIC_lin_array_work", h, noutput_items, {input_items0, output_items0}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->tab.N, P = h->tab.P;
-    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_MUSIC_lin_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    doa::HostCall io(*h);
+    io.in(h->d_in, input_items0, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
+    io.out(h->d_out, output_items0, (size_t)noutput_items * h->tab.P * sizeof(float));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = doa_MUSIC_lin_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
+    return io.finish(rc);
 }
 
 int doa_MUSIC_lin_array_work_dev_counts(doa_MUSIC_lin_array_t *h, int noutput_items, const void *d_cov_items,
                                         const void *d_counts, void *d_spectrum_out, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_cov_items || !d_counts || !d_spectrum_out))) {
-        doa::set_error("MUSIC_lin_array_work_dev_counts: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("MUSIC_lin_array_work_dev_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
+    if (int rc = music_counts_args("MUSIC_lin_array_work_dev_counts", h, noutput_items, d_cov_items, d_counts, d_spectrum_out); rc != DOA_OK)
+        return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -293,64 +262,39 @@ int doa_MUSIC_lin_array_work_counts(doa_MUSIC_lin_array_t *h, int noutput_items,
                                     void *spectrum_out)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!cov_items || !counts || !spectrum_out))) {
-        doa::set_error("MUSIC_lin_array_work_counts: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("MUSIC_lin_array_work_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
+    if (int rc = music_counts_args("MUSIC_lin_array_work_counts", h, noutput_items, cov_items, counts, spectrum_out); rc != DOA_OK)
+        return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int N = h->tab.N, P = h->tab.P;
-    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * P * sizeof(float);
-    const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_MUSIC_lin_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(spectrum_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
+    io.in(h->d_counts, counts, (size_t)noutput_items * sizeof(int));
+    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = doa_MUSIC_lin_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, h->stream);
+    return io.finish(rc);
 }
 
 int doa_MUSIC_lin_array_debug(doa_MUSIC_lin_array_t *h, int noutput_items, const void *input_items0,
                               void *projector_out, void *null_spectrum_out)
 {
     doa::clear_error();
-    if (!h || noutput_items <= 0 || !input_items0) {
-        doa::set_error("MUSIC_lin_array_debug: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    if (int rc = doa::work_args("MUSIC_lin_array_debug", h, noutput_items, {input_items0}, 1); rc != DOA_OK) return rc;
     const int N = h->tab.N, P = h->tab.P;
     const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
     const size_t sp_bytes = (size_t)noutput_items * P * sizeof(float);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = h->d_q.reserve(sp_bytes);
-    if (rc == DOA_OK) rc = h->d_pn.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(N) * sizeof(double));
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
+    doa::HostCall io(*h);
+    io.in(h->d_in, input_items0, in_bytes);
+    io.out(h->d_out, nullptr, sp_bytes);
+    io.out(h->d_q, null_spectrum_out, sp_bytes);
+    io.out(h->d_pn, projector_out, in_bytes);
+    io.out(h->d_coef, nullptr, (size_t)noutput_items * doa::coef_stride(N) * sizeof(double));
+    int rc = io.status();
     const bool dbl = (h->bits == 64);
-    rc = doa::launch_music_evd(N, h->tab.M, noutput_items, h->d_in.p, dbl ? nullptr : h->d_coef.p,
-                               dbl ? h->d_coef.p : nullptr, h->d_pn.p, h->bits, h->stream);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_scan(h->tab, h->bits, noutput_items, h->d_coef.p, h->d_out.p, h->d_q.p, h->stream);
-    if (rc != DOA_OK) return rc;
-    if (projector_out)
-        DOA_HIP_TRY(hipMemcpyAsync(projector_out, h->d_pn.p, in_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (null_spectrum_out)
-        DOA_HIP_TRY(hipMemcpyAsync(null_spectrum_out, h->d_q.p, sp_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    if (rc == DOA_OK)
+        rc = doa::launch_music_evd(N, h->tab.M, noutput_items, h->d_in.p, dbl ? nullptr : h->d_coef.p,
+                                   dbl ? h->d_coef.p : nullptr, h->d_pn.p, h->bits, h->stream);
+    if (rc == DOA_OK) rc = doa::launch_music_scan(h->tab, h->bits, noutput_items, h->d_coef.p, h->d_out.p, h->d_q.p, h->stream);
+    return io.finish(rc == DOA_OK ? noutput_items : rc);
 }
 
 long long doa_hip_evd_fallback_count(int reset)

@@ -334,7 +334,7 @@ int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double 
         doa::PeakTables axis;
         if (int rc = axis.build(M, P, 0.0f, 180.0f); rc != DOA_OK) { axis.release(); return rc; }
         h->peaks.release();
-        h->peaks = axis;
+        h->peaks = std::move(axis);
         h->has_table = false;
         return DOA_OK;
     }
@@ -360,7 +360,7 @@ int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double 
     if (rc == DOA_OK) rc = h->d_full.reserve((size_t)h->max_batch * doa::full_record_len(N) * sizeof(double));
     if (rc != DOA_OK) { table.release(); axis.release(); return rc; }
     h->array.release(); h->peaks.release();
-    h->array = table; h->peaks = axis;
+    h->array = std::move(table); h->peaks = std::move(axis);
     h->has_table = true;
     return DOA_OK;
 }

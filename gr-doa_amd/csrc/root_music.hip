@@ -460,15 +460,34 @@ int launch_root_select_counts(int N, int W, float norm_spacing, int n_items, con
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_rootMUSIC_linear_array {
+#include "block_host.hpp"
+
+struct doa_rootMUSIC_linear_array : doa::BlockBase {
     float norm_spacing = 0.f;
     int M = 0, N = 0;
-    int bits = 64;
-    int device = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out, d_coef, d_status, d_roots, d_counts;
     doa::PinnedBuf h_status;
 };
+
+// the host entries' status scan after the synchronise.  With per-item counts, status 2 (no usable count) is what the
+// caller asked for, not an error
+static int root_status_scan(const doa_rootMUSIC_linear_array *h, int n, bool counted)
+{
+    const int *stt = h->h_status.as<int>();
+    for (int i = 0; i < n; i++)
+        if (counted ? stt[i] == 1 : stt[i] != 0) {
+            doa::set_error("rootMUSIC_linear_array: item %d has no root strictly inside the unit circle "
+                           "(the reference raises in arma::index_min here)", i);
+            return DOA_ERR_NUMERIC;
+        }
+    return n;
+}
+
+static int root_counts_args(const char *who, doa_rootMUSIC_linear_array_t *h, int n, const void *cov, const void *counts, const void *out)
+{
+    if (int rc = doa::work_args(who, h, n, {cov, counts, out}); rc != DOA_OK) return rc;
+    return doa::need_bits64(who, h->bits, "per-item counts");
+}
 
 extern "C" {
 
@@ -489,38 +508,19 @@ doa_rootMUSIC_linear_array_t *doa_rootMUSIC_linear_array_create(float norm_spaci
                        num_ant_ele, num_targets, DOA_MAX_ANT_ELE, DOA_MAX_PEAKS);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_rootMUSIC_linear_array();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->norm_spacing = norm_spacing; h->M = num_targets; h->N = num_ant_ele; h->device = dev;
-    h->bits = doa::internal_precision_bits();
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("rootMUSIC_linear_array: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_rootMUSIC_linear_array>("rootMUSIC_linear_array", [&](doa_rootMUSIC_linear_array &h) {
+        h.norm_spacing = norm_spacing; h.M = num_targets; h.N = num_ant_ele;
+        return DOA_OK;
+    });
 }
 
-void doa_rootMUSIC_linear_array_destroy(doa_rootMUSIC_linear_array_t *h)
-{
-    if (!h) return;
-    h->d_in.release(); h->d_out.release(); h->d_coef.release(); h->d_status.release(); h->d_roots.release();
-    h->d_counts.release();
-    h->h_status.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_rootMUSIC_linear_array_destroy(doa_rootMUSIC_linear_array_t *h) { doa::destroy_block(h); }
 
 int doa_rootMUSIC_linear_array_work_dev(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *d_input_items0,
                                         void *d_output_items0, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_input_items0 || !d_output_items0))) {
-        doa::set_error("rootMUSIC_linear_array_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("rootMUSIC_linear_array_work_dev", h, noutput_items, {d_input_items0, d_output_items0}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -538,47 +538,28 @@ int doa_rootMUSIC_linear_array_work(doa_rootMUSIC_linear_array_t *h, int noutput
                                     void *output_items0)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!input_items0 || !output_items0))) {
-        doa::set_error("rootMUSIC_linear_array_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("rootMUSIC_linear_array_work", h, noutput_items, {input_items0, output_items0}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t in_bytes = (size_t)noutput_items * h->N * h->N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * h->M * sizeof(float);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->h_status.reserve((size_t)noutput_items * sizeof(int));
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_rootMUSIC_linear_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(h->h_status.p, h->d_status.p, (size_t)noutput_items * sizeof(int),
-                               hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    const int *stt = h->h_status.as<int>();
-    for (int i = 0; i < noutput_items; i++)
-        if (stt[i] != 0) {
-            doa::set_error("rootMUSIC_linear_array: item %d has no root strictly inside the unit circle "
-                           "(the reference raises in arma::index_min here)", i);
-            return DOA_ERR_NUMERIC;
-        }
-    return noutput_items;
+    const size_t st_bytes = (size_t)noutput_items * sizeof(int);
+    doa::HostCall io(*h);
+    int rc = io.status();
+    if (rc == DOA_OK) rc = h->h_status.reserve(st_bytes);
+    if (rc != DOA_OK) return rc;                         // nothing is queued yet
+    io.in(h->d_in, input_items0, (size_t)noutput_items * h->N * h->N * sizeof(float2));
+    io.out(h->d_out, output_items0, (size_t)noutput_items * h->M * sizeof(float));
+    io.out(h->d_status, h->h_status.p, st_bytes);
+    rc = io.status();
+    if (rc == DOA_OK) rc = doa_rootMUSIC_linear_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
+    rc = io.finish(rc);
+    return rc < 0 ? rc : root_status_scan(h, noutput_items, false);
 }
 
 int doa_rootMUSIC_linear_array_work_dev_counts(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *d_cov_items,
                                                const void *d_counts, void *d_angles_out, int *d_status_out, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_cov_items || !d_counts || !d_angles_out))) {
-        doa::set_error("rootMUSIC_linear_array_work_dev_counts: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("rootMUSIC_linear_array_work_dev_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
+    if (int rc = root_counts_args("rootMUSIC_linear_array_work_dev_counts", h, noutput_items, d_cov_items, d_counts, d_angles_out); rc != DOA_OK)
+        return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -598,132 +579,77 @@ int doa_rootMUSIC_linear_array_work_counts(doa_rootMUSIC_linear_array_t *h, int 
                                            const void *counts, void *angles_out)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!cov_items || !counts || !angles_out))) {
-        doa::set_error("rootMUSIC_linear_array_work_counts: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (h->bits != 64) {
-        doa::set_error("rootMUSIC_linear_array_work_counts: per-item counts need internal precision 64 (handle is at %d)", h->bits);
-        return DOA_ERR_UNSUPPORTED;
-    }
+    if (int rc = root_counts_args("rootMUSIC_linear_array_work_counts", h, noutput_items, cov_items, counts, angles_out); rc != DOA_OK)
+        return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t in_bytes = (size_t)noutput_items * h->N * h->N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * h->M * sizeof(float);
     const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
-    if (rc == DOA_OK) rc = h->d_status.reserve(cnt_bytes);
+    doa::HostCall io(*h);
+    int rc = io.status();
     if (rc == DOA_OK) rc = h->h_status.reserve(cnt_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_rootMUSIC_linear_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, nullptr, h->stream);
-    if (rc < 0) { (void)hipStreamSynchronize(h->stream); return rc; }
-    DOA_HIP_TRY(hipMemcpyAsync(angles_out, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(h->h_status.p, h->d_status.p, cnt_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    // status 2 (no usable count) is what the caller asked for, not an error
-    const int *stt = h->h_status.as<int>();
-    for (int i = 0; i < noutput_items; i++)
-        if (stt[i] == 1) {
-            doa::set_error("rootMUSIC_linear_array: item %d has no root strictly inside the unit circle "
-                           "(the reference raises in arma::index_min here)", i);
-            return DOA_ERR_NUMERIC;
-        }
-    return noutput_items;
+    if (rc != DOA_OK) return rc;                         // nothing is queued yet
+    io.in(h->d_in, cov_items, (size_t)noutput_items * h->N * h->N * sizeof(float2));
+    io.in(h->d_counts, counts, cnt_bytes);
+    io.out(h->d_out, angles_out, (size_t)noutput_items * h->M * sizeof(float));
+    io.out(h->d_status, h->h_status.p, cnt_bytes);
+    rc = io.status();
+    if (rc == DOA_OK)
+        rc = doa_rootMUSIC_linear_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, nullptr, h->stream);
+    rc = io.finish(rc);
+    return rc < 0 ? rc : root_status_scan(h, noutput_items, true);
 }
 
 int doa_rootMUSIC_linear_array_debug(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *input_items0,
                                      void *output_items0, void *roots_out, int *status_out)
 {
     doa::clear_error();
-    if (!h || noutput_items <= 0 || !input_items0 || !output_items0) {
-        doa::set_error("rootMUSIC_linear_array_debug: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int D = 2 * h->N - 2;
-    const size_t in_bytes = (size_t)noutput_items * h->N * h->N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * h->M * sizeof(float);
-    const size_t root_bytes = (size_t)noutput_items * D * sizeof(double2);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_roots.reserve(root_bytes);
-    if (rc == DOA_OK) rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
-    if (rc == DOA_OK) rc = h->d_status.reserve((size_t)noutput_items * sizeof(int));
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa::launch_music_evd(h->N, h->M, noutput_items, h->d_in.p, nullptr, h->d_coef.p, nullptr, h->bits, h->stream);
+    if (int rc = doa::work_args("rootMUSIC_linear_array_debug", h, noutput_items, {input_items0, output_items0}, 1); rc != DOA_OK) return rc;
+    doa::HostCall io(*h);
+    io.in(h->d_in, input_items0, (size_t)noutput_items * h->N * h->N * sizeof(float2));
+    io.out(h->d_out, output_items0, (size_t)noutput_items * h->M * sizeof(float));
+    io.out(h->d_roots, roots_out, (size_t)noutput_items * (2 * h->N - 2) * sizeof(double2));
+    io.out(h->d_status, status_out, (size_t)noutput_items * sizeof(int));
+    io.out(h->d_coef, nullptr, (size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = doa::launch_music_evd(h->N, h->M, noutput_items, h->d_in.p, nullptr, h->d_coef.p, nullptr, h->bits, h->stream);
     if (rc == DOA_OK)
         rc = doa::launch_root_music(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, h->d_out.p, h->d_status.p,
                                     h->stream, h->d_roots.p);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (roots_out) DOA_HIP_TRY(hipMemcpyAsync(roots_out, h->d_roots.p, root_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (status_out)
-        DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, (size_t)noutput_items * sizeof(int), hipMemcpyDeviceToHost,
-                                   h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    return io.finish(rc == DOA_OK ? noutput_items : rc);
+}
+
+// the two select entries: roots (and counts, or NULL) up, the selection kernel alone, angles and status down
+static int root_select_debug(doa_rootMUSIC_linear_array_t *h, int n, const void *roots_in, const void *counts,
+                             void *output_items0, int *status_out)
+{
+    doa::HostCall io(*h);
+    io.in(h->d_roots, roots_in, (size_t)n * (2 * h->N - 2) * sizeof(double2));
+    if (counts) io.in(h->d_counts, counts, (size_t)n * sizeof(int));
+    io.out(h->d_out, output_items0, (size_t)n * h->M * sizeof(float));
+    io.out(h->d_status, status_out, (size_t)n * sizeof(int));
+    int rc = io.status();
+    if (rc == DOA_OK)
+        rc = counts ? doa::launch_root_select_counts(h->N, h->M, h->norm_spacing, n, h->d_roots.p, h->d_counts.p, h->d_out.p,
+                                                     h->d_status.p, h->stream)
+                    : doa::launch_root_select(h->N, h->M, h->norm_spacing, n, h->d_roots.p, h->d_out.p, h->d_status.p, h->stream);
+    return io.finish(rc == DOA_OK ? n : rc);
 }
 
 int doa_rootMUSIC_linear_array_select_debug(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *roots_in,
                                             void *output_items0, int *status_out)
 {
     doa::clear_error();
-    if (!h || noutput_items <= 0 || !roots_in || !output_items0) {
-        doa::set_error("rootMUSIC_linear_array_select_debug: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int D = 2 * h->N - 2;
-    const size_t out_bytes = (size_t)noutput_items * h->M * sizeof(float);
-    const size_t root_bytes = (size_t)noutput_items * D * sizeof(double2);
-    int rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_roots.reserve(root_bytes);
-    if (rc == DOA_OK) rc = h->d_status.reserve((size_t)noutput_items * sizeof(int));
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_roots.p, roots_in, root_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa::launch_root_select(h->N, h->M, h->norm_spacing, noutput_items, h->d_roots.p, h->d_out.p, h->d_status.p, h->stream);
-    if (rc != DOA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (status_out)
-        DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, (size_t)noutput_items * sizeof(int), hipMemcpyDeviceToHost,
-                                   h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    const char *who = "rootMUSIC_linear_array_select_debug";
+    if (int rc = doa::work_args(who, h, noutput_items, {roots_in, output_items0}, 1); rc != DOA_OK) return rc;
+    return root_select_debug(h, noutput_items, roots_in, nullptr, output_items0, status_out);
 }
 
 int doa_rootMUSIC_linear_array_select_counts_debug(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *roots_in,
                                                    const void *counts, void *output_items0, int *status_out)
 {
     doa::clear_error();
-    if (!h || noutput_items <= 0 || !roots_in || !counts || !output_items0) {
-        doa::set_error("rootMUSIC_linear_array_select_counts_debug: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int D = 2 * h->N - 2;
-    const size_t out_bytes = (size_t)noutput_items * h->M * sizeof(float);
-    const size_t root_bytes = (size_t)noutput_items * D * sizeof(double2);
-    const size_t cnt_bytes = (size_t)noutput_items * sizeof(int);
-    int rc = h->d_out.reserve(out_bytes);
-    if (rc == DOA_OK) rc = h->d_roots.reserve(root_bytes);
-    if (rc == DOA_OK) rc = h->d_counts.reserve(cnt_bytes);
-    if (rc == DOA_OK) rc = h->d_status.reserve(cnt_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_roots.p, roots_in, root_bytes, hipMemcpyHostToDevice, h->stream));
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_counts.p, counts, cnt_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa::launch_root_select_counts(h->N, h->M, h->norm_spacing, noutput_items, h->d_roots.p, h->d_counts.p, h->d_out.p,
-                                        h->d_status.p, h->stream);
-    if (rc != DOA_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (status_out)
-        DOA_HIP_TRY(hipMemcpyAsync(status_out, h->d_status.p, cnt_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    const char *who = "rootMUSIC_linear_array_select_counts_debug";
+    if (int rc = doa::work_args(who, h, noutput_items, {roots_in, counts, output_items0}, 1); rc != DOA_OK) return rc;
+    return root_select_debug(h, noutput_items, roots_in, counts, output_items0, status_out);
 }
 
 int doa_rootMUSIC_linear_array_set_internal_precision(doa_rootMUSIC_linear_array_t *h, int bits)

@@ -168,10 +168,10 @@ int launch_spatial_smooth(int N, int S, int fb, int n_items, const void *d_R, vo
 
 }  // namespace doa
 
-struct doa_spatial_smooth {
+#include "block_host.hpp"
+
+struct doa_spatial_smooth : doa::BlockBase {
     int N = 0, S = 0, fb = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out;
 };
 
@@ -189,35 +189,19 @@ doa_spatial_smooth_t *doa_spatial_smooth_create(int num_ant_ele, int subarray_si
         doa::set_error("spatial_smooth: num_ant_ele=%d exceeds DOA_MAX_ANT_ELE=%d", num_ant_ele, DOA_MAX_ANT_ELE);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_spatial_smooth();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->N = num_ant_ele; h->S = subarray_size; h->fb = forward_backward; h->device = dev;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("spatial_smooth: device setup failed");
-        doa_spatial_smooth_destroy(h);
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_spatial_smooth>("spatial_smooth", [&](doa_spatial_smooth &h) {
+        h.N = num_ant_ele; h.S = subarray_size; h.fb = forward_backward;
+        return DOA_OK;
+    });
 }
 
-void doa_spatial_smooth_destroy(doa_spatial_smooth_t *h)
-{
-    if (!h) return;
-    h->d_in.release(); h->d_out.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_spatial_smooth_destroy(doa_spatial_smooth_t *h) { doa::destroy_block(h); }
 
 int doa_spatial_smooth_work_dev(doa_spatial_smooth_t *h, int noutput_items, const void *d_cov_items, void *d_smoothed_items,
                                 void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!d_cov_items || !d_smoothed_items))) {
-        doa::set_error("spatial_smooth_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("spatial_smooth_work_dev", h, noutput_items, {d_cov_items, d_smoothed_items}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const int rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, noutput_items, d_cov_items, d_smoothed_items,
@@ -228,23 +212,14 @@ int doa_spatial_smooth_work_dev(doa_spatial_smooth_t *h, int noutput_items, cons
 int doa_spatial_smooth_work(doa_spatial_smooth_t *h, int noutput_items, const void *cov_items, void *smoothed_items)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || (noutput_items > 0 && (!cov_items || !smoothed_items))) {
-        doa::set_error("spatial_smooth_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("spatial_smooth_work", h, noutput_items, {cov_items, smoothed_items}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t in_bytes = (size_t)noutput_items * h->N * h->N * sizeof(float2);
-    const size_t out_bytes = (size_t)noutput_items * h->S * h->S * sizeof(float2);
-    int rc = h->d_in.reserve(in_bytes);
-    if (rc == DOA_OK) rc = h->d_out.reserve(out_bytes);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, cov_items, in_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_spatial_smooth_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(smoothed_items, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov_items, (size_t)noutput_items * h->N * h->N * sizeof(float2));
+    io.out(h->d_out, smoothed_items, (size_t)noutput_items * h->S * h->S * sizeof(float2));
+    int rc = io.status();
+    if (rc == DOA_OK) rc = doa_spatial_smooth_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
+    return io.finish(rc);
 }
 
 }  // extern "C"

@@ -42,7 +42,14 @@ def _count_method(method) -> int:
 
 
 def _opt_ptr(p) -> C.c_void_p:
+    """An optional device pointer: None is NULL.  (The per-item count pointers take it too: a missing one is the library's to
+    refuse.)"""
     return C.c_void_p(0 if p is None else int(p))
+
+
+def _dev_ptr(p) -> C.c_void_p:
+    """A required device pointer."""
+    return C.c_void_p(int(p))
 
 # estimators of music_pipeline (DOA_ESTIMATOR_MUSIC / DOA_ESTIMATOR_CAPON, include/doa_hip.h)
 _ESTIMATORS = {"music": 0, "capon": 1}
@@ -95,6 +102,31 @@ class _Block:
         if type(self)._set_precision is None:
             raise AttributeError(f"{type(self).__name__} has no internal precision")
         check(type(self)._set_precision(self._h, int(bits)))
+
+
+class _ItemBlock(_Block):
+    """Base of the blocks that take one item stream (covariance items or spectra): the checks of the host `work` arguments.
+    Each helper returns the pointer the C entry takes.  A new block's work is these three and one library call."""
+
+    @staticmethod
+    def _items_in(arr, dtype, n, width) -> C.c_void_p:
+        """n input items of `width` elements: converted to a C-contiguous `dtype` array if need be (the pointer keeps it alive)."""
+        a = np.ascontiguousarray(arr, dtype=dtype)
+        assert a.size >= n * width
+        return a.ctypes.data_as(C.c_void_p)
+
+    @staticmethod
+    def _items_out(arr, dtype, n, width) -> C.c_void_p:
+        """n output items of `width` elements, written in place: the array must already have the dtype and layout."""
+        assert arr.dtype == dtype and arr.flags.c_contiguous and arr.size >= n * width
+        return _vp(arr)
+
+    @classmethod
+    def _opt_out(cls, output_items, index, dtype, n, width) -> C.c_void_p:
+        """Output port `index` if the caller passed one, else NULL."""
+        if len(output_items) <= index or output_items[index] is None:
+            return C.c_void_p(0)
+        return cls._items_out(output_items[index], dtype, n, width)
 
 
 class _StreamInput:
@@ -283,7 +315,7 @@ class phase_correct_hier(antenna_correction):
         self.out_sig = [(_C64, 1)] * self.num_ports
 
 
-class MUSIC_lin_array(_Block):
+class MUSIC_lin_array(_ItemBlock):
     """doa.MUSIC_lin_array(norm_spacing, num_targets, inputs, pspectrum_len) — gr::sync_block
     (reference lib/MUSIC_lin_array_impl.cc:47-87)."""
 
@@ -302,30 +334,24 @@ class MUSIC_lin_array(_Block):
 
     def work(self, noutput_items, input_items, output_items) -> int:
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
-        return check(lib.doa_MUSIC_lin_array_work(self._h, n, _vp(a), _vp(out)))
+        return check(lib.doa_MUSIC_lin_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                  self._items_out(output_items[0], _F32, n, self.pspectrum_len)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
-        return check(lib.doa_MUSIC_lin_array_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                      C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
+        return check(lib.doa_MUSIC_lin_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                      _dev_ptr(d_out_ptr), _stream_ptr(stream)))
 
     def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
         """work with a source count PER ITEM (int32 array) in place of num_targets: count 0 gives an all-0.0 dB row, a count
         outside 0..inputs-1 (source_count's -1 status included) a NaN row (doa_MUSIC_lin_array_work_counts)."""
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        c = np.ascontiguousarray(counts, dtype=_I32)
-        out = output_items[0]
-        assert a.size >= n * self.num_ant_ele ** 2 and c.size >= n
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
-        return check(lib.doa_MUSIC_lin_array_work_counts(self._h, n, _vp(a), _vp(c), _vp(out)))
+        return check(lib.doa_MUSIC_lin_array_work_counts(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                         self._items_in(counts, _I32, n, 1),
+                                                         self._items_out(output_items[0], _F32, n, self.pspectrum_len)))
 
     def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out_ptr, stream=None) -> int:
-        return check(lib.doa_MUSIC_lin_array_work_dev_counts(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                             _opt_ptr(d_counts_ptr), C.c_void_p(int(d_out_ptr)),
+        return check(lib.doa_MUSIC_lin_array_work_dev_counts(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                             _opt_ptr(d_counts_ptr), _dev_ptr(d_out_ptr),
                                                              _stream_ptr(stream)))
 
     def debug(self, R_items: np.ndarray):
@@ -341,7 +367,7 @@ class MUSIC_lin_array(_Block):
         return int(lib.doa_MUSIC_lin_array_items_total(self._h))
 
 
-class find_local_max(_Block):
+class find_local_max(_ItemBlock):
     """doa.find_local_max(num_max_vals, vector_len, x_min, x_max) — gr::sync_block with two
     outputs (reference lib/find_local_max_impl.cc:47-71)."""
 
@@ -358,38 +384,33 @@ class find_local_max(_Block):
 
     def work(self, noutput_items, input_items, output_items) -> int:
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_F32)
         o0, o1 = output_items
-        assert a.size >= n * self.vector_len
-        for o in (o0, o1):
-            assert o.dtype == _F32 and o.flags.c_contiguous and o.size >= n * self.num_max_vals
-        return check(lib.doa_find_local_max_work(self._h, n, _vp(a), _vp(o0), _vp(o1)))
+        return check(lib.doa_find_local_max_work(self._h, n, self._items_in(input_items[0], _F32, n, self.vector_len),
+                                                 self._items_out(o0, _F32, n, self.num_max_vals),
+                                                 self._items_out(o1, _F32, n, self.num_max_vals)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out0_ptr, d_out1_ptr, stream=None) -> int:
-        return check(lib.doa_find_local_max_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                     C.c_void_p(int(d_out0_ptr)), C.c_void_p(int(d_out1_ptr)),
+        return check(lib.doa_find_local_max_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                     _dev_ptr(d_out0_ptr), _dev_ptr(d_out1_ptr),
                                                      _stream_ptr(stream)))
-
 
     def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
         """work with a peak count m_i PER ITEM (int32 array): the first m_i slots of both ports are find_local_max(m_i, ...)'s,
         the rest of the num_max_vals-wide items NaN; m_i outside 0..num_max_vals: all NaN (doa_find_local_max_work_counts)."""
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_F32)
-        c = np.ascontiguousarray(counts, dtype=_I32)
         o0, o1 = output_items
-        assert a.size >= n * self.vector_len and c.size >= n
-        for o in (o0, o1):
-            assert o.dtype == _F32 and o.flags.c_contiguous and o.size >= n * self.num_max_vals
-        return check(lib.doa_find_local_max_work_counts(self._h, n, _vp(a), _vp(c), _vp(o0), _vp(o1)))
+        return check(lib.doa_find_local_max_work_counts(self._h, n, self._items_in(input_items[0], _F32, n, self.vector_len),
+                                                        self._items_in(counts, _I32, n, 1),
+                                                        self._items_out(o0, _F32, n, self.num_max_vals),
+                                                        self._items_out(o1, _F32, n, self.num_max_vals)))
 
     def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out0_ptr, d_out1_ptr, stream=None) -> int:
-        return check(lib.doa_find_local_max_work_dev_counts(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                            _opt_ptr(d_counts_ptr), C.c_void_p(int(d_out0_ptr)),
-                                                            C.c_void_p(int(d_out1_ptr)), _stream_ptr(stream)))
+        return check(lib.doa_find_local_max_work_dev_counts(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                            _opt_ptr(d_counts_ptr), _dev_ptr(d_out0_ptr),
+                                                            _dev_ptr(d_out1_ptr), _stream_ptr(stream)))
 
 
-class source_count(_Block):
+class source_count(_ItemBlock):
     """doa.source_count(num_ant_ele, num_snapshots, method="mdl", max_sources=None) — the number of sources per covariance
     item, estimated on the device from its eigenvalues (Wax-Kailath MDL, or AIC; include/doa_hip.h).  Not a block of the
     reference, which takes num_targets as a flowgraph parameter.  Port 0: int32 count (-1: non-finite or non-positive item);
@@ -410,21 +431,16 @@ class source_count(_Block):
     def work(self, noutput_items, input_items, output_items) -> int:
         """output_items = [counts int32 [n]] or [counts, eigenvalues float32 [n, num_ant_ele]]."""
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        cnt = output_items[0]
-        eig = output_items[1] if len(output_items) > 1 else None
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert cnt.dtype == _I32 and cnt.flags.c_contiguous and cnt.size >= n
-        if eig is not None:
-            assert eig.dtype == _F32 and eig.flags.c_contiguous and eig.size >= n * self.num_ant_ele
-        return check(lib.doa_source_count_work(self._h, n, _vp(a), _vp(cnt), _vp(eig) if eig is not None else C.c_void_p(0)))
+        return check(lib.doa_source_count_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                               self._items_out(output_items[0], _I32, n, 1),
+                                               self._opt_out(output_items, 1, _F32, n, self.num_ant_ele)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_count_ptr, d_eig_ptr=None, stream=None) -> int:
-        return check(lib.doa_source_count_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                   _opt_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _stream_ptr(stream)))
+        return check(lib.doa_source_count_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                   _dev_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _stream_ptr(stream)))
 
 
-class spatial_smooth(_Block):
+class spatial_smooth(_ItemBlock):
     """doa.spatial_smooth(num_ant_ele, subarray_size, forward_backward=True) — spatial smoothing of covariance items for
     coherent sources (multipath, emitters on one oscillator): each num_ant_ele x num_ant_ele item is replaced by the
     average of its num_ant_ele - subarray_size + 1 overlapping subarray_size x subarray_size diagonal blocks, with
@@ -444,19 +460,16 @@ class spatial_smooth(_Block):
 
     def work(self, noutput_items, input_items, output_items) -> int:
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _C64 and out.flags.c_contiguous and out.size >= n * self.subarray_size ** 2
-        return check(lib.doa_spatial_smooth_work(self._h, n, _vp(a), _vp(out)))
+        return check(lib.doa_spatial_smooth_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                 self._items_out(output_items[0], _C64, n, self.subarray_size ** 2)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
         """d_out_ptr must not overlap d_in_ptr."""
-        return check(lib.doa_spatial_smooth_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                     C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
+        return check(lib.doa_spatial_smooth_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                     _dev_ptr(d_out_ptr), _stream_ptr(stream)))
 
 
-class capon_lin_array(_Block):
+class capon_lin_array(_ItemBlock):
     """doa.capon_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0) — the Capon (minimum-variance, MVDR)
     spectrum 1 / (a^H R^-1 a) of each covariance item on MUSIC_lin_array's angle grid, in its output format (dB against the
     row maximum): no source count, no eigendecomposition, a run time that does not depend on the data (definition:
@@ -478,18 +491,12 @@ class capon_lin_array(_Block):
     def work(self, noutput_items, input_items, output_items) -> int:
         """output_items = [spectrum float32 [n, P]] or [spectrum, status int32 [n]]."""
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        status = output_items[1] if len(output_items) > 1 else None
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
-        if status is not None:
-            assert status.dtype == _I32 and status.flags.c_contiguous and status.size >= n
-        return check(lib.doa_capon_lin_array_work(self._h, n, _vp(a), _vp(out),
-                                                  _vp(status) if status is not None else C.c_void_p(0)))
+        return check(lib.doa_capon_lin_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                  self._items_out(output_items[0], _F32, n, self.pspectrum_len),
+                                                  self._opt_out(output_items, 1, _I32, n, 1)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
-        return check(lib.doa_capon_lin_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+        return check(lib.doa_capon_lin_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _dev_ptr(d_out_ptr),
                                                       _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
     def debug(self, R_items: np.ndarray):
@@ -533,7 +540,7 @@ def planar_steering_table(positions, pspectrum_len, az_min=0.0, az_max=360.0, el
     return out
 
 
-class MUSIC_array(_Block):
+class MUSIC_array(_ItemBlock):
     """doa.MUSIC_array(num_targets, steering) — the MUSIC spectrum for an arbitrary array geometry: steering is a
     [pspectrum_len, inputs] complex table (row i = the array response towards direction i; planar_steering_table builds one
     for a planar array, a measured manifold works as well), Q_i = Re(a_i^H P_N a_i) in double, output as MUSIC_lin_array's
@@ -553,14 +560,11 @@ class MUSIC_array(_Block):
 
     def work(self, noutput_items, input_items, output_items) -> int:
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
-        return check(lib.doa_MUSIC_array_work(self._h, n, _vp(a), _vp(out)))
+        return check(lib.doa_MUSIC_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                              self._items_out(output_items[0], _F32, n, self.pspectrum_len)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
-        return check(lib.doa_MUSIC_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+        return check(lib.doa_MUSIC_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _dev_ptr(d_out_ptr),
                                                   _stream_ptr(stream)))
 
     def debug(self, R_items: np.ndarray):
@@ -576,7 +580,7 @@ class MUSIC_array(_Block):
         return int(lib.doa_MUSIC_array_items_total(self._h))
 
 
-class capon_array(_Block):
+class capon_array(_ItemBlock):
     """doa.capon_array(steering, diagonal_loading=0.0) — the Capon (MVDR) spectrum 1 / (a^H R^-1 a) for an arbitrary array
     geometry: steering as for MUSIC_array, the inverse, its status and diagonal_loading exactly as capon_lin_array's
     (definition: include/doa_hip.h).  Port 0: the spectrum; port 1 (optional): int32 status, 1 = not positive definite enough
@@ -597,18 +601,12 @@ class capon_array(_Block):
     def work(self, noutput_items, input_items, output_items) -> int:
         """output_items = [spectrum float32 [n, P]] or [spectrum, status int32 [n]]."""
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        status = output_items[1] if len(output_items) > 1 else None
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.pspectrum_len
-        if status is not None:
-            assert status.dtype == _I32 and status.flags.c_contiguous and status.size >= n
-        return check(lib.doa_capon_array_work(self._h, n, _vp(a), _vp(out),
-                                              _vp(status) if status is not None else C.c_void_p(0)))
+        return check(lib.doa_capon_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                              self._items_out(output_items[0], _F32, n, self.pspectrum_len),
+                                              self._opt_out(output_items, 1, _I32, n, 1)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
-        return check(lib.doa_capon_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+        return check(lib.doa_capon_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _dev_ptr(d_out_ptr),
                                                   _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
     def debug(self, R_items: np.ndarray):
@@ -624,7 +622,7 @@ class capon_array(_Block):
         return int(lib.doa_capon_array_items_total(self._h))
 
 
-class rootMUSIC_linear_array(_Block):
+class rootMUSIC_linear_array(_ItemBlock):
     """doa.rootMUSIC_linear_array(norm_spacing, num_targets, inputs) — gr::sync_block
     (reference lib/rootMUSIC_linear_array_impl.cc:46-59)."""
 
@@ -641,15 +639,12 @@ class rootMUSIC_linear_array(_Block):
 
     def work(self, noutput_items, input_items, output_items) -> int:
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.num_targets
-        return check(lib.doa_rootMUSIC_linear_array_work(self._h, n, _vp(a), _vp(out)))
+        return check(lib.doa_rootMUSIC_linear_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                         self._items_out(output_items[0], _F32, n, self.num_targets)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
-        return check(lib.doa_rootMUSIC_linear_array_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                             C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
+        return check(lib.doa_rootMUSIC_linear_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                             _dev_ptr(d_out_ptr), _stream_ptr(stream)))
 
     def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
         """work with a source count PER ITEM (int32 array) in place of num_targets: items stay num_targets floats wide, the
@@ -658,18 +653,15 @@ class rootMUSIC_linear_array(_Block):
         DoaError(DOA_ERR_NUMERIC) only for an item with a usable count and no root inside the unit circle
         (doa_rootMUSIC_linear_array_work_counts)."""
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        c = np.ascontiguousarray(counts, dtype=_I32)
-        out = output_items[0]
-        assert a.size >= n * self.num_ant_ele ** 2 and c.size >= n
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.num_targets
-        return check(lib.doa_rootMUSIC_linear_array_work_counts(self._h, n, _vp(a), _vp(c), _vp(out)))
+        return check(lib.doa_rootMUSIC_linear_array_work_counts(
+            self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2), self._items_in(counts, _I32, n, 1),
+            self._items_out(output_items[0], _F32, n, self.num_targets)))
 
     def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
         """The device form; d_status_ptr (optional): one int32 per item, 0 = fine, 1 = no root inside the unit circle,
         2 = no usable count."""
-        return check(lib.doa_rootMUSIC_linear_array_work_dev_counts(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                                    _opt_ptr(d_counts_ptr), C.c_void_p(int(d_out_ptr)),
+        return check(lib.doa_rootMUSIC_linear_array_work_dev_counts(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                                    _opt_ptr(d_counts_ptr), _dev_ptr(d_out_ptr),
                                                                     _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
     def debug(self, R_items: np.ndarray):
@@ -697,15 +689,14 @@ class rootMUSIC_linear_array(_Block):
         2 = no usable count): the selection stage of work_counts."""
         z = np.ascontiguousarray(roots, dtype=np.complex128).reshape(-1, 2 * self.num_ant_ele - 2)
         n = z.shape[0]
-        c = np.ascontiguousarray(counts, dtype=_I32)
-        assert c.size >= n
         ang = np.empty((n, self.num_targets), dtype=_F32)
         status = np.empty(n, dtype=np.int32)
-        check(lib.doa_rootMUSIC_linear_array_select_counts_debug(self._h, n, _vp(z), _vp(c), _vp(ang), _vp(status)))
+        check(lib.doa_rootMUSIC_linear_array_select_counts_debug(self._h, n, _vp(z), self._items_in(counts, _I32, n, 1), _vp(ang),
+                                                                 _vp(status)))
         return ang, status
 
 
-class esprit_linear_array(_Block):
+class esprit_linear_array(_ItemBlock):
     """doa.esprit_linear_array(norm_spacing, num_targets, inputs) — least-squares ESPRIT for a uniform linear array: the
     angles from the eigenvalues of the num_targets x num_targets matrix that maps the signal subspace of rows 0..N-2 onto rows
     1..N-1; no polynomial, no search, no unit-circle filter (definition: include/doa_hip.h).  Port 0: num_targets angles in
@@ -723,24 +714,15 @@ class esprit_linear_array(_Block):
         self.in_sig = [(_C64, self.num_ant_ele ** 2)]
         self.out_sig = [(_F32, self.num_targets), (_I32, 1)]
 
-    def _host_args(self, noutput_items, input_items, output_items):
-        n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        status = output_items[1] if len(output_items) > 1 else None
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _F32 and out.flags.c_contiguous and out.size >= n * self.num_targets
-        if status is not None:
-            assert status.dtype == _I32 and status.flags.c_contiguous and status.size >= n
-        return n, a, out, _vp(status) if status is not None else C.c_void_p(0)
-
     def work(self, noutput_items, input_items, output_items) -> int:
         """output_items = [angles float32 [n, num_targets]] or [angles, status int32 [n]]."""
-        n, a, out, st = self._host_args(noutput_items, input_items, output_items)
-        return check(lib.doa_esprit_linear_array_work(self._h, n, _vp(a), _vp(out), st))
+        n = int(noutput_items)
+        return check(lib.doa_esprit_linear_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                      self._items_out(output_items[0], _F32, n, self.num_targets),
+                                                      self._opt_out(output_items, 1, _I32, n, 1)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
-        return check(lib.doa_esprit_linear_array_work_dev(self._h, int(noutput_items), _opt_ptr(d_in_ptr), _opt_ptr(d_out_ptr),
+        return check(lib.doa_esprit_linear_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _dev_ptr(d_out_ptr),
                                                           _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
     def work_counts(self, noutput_items, input_items, counts, output_items) -> int:
@@ -748,18 +730,18 @@ class esprit_linear_array(_Block):
         rootMUSIC_linear_array.work_counts: items stay num_targets floats wide, the first count slots are
         esprit_linear_array(norm_spacing, count, inputs)'s and the rest NaN; count 0: all NaN, status 0; a count outside
         0..min(num_targets, inputs-1) (source_count's -1 included): all NaN, status 2."""
-        n, a, out, st = self._host_args(noutput_items, input_items, output_items)
-        c = np.ascontiguousarray(counts, dtype=_I32)
-        assert c.size >= n
-        return check(lib.doa_esprit_linear_array_work_counts(self._h, n, _vp(a), _vp(c), _vp(out), st))
+        n = int(noutput_items)
+        return check(lib.doa_esprit_linear_array_work_counts(
+            self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2), self._items_in(counts, _I32, n, 1),
+            self._items_out(output_items[0], _F32, n, self.num_targets), self._opt_out(output_items, 1, _I32, n, 1)))
 
     def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out_ptr, d_status_ptr=None, stream=None) -> int:
-        return check(lib.doa_esprit_linear_array_work_dev_counts(self._h, int(noutput_items), _opt_ptr(d_in_ptr),
-                                                                 _opt_ptr(d_counts_ptr), _opt_ptr(d_out_ptr),
+        return check(lib.doa_esprit_linear_array_work_dev_counts(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                                 _opt_ptr(d_counts_ptr), _dev_ptr(d_out_ptr),
                                                                  _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
 
-class calibrate_lin_array(_Block):
+class calibrate_lin_array(_ItemBlock):
     """doa.calibrate_lin_array(norm_spacing, num_ant_ele, pilot_angle) — gr::sync_block, vlen N^2
     complex in, vlen N complex out (reference lib/calibrate_lin_array_impl.cc:46-75)."""
 
@@ -776,15 +758,12 @@ class calibrate_lin_array(_Block):
 
     def work(self, noutput_items, input_items, output_items) -> int:
         n = int(noutput_items)
-        a = np.ascontiguousarray(input_items[0], dtype=_C64)
-        out = output_items[0]
-        assert a.size >= n * self.num_ant_ele ** 2
-        assert out.dtype == _C64 and out.flags.c_contiguous and out.size >= n * self.num_ant_ele
-        return check(lib.doa_calibrate_lin_array_work(self._h, n, _vp(a), _vp(out)))
+        return check(lib.doa_calibrate_lin_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                      self._items_out(output_items[0], _C64, n, self.num_ant_ele)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
-        return check(lib.doa_calibrate_lin_array_work_dev(self._h, int(noutput_items), C.c_void_p(int(d_in_ptr)),
-                                                          C.c_void_p(int(d_out_ptr)), _stream_ptr(stream)))
+        return check(lib.doa_calibrate_lin_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                          _dev_ptr(d_out_ptr), _stream_ptr(stream)))
 
 
 class music_pipeline(_StreamInput, _Block):
