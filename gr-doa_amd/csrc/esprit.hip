@@ -385,6 +385,23 @@ static int esprit_run_host(doa_esprit_linear_array_t *h, int n, const void *cov,
     return io.finish(rc);
 }
 
+// the record entry: items, records (and counts, or NULL) up, esprit_kernel alone, angles and status down
+static int esprit_record_debug(doa_esprit_linear_array_t *h, int n, const void *cov, const void *records, const void *counts,
+                               void *angles, int *status)
+{
+    doa::HostCall io(*h);
+    io.in(h->d_in, cov, (size_t)n * h->N * h->N * sizeof(float2));
+    io.in(h->d_rec, records, (size_t)n * doa::subspace_record_len(h->N) * sizeof(double));
+    if (counts) io.in(h->d_counts, counts, (size_t)n * sizeof(int));
+    io.out(h->d_out, angles, (size_t)n * h->M * sizeof(float));
+    io.out(h->d_status, status, (size_t)n * sizeof(int));
+    int rc = io.status();
+    if (rc == DOA_OK)
+        rc = doa::launch_esprit(h->N, h->M, h->norm_spacing, n, h->d_in.p, h->d_rec.p, counts ? h->d_counts.p : nullptr, h->d_out.p,
+                                h->d_status.p, h->stream);
+    return io.finish(rc == DOA_OK ? n : rc);
+}
+
 extern "C" {
 
 doa_esprit_linear_array_t *doa_esprit_linear_array_create(float norm_spacing, int num_targets, int num_ant_ele)
@@ -449,6 +466,16 @@ int doa_esprit_linear_array_work_counts(doa_esprit_linear_array_t *h, int noutpu
         return rc;
     if (noutput_items == 0) return 0;
     return esprit_run_host(h, noutput_items, cov_items, counts, angles_out, status_out);
+}
+
+int doa_esprit_linear_array_record_debug(doa_esprit_linear_array_t *h, int noutput_items, const void *cov_items, const void *records,
+                                         const void *counts, void *angles_out, int *status_out)
+{
+    doa::clear_error();
+    const char *who = "esprit_linear_array_record_debug";
+    if (int rc = doa::work_args(who, h, noutput_items, {cov_items, records, angles_out}, 1); rc != DOA_OK) return rc;
+    if (int rc = doa::need_bits64(who, h->bits, "ESPRIT"); rc != DOA_OK) return rc;
+    return esprit_record_debug(h, noutput_items, cov_items, records, counts, angles_out, status_out);
 }
 
 }  // extern "C"

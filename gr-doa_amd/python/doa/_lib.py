@@ -200,6 +200,7 @@ SIGNATURES = {
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_capon_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_esprit_linear_array_record_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "doa_root_pipeline_inject_failure": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_lanes_idle": (C.c_int, [_vp]),
     "doa_hip_evd_fallback_counter_device_debug": (C.c_int, []),

@@ -740,6 +740,21 @@ class esprit_linear_array(_ItemBlock):
                                                                  _opt_ptr(d_counts_ptr), _dev_ptr(d_out_ptr),
                                                                  _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
+    def record_debug(self, R_items: np.ndarray, records: np.ndarray, counts=None):
+        """esprit_kernel alone on the given signal-subspace records [n, 2 N^2] float64 (gr-doa_amd/csrc/kernels.hpp) in place
+        of the eigen stage's; R_items [n, N*N] complex64 supplies the trace and finiteness test; counts: int32 [n] or None
+        -> (angles [n, num_targets] float32, status [n] int32), for the solver tests."""
+        N = self.num_ant_ele
+        a = np.ascontiguousarray(R_items, dtype=_C64).reshape(-1, N * N)
+        n = a.shape[0]
+        rec = np.ascontiguousarray(records, dtype=np.float64).reshape(n, 2 * N * N)
+        cnt = None if counts is None else np.ascontiguousarray(counts, dtype=_I32).reshape(n)
+        ang = np.empty((n, self.num_targets), dtype=_F32)
+        status = np.empty(n, dtype=np.int32)
+        check(lib.doa_esprit_linear_array_record_debug(self._h, n, _vp(a), _vp(rec), C.c_void_p(0) if cnt is None else _vp(cnt),
+                                                       _vp(ang), _vp(status)))
+        return ang, status
+
 
 class calibrate_lin_array(_ItemBlock):
     """doa.calibrate_lin_array(norm_spacing, num_ant_ele, pilot_angle) — gr::sync_block, vlen N^2

@@ -64,6 +64,18 @@ DOA_HIP_API int doa_MUSIC_array_debug(doa_MUSIC_array_t *h, int noutput_items, c
 DOA_HIP_API int doa_capon_array_debug(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *inverse_out,
                                       void *null_spectrum_out);
 
+/* Diagnostics of esprit_linear_array (host buffers, synchronous): ONLY esprit_kernel, the very launch the work entries end
+ * in, on CALLER-SUPPLIED signal-subspace records in place of the eigen stage's (records: noutput_items x 2 num_ant_ele^2
+ * doubles, [2 (k N + row)] = Re, [.. + 1] = Im of entry `row` of column k; the kernel reads the first m columns of an item
+ * with count m and no others), so that the eigenvalue solver can be driven with subspaces no covariance item produces on
+ * purpose: non-normal Psi, gamma at its threshold, components outside the visible region.  cov_items supplies only what
+ * the kernel takes from the item itself, the trace and finiteness test of status 1.  counts (int32 per item) may be NULL:
+ * every item takes num_targets columns.  angles_out: num_targets floats per item; status_out (may be NULL): 0 / 1 / 2 / 3 as
+ * doa_esprit_linear_array_work_counts defines them.  Returns noutput_items on success. */
+DOA_HIP_API int doa_esprit_linear_array_record_debug(doa_esprit_linear_array_t *h, int noutput_items, const void *cov_items,
+                                                     const void *records, const void *counts, void *angles_out,
+                                                     int *status_out);
+
 /* Profiling aid: which stages later work_dev calls on this handle launch (bit 0 = K1 covariance, bit 1 = K2+K3
  * EVD, bit 2 = K4+K5 scan + peak pick; default 7).  A dropped stage leaves its outputs as the previous call
  * wrote them, so a profiler can time one kernel on valid intermediates; not for production use. */

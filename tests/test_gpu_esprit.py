@@ -178,6 +178,8 @@ PIPE_SHAPES = {
     "n4": (4, 2, (30.0, 123.0), 0, 0),
     "n8": (8, 3, (60.0, 75.0, 120.0), 0, 0),
     "n8_smoothed": (8, 3, (60.0, 75.0, 120.0), 5, 1),
+    "n16": (16, 3, (40.0, 75.0, 120.0), 0, 0),                     # 16 lanes per item
+    "n16_smoothed": (16, 3, (40.0, 75.0, 120.0), 9, 1),            # subarrays of 9: 16 lanes per item after smoothing
 }
 
 
