@@ -6,12 +6,9 @@
 // stream: K1 covariance, K2+K3 EVD/projector/diagonal sums, K4 scan, K5 peak pick.  Intermediates
 // (covariances, coefficient records, spectra) stay in HBM-resident buffers owned by the handle
 // unless the caller asks for them.
-#include "kernels.hpp"
-#include "pipeline_lanes.hpp"
+#include "pipeline_front.hpp"
 
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -22,35 +19,20 @@ int launch_find_local_max_serial(const PeakTables &t, int n_items, const void *d
                                  void *d_scratch, hipStream_t st);
 }  // namespace doa
 
-struct doa_music_pipeline {
-    int N = 0, K = 0, ovl = 0, avg = 0;
-    int max_batch = 0;
-    int bits = 64;
-    int device = 0;
+// the front (K1, smoothing, the host entry's transport, the lanes) is doa::PipeFront's; these are the estimator stage's
+struct doa_music_pipeline : doa::PipeFront {
     unsigned stages = 7;           // bit 0 K1, bit 1 K2+K3, bit 2 K4+K5 (doa_music_pipeline_set_stages)
     doa::MusicTables music;
     doa::PeakTables peaks;
-    doa::DevBuf d_cov, d_coef, d_cheb, d_spec, d_scratch, d_gain;
-    bool has_gain = false;
-    int format = DOA_SAMPLE_FC32;   // doa_music_pipeline_set_input_format
-    float scale = 1.0f;
-    int S = 0, fb = 0;              // doa_music_pipeline_set_spatial_smoothing: subarray size (0 = off), forward-backward
-    doa::DevBuf d_smooth;           // the smoothed items (S * S per item) between K1 and the eigen stage
+    doa::DevBuf d_coef, d_cheb, d_spec, d_scratch;
     int estimator = DOA_ESTIMATOR_MUSIC;    // doa_music_pipeline_set_estimator
     double loading = 0.0;           // Capon: the diagonal loading
     doa::DevBuf d_status;           // Capon: int32 per item between the inverse launch and the NaN follow-up
     bool has_table = false;         // doa_music_pipeline_set_steering_table: an arbitrary array geometry
     doa::ArrayTable array;          // its table in the scan's form (array_scan.hip)
     doa::DevBuf d_full;             // the full records (N * N doubles per item) between the stage in front and the scan
-    // host-pointer entry point only: two copy/compute lanes
-    hipStream_t hst[2] = {nullptr, nullptr};
-    doa::DevBuf d_in[2], d_res;
-    doa::DevBuf d_work[2];          // K1's piece sums (overlapping windows), one per copy/compute lane
-    doa::PinnedBuf h_stage;         // scheduler-sized calls: one page-locked staging buffer, one copy each way
-    int fail_chunk = -1;            // doa_music_pipeline_inject_failure, host-pointer entry: one-shot, cleared by every call (tests)
-    // doa_music_pipeline_work_dev_batches: the library's own overlap lanes (pipeline_lanes.hpp); a lane's buffers:
+    // doa_music_pipeline_work_dev_batches: a lane's buffers
     enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch, kSmooth, kStatus, kFull };
-    doa::PipeLanes lanes;
 };
 
 // what one K1 -> EVD -> scan chain needs besides its inputs and outputs
@@ -72,11 +54,8 @@ struct PipeWs {
 static int run_k1(doa_music_pipeline *h, int n, const void *const *d_in, void *cov, const PipeWs &ws, hipStream_t st)
 {
     if (~h->stages & 1u) return DOA_OK;         // doa_music_pipeline_set_stages (profiling aid; all stages in production)
-    return doa::launch_autocorrelate(h->N, h->K, h->ovl, h->avg, n, d_in, cov, st, h->has_gain ? h->d_gain.p : nullptr, ws.work,
-                                     h->format, h->scale);
+    return h->run_k1(n, d_in, cov, ws.work, st);
 }
-// the array the eigen stage, the scan and the peak pick see: the subarray of a smoothed handle
-static int evd_elements(const doa_music_pipeline *h) { return h->S ? h->S : h->N; }
 static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, void *mx, void *am, const PipeWs &ws, hipStream_t st)
 {
     const bool store_spec = (spec != nullptr);
@@ -85,11 +64,10 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
     int rc = DOA_OK;
     const bool dbl = (h->bits == 64);
     void *coef = ws.coef;
-    if (h->S) {                                 // spatial smoothing: one launch, part of stage bit 1; `cov` stays the N x N item
-        if (!(skip & 2)) rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, n, cov, ws.smooth, st);
-        if (rc != DOA_OK) return rc;
-        cov = ws.smooth;
-    }
+    // spatial smoothing: one launch, part of stage bit 1; the eigen stage reads the smoothed items either way
+    if (!(skip & 2)) rc = h->run_smoothing(n, cov, ws.smooth, st);
+    else if (h->S) cov = ws.smooth;
+    if (rc != DOA_OK) return rc;
     const bool capon = (h->estimator == DOA_ESTIMATOR_CAPON);
     if (capon && !dbl) {
         doa::set_error("music_pipeline: the Capon estimator needs internal precision 64 (handle is at %d)", h->bits);
@@ -127,9 +105,9 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
     }
     if (!(skip & 2)) {
         if (capon)
-            rc = doa::launch_capon_inverse(evd_elements(h), n, cov, h->loading, coef, ws.cheb, nullptr, ws.status, st);
+            rc = doa::launch_capon_inverse(h->elements(), n, cov, h->loading, coef, ws.cheb, nullptr, ws.status, st);
         else
-            rc = doa::launch_music_evd(evd_elements(h), h->music.M, n, cov, dbl ? nullptr : coef, dbl ? coef : nullptr, nullptr, h->bits, st, ws.cheb);
+            rc = doa::launch_music_evd(h->elements(), h->music.M, n, cov, dbl ? nullptr : coef, dbl ? coef : nullptr, nullptr, h->bits, st, ws.cheb);
     }
     if (rc != DOA_OK) return rc;
     bool peaks_done = false;
@@ -184,12 +162,7 @@ doa_music_pipeline_t *doa_music_pipeline_create(int inputs, int snapshot_size, i
                                                 float norm_spacing, int num_targets, int pspectrum_len, int max_batch)
 {
     doa::clear_error();
-    if (inputs <= 0 || inputs > DOA_MAX_ANT_ELE || snapshot_size <= 0 || overlap_size < 0 ||
-        overlap_size >= snapshot_size) {
-        doa::set_error("music_pipeline: bad autocorrelate parameters (inputs=%d snapshot=%d overlap=%d)", inputs,
-                       snapshot_size, overlap_size);
-        return nullptr;
-    }
+    if (!doa::PipeFront::check_create("music_pipeline", inputs, snapshot_size, overlap_size)) return nullptr;
     if (num_targets <= 0 || num_targets >= inputs || num_targets > DOA_MAX_PEAKS || !(norm_spacing > 0.0f) ||
         norm_spacing > 0.5f || pspectrum_len <= 0 || max_batch <= 0) {
         doa::set_error("music_pipeline: bad MUSIC parameters (norm_spacing=%g num_targets=%d inputs=%d "
@@ -197,71 +170,30 @@ doa_music_pipeline_t *doa_music_pipeline_create(int inputs, int snapshot_size, i
                        max_batch);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_music_pipeline();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->N = inputs; h->K = snapshot_size; h->ovl = overlap_size; h->avg = avg_method;
-    h->max_batch = max_batch; h->device = dev;
-    h->bits = doa::internal_precision_bits();
-    int rc = h->music.build(norm_spacing, num_targets, inputs, pspectrum_len);
-    if (rc == DOA_OK) rc = h->peaks.build(num_targets, pspectrum_len, 0.0f, 180.0f);
-    if (rc == DOA_OK) rc = h->d_cov.reserve((size_t)max_batch * inputs * inputs * sizeof(float2));
-    if (rc == DOA_OK) rc = h->d_coef.reserve((size_t)max_batch * doa::coef_stride(inputs) * sizeof(double));
-    if (rc == DOA_OK && doa::music_uses_cheb(inputs, h->bits)) rc = h->d_cheb.reserve((size_t)max_batch * doa::kChebRecord * sizeof(double));
-    if (rc == DOA_OK) rc = h->d_spec.reserve((size_t)max_batch * pspectrum_len * sizeof(float));
-    if (const size_t ws = doa::autocorrelate_workspace_bytes(inputs, snapshot_size, overlap_size, max_batch); ws && rc == DOA_OK)
-        rc = h->d_work[0].reserve(ws);
-    if (rc != DOA_OK) {
-        doa_music_pipeline_destroy(h);
-        return nullptr;
-    }
-    return h;
+    return doa::create_pipeline<doa_music_pipeline>(inputs, snapshot_size, overlap_size, avg_method, max_batch, [&](doa_music_pipeline &h) {
+        int rc = h.music.build(norm_spacing, num_targets, inputs, pspectrum_len);
+        if (rc == DOA_OK) rc = h.peaks.build(num_targets, pspectrum_len, 0.0f, 180.0f);
+        if (rc == DOA_OK) rc = h.d_coef.reserve((size_t)max_batch * doa::coef_stride(inputs) * sizeof(double));
+        if (rc == DOA_OK && doa::music_uses_cheb(inputs, h.bits)) rc = h.d_cheb.reserve((size_t)max_batch * doa::kChebRecord * sizeof(double));
+        if (rc == DOA_OK) rc = h.d_spec.reserve((size_t)max_batch * pspectrum_len * sizeof(float));
+        return rc;
+    });
 }
 
-void doa_music_pipeline_destroy(doa_music_pipeline_t *h)
-{
-    if (!h) return;
-    h->music.release();
-    h->peaks.release();
-    h->d_cov.release(); h->d_coef.release(); h->d_cheb.release(); h->d_spec.release(); h->d_scratch.release(); h->d_gain.release();
-    h->d_smooth.release(); h->d_status.release();
-    h->array.release(); h->d_full.release();
-    h->d_res.release(); h->h_stage.release();
-    for (auto &b : h->d_work) b.release();
-    for (auto &b : h->d_in) b.release();
-    for (auto st : h->hst)
-        if (st) (void)hipStreamDestroy(st);
-    h->lanes.release();
-    delete h;
-}
+void doa_music_pipeline_destroy(doa_music_pipeline_t *h) { doa::PipeFront::destroy(h); }
 
 int doa_music_pipeline_fuse_antenna_correction(doa_music_pipeline_t *h, const float *gains_re_im)
 {
     doa::clear_error();
     if (!h) return DOA_ERR_INVALID_ARG;
-    if (!gains_re_im) { h->has_gain = false; return DOA_OK; }
-    const int N = h->N;
-    float2 w[DOA_MAX_ANT_ELE * DOA_MAX_ANT_ELE];
-    for (int b = 0; b < N; b++)
-        for (int a = 0; a < N; a++) {
-            const float ar = gains_re_im[2 * a], ai = gains_re_im[2 * a + 1], br = gains_re_im[2 * b], bi = gains_re_im[2 * b + 1];
-            w[a + b * N] = make_float2(ar * br + ai * bi, ai * br - ar * bi);   // g_a conj(g_b)
-        }
-    int rc = h->d_gain.reserve(sizeof(float2) * N * N);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpy(h->d_gain.p, w, sizeof(float2) * N * N, hipMemcpyHostToDevice));
-    h->has_gain = true;
-    return DOA_OK;
+    return h->fuse_antenna_correction(gains_re_im);
 }
 
 int doa_music_pipeline_set_input_format(doa_music_pipeline_t *h, int format, float scale)
 {
     doa::clear_error();
     if (!h) { doa::set_error("music_pipeline_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (const int rc = doa::check_input_format("music_pipeline", format, scale); rc != DOA_OK) return rc;
-    h->format = format; h->scale = scale;
-    return DOA_OK;
+    return h->set_input_format("music_pipeline", format, scale);
 }
 
 int doa_music_pipeline_set_stages(doa_music_pipeline_t *h, int stage_mask)
@@ -277,22 +209,16 @@ int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarr
     doa::clear_error();
     if (!h) { doa::set_error("music_pipeline_set_spatial_smoothing: bad arguments"); return DOA_ERR_INVALID_ARG; }
     const int S = subarray_size, fb = S ? forward_backward : 0;
-    if (S != 0 && (S < 2 || S > h->N || h->music.M >= S || (fb != 0 && fb != 1))) {
-        doa::set_error("music_pipeline_set_spatial_smoothing: need subarray_size 0 (off) or 2 <= subarray_size <= inputs with "
-                       "num_targets < subarray_size, forward_backward 0 or 1 (got %d, %d; inputs=%d num_targets=%d)", S,
-                       forward_backward, h->N, h->music.M);
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = h->smoothing_args("music_pipeline_set_spatial_smoothing", h->music.M, S, forward_backward); rc != DOA_OK) return rc;
     if (S != 0 && h->has_table) {
         doa::set_error("music_pipeline_set_spatial_smoothing: smoothing assumes a translation-invariant (uniform linear) array; "
                        "this handle has a steering table");
         return DOA_ERR_UNSUPPORTED;
     }
-    if (S == h->S && fb == h->fb) return DOA_OK;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    int rc = h->smoothing_reserve(S, fb);
+    if (rc <= 0) return rc;
     const int elements = S ? S : h->N;
-    int rc = S ? h->d_smooth.reserve((size_t)h->max_batch * S * S * sizeof(float2)) : DOA_OK;
-    if (rc == DOA_OK && doa::music_uses_cheb(elements, h->bits)) rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double));
+    rc = doa::music_uses_cheb(elements, h->bits) ? h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double)) : DOA_OK;
     if (rc != DOA_OK) return rc;
     // the scan's tables for `elements` antennas (the steering phases themselves depend on norm_spacing and pspectrum_len alone)
     const int was = h->music.N;
@@ -423,7 +349,7 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const int n = noutput_items;
-    const int elements = evd_elements(h);
+    const int elements = h->elements();
     const bool cheb = doa::music_uses_cheb(elements, 64);
     // (a handle created at precision 32 and switched to 64 afterwards has no Chebyshev records yet)
     if (cheb && !h->d_cheb.p)
@@ -433,10 +359,7 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     PipeWs ws{};
     ws.work = h->d_work[0].p;
     int rc = run_k1(h, n, d_input_items, cov, ws, st);
-    if (rc == DOA_OK && h->S) {
-        rc = doa::launch_spatial_smooth(h->N, h->S, h->fb, n, cov, h->d_smooth.p, st);
-        cov = h->d_smooth.p;
-    }
+    if (rc == DOA_OK) rc = h->run_smoothing(n, cov, h->d_smooth.p, st);
     if (rc == DOA_OK)
         rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->music.M, h->d_coef.p,
                                           cheb ? h->d_cheb.p : nullptr, st);
@@ -624,7 +547,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         if (rc == DOA_OK && h->S) rc = smooth.reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
         if (rc == DOA_OK && h->estimator == DOA_ESTIMATOR_CAPON) rc = status.reserve((size_t)h->max_batch * sizeof(int));
         if (rc == DOA_OK && h->has_table) rc = full.reserve((size_t)h->max_batch * doa::full_record_len(N) * sizeof(double));
-        if (rc == DOA_OK && doa::music_uses_cheb(evd_elements(h), h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
+        if (rc == DOA_OK && doa::music_uses_cheb(h->elements(), h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
         if (rc == DOA_OK && need_cov) rc = cov.reserve((size_t)G * h->max_batch * N * N * sizeof(float2));
         if (rc == DOA_OK && need_spec) rc = spec.reserve((size_t)G_angles * h->max_batch * P * sizeof(float));
         if (rc == DOA_OK && work_bytes) rc = work.reserve(work_bytes);
@@ -728,158 +651,40 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
         return DOA_ERR_INVALID_ARG;
     }
     if (noutput_items == 0) return 0;
-    const int N = h->N, M = h->music.M, P = h->peaks.L;
-    for (int k = 0; k < N; k++)
-        if (!input_items[k]) { doa::set_error("music_pipeline_work: input_items[%d] is NULL", k); return DOA_ERR_INVALID_ARG; }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    if (const int src = doa::ensure_stream_pair(h->hst); src != DOA_OK) return src;
-    const size_t nonoverlap = (size_t)(h->K - h->ovl);
-    const size_t sb = doa::sample_bytes(h->format);     // bytes per input sample: 8 (fc32) or 4 (sc16)
-    // Scheduler-sized calls (a GNU Radio work() hands over a few to a few hundred items): the fixed costs are what
-    // counts -- N pageable host-to-device copies, up to four copies back and two stream synchronisations.  Below
-    // kSmallCallBytes of input the window of every stream is packed into ONE page-locked staging buffer (the same
-    // bytes the driver's pageable path would stage, minus its per-copy set-up), crosses PCIe as ONE transfer, and the
-    // angles (+ the optional covariances / spectra) come back as ONE transfer through the same buffer.  Measured: 8 items
-    // 105 -> 53 us per call, 64 items 151 -> 116 us; from 8 MiB up the host-side packing costs more than it saves.
-    {
-        static const size_t kSmallCallBytes = [] { const char *e = getenv("DOA_PIPE_SMALL_CALL_KB"); return (size_t)(e ? atoi(e) : 2048) << 10; }();
-        const size_t span = (size_t)(noutput_items - 1) * nonoverlap + h->K;
-        const size_t span_al = (span + 1) & ~(size_t)1;       // streams two samples apart: pair-load aligned
-        const size_t in_bytes = span_al * N * sb;
-        const size_t n = (size_t)noutput_items;
-        // sections of the result block [max | argmax | cov | spectrum], each on a 256-byte boundary (the scan kernels'
-        // 16-byte stores need aligned spectrum rows)
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t pk_b = n * M * sizeof(float);
-        const size_t cov_b = cov_out ? n * N * N * sizeof(float2) : 0, spec_b = spectrum_out ? n * P * sizeof(float) : 0;
-        const size_t off_am = up(pk_b), off_cov = off_am + up(pk_b), off_spec = off_cov + up(cov_b);
-        const size_t out_bytes = off_spec + spec_b;
-        // (the gate looks at BOTH directions: a short-snapshot, long-spectrum call returns n * P * 4 bytes, and staging
-        // hundreds of MiB of spectra through the page-locked buffer -- plus a host memcpy each -- is what the chunked
-        // path below exists to avoid)
-        if (in_bytes <= kSmallCallBytes && out_bytes <= kSmallCallBytes) {
-            const size_t res_min = (size_t)h->max_batch * M * 2 * sizeof(float);
-            int rc = h->h_stage.reserve(in_bytes > out_bytes ? in_bytes : out_bytes);
-            if (rc == DOA_OK) rc = h->d_in[0].reserve(in_bytes);
-            if (rc == DOA_OK) rc = h->d_res.reserve(out_bytes > res_min ? out_bytes : res_min);
-            if (rc != DOA_OK) return rc;
-            hipStream_t st = h->hst[0];
-            char *hs = h->h_stage.as<char>();
-            const void *d_ptrs[DOA_MAX_ANT_ELE];
-            for (int k = 0; k < N; k++) {
-                memcpy(hs + (size_t)k * span_al * sb, input_items[k], span * sb);
-                d_ptrs[k] = h->d_in[0].as<char>() + (size_t)k * span_al * sb;
-            }
-            // From the upload on, every exit synchronises the stream first: a copy still reading the staging buffer
-            // would race the next call's memcpy into it.
-            auto staged = [&]() -> int {
-                DOA_HIP_TRY(hipMemcpyAsync(h->d_in[0].p, hs, in_bytes, hipMemcpyHostToDevice, st));
-                char *dr = h->d_res.as<char>();
-                float *d_mx = reinterpret_cast<float *>(dr), *d_am = reinterpret_cast<float *>(dr + off_am);
-                void *d_cov = cov_out ? (void *)(dr + off_cov) : h->d_cov.p;
-                void *d_spec = spectrum_out ? (void *)(dr + off_spec) : nullptr;            // NULL = angles only
-                const int rr = (h->fail_chunk == 0) ? (doa::set_error("music_pipeline_work: injected failure"), DOA_ERR_HIP)
-                                                    : run_dev(h, noutput_items, d_ptrs, d_cov, d_spec, d_mx, d_am, 0, st, 0);
-                if (rr < 0) return rr;
-                // (the staging buffer is free again: the upload was enqueued before the kernels on the same stream, and
-                // the download below is ordered behind them)
-                DOA_HIP_TRY(hipMemcpyAsync(hs, dr, out_bytes, hipMemcpyDeviceToHost, st));
-                return DOA_OK;
-            };
-            rc = staged();
-            h->fail_chunk = -1; h->lanes.fail_batch = -1;
-            const hipError_t se = hipStreamSynchronize(st);
-            if (rc < 0) return rc;
-            if (se != hipSuccess) { doa::set_error("music_pipeline_work: %s", hipGetErrorString(se)); return DOA_ERR_HIP; }
-            memcpy(max_out, hs, pk_b);
-            memcpy(argmax_out, hs + off_am, pk_b);
-            if (cov_out) memcpy(cov_out, hs + off_cov, cov_b);
-            if (spectrum_out) memcpy(spectrum_out, hs + off_spec, spec_b);
-            return noutput_items;
-        }
-    }
-    // Chunks of ~32 MiB of new samples alternate over two streams: while one chunk's results travel back
-    // the next chunk's samples travel in (PCIe is full duplex; the kernels themselves are ~1 % of a
-    // chunk's transfer time).  The overlap needs page-locked caller buffers; pageable ones still work.
-    size_t chunk = ((size_t)32 << 20) / (nonoverlap * N * sb);
-    chunk = chunk < 1 ? 1 : (chunk > (size_t)noutput_items ? (size_t)noutput_items : chunk);
-    const size_t span_max = (chunk - 1) * nonoverlap + h->K;
-    // distance between the device copies of the streams: 16-B aligned and staggered against the 8 KiB aliasing period
-    const size_t stride = doa::stream_stride_bytes(span_max * sb);
-    int rc = h->d_res.reserve((size_t)h->max_batch * M * 2 * sizeof(float));
-    for (auto &b : h->d_in)
-        if (rc == DOA_OK) rc = b.reserve(stride * N);
-    if (const size_t ws = doa::autocorrelate_workspace_bytes(N, h->K, h->ovl, (int)chunk); ws && rc == DOA_OK)
-        rc = h->d_work[1].reserve(ws);                 // lane 0 uses the workspace create() sized for max_batch
-    if (rc != DOA_OK) return rc;
-    float *d_mx = h->d_res.as<float>(), *d_am = d_mx + (size_t)h->max_batch * M;
-    int lane = 0, chunk_index = 0;
-    // One chunk: uploads, kernels, downloads, all on its lane's stream.  A failure anywhere in it ends the loop, and the
-    // loop's exit -- normal or not -- synchronises BOTH lanes: the other lane may still be copying to or from caller-owned
-    // host buffers, which must be quiet before this call returns.
-    auto enqueue_chunk = [&](size_t s0, size_t n, hipStream_t st) -> int {
-        const size_t span = (n - 1) * nonoverlap + h->K;
-        const void *d_ptrs[DOA_MAX_ANT_ELE];
-        for (int k = 0; k < N; k++) {
-            char *dst = h->d_in[lane].as<char>() + k * stride;
-            const char *src = static_cast<const char *>(input_items[k]) + s0 * nonoverlap * sb;
-            DOA_HIP_TRY(hipMemcpyAsync(dst, src, span * sb, hipMemcpyHostToDevice, st));
-            d_ptrs[k] = dst;
-        }
-        if (h->fail_chunk == chunk_index) { doa::set_error("music_pipeline_work: injected failure in chunk %d", chunk_index); return DOA_ERR_HIP; }
-        float2 *cov = h->d_cov.as<float2>() + s0 * N * N;
-        float *spec = spectrum_out ? h->d_spec.as<float>() + s0 * P : nullptr;         // NULL = angles only
-        const int rr = run_dev(h, (int)n, d_ptrs, cov, spec, d_mx + s0 * M, d_am + s0 * M, s0, st, lane);
-        if (rr < 0) return rr;
-        if (cov_out)
-            DOA_HIP_TRY(hipMemcpyAsync(static_cast<float2 *>(cov_out) + s0 * N * N, cov, n * N * N * sizeof(float2),
-                                       hipMemcpyDeviceToHost, st));
-        if (spectrum_out)
-            DOA_HIP_TRY(hipMemcpyAsync(static_cast<float *>(spectrum_out) + s0 * P, spec, n * P * sizeof(float),
-                                       hipMemcpyDeviceToHost, st));
-        DOA_HIP_TRY(hipMemcpyAsync(static_cast<float *>(max_out) + s0 * M, d_mx + s0 * M, n * M * sizeof(float),
-                                   hipMemcpyDeviceToHost, st));
-        DOA_HIP_TRY(hipMemcpyAsync(static_cast<float *>(argmax_out) + s0 * M, d_am + s0 * M, n * M * sizeof(float),
-                                   hipMemcpyDeviceToHost, st));
-        return DOA_OK;
-    };
-    for (size_t s0 = 0; s0 < (size_t)noutput_items; s0 += chunk, lane ^= 1, chunk_index++) {
-        const size_t n = ((size_t)noutput_items - s0 < chunk) ? (size_t)noutput_items - s0 : chunk;
-        rc = enqueue_chunk(s0, n, h->hst[lane]);
-        if (rc < 0) break;
-    }
-    h->fail_chunk = -1; h->lanes.fail_batch = -1;
-    for (auto st : h->hst) {
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess && rc >= 0) { doa::set_error("music_pipeline_work: %s", hipGetErrorString(e)); rc = DOA_ERR_HIP; }
-    }
-    return rc < 0 ? rc : noutput_items;
+    const char *who = "music_pipeline_work";
+    if (const int rc = h->host_open(who, input_items); rc != DOA_OK) return rc;
+    const size_t N = h->N, M = h->music.M, P = h->peaks.L;
+    // [max | argmax | cov | spectrum]; on the chunked path the peaks lie in the transport's result block, the covariances
+    // and spectra in the handle's own d_cov and d_spec at their item offsets
+    const doa::HostSection sec[4] = {{max_out, M * sizeof(float), nullptr}, {argmax_out, M * sizeof(float), nullptr},
+                                     {cov_out, N * N * sizeof(float2), h->d_cov.p}, {spectrum_out, P * sizeof(float), h->d_spec.p}};
+    return h->host_run(who, noutput_items, input_items, sec, 4,
+                       [h](int n, const void *const *d_in, size_t item_off, void *const *d_sec, hipStream_t st, int lane) {
+                           void *cov = d_sec[2] ? d_sec[2] : h->d_cov.as<float2>() + item_off * h->N * h->N;
+                           // (no spectrum section = angles only)
+                           return run_dev(h, n, d_in, cov, d_sec[3], d_sec[0], d_sec[1], item_off, st, lane);
+                       });
 }
 
 int doa_music_pipeline_inject_failure(doa_music_pipeline_t *h, int chunk_index)
 {
     doa::clear_error();
     if (!h || chunk_index < -1) { doa::set_error("music_pipeline_inject_failure: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    h->fail_chunk = chunk_index;            // whichever entry is called next consumes it: the host entry (chunk index) ...
-    h->lanes.fail_batch = chunk_index;      // ... or the batches entry (batch index); both clear both
-    return DOA_OK;
+    return h->inject_failure(chunk_index);
 }
 
 int doa_music_pipeline_lanes_idle(doa_music_pipeline_t *h)
 {
     doa::clear_error();
     if (!h) { doa::set_error("music_pipeline_lanes_idle: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    for (auto st : h->hst)
-        if (st && hipStreamQuery(st) != hipSuccess) return 0;
-    return h->lanes.idle() ? 1 : 0;
+    return h->lanes_idle();
 }
 
 int doa_music_pipeline_set_internal_precision(doa_music_pipeline_t *h, int bits)
 {
     doa::clear_error();
     if (!h || (bits != 32 && bits != 64)) { doa::set_error("music_pipeline_set_internal_precision: need a handle and bits = 32 or 64"); return DOA_ERR_INVALID_ARG; }
-    if (doa::music_uses_cheb(evd_elements(h), bits)) {
+    if (doa::music_uses_cheb(h->elements(), bits)) {
         if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
         const int rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double));
         if (rc != DOA_OK) return rc;

@@ -781,11 +781,79 @@ class calibrate_lin_array(_ItemBlock):
                                                           _dev_ptr(d_out_ptr), _stream_ptr(stream)))
 
 
-class music_pipeline(_StreamInput, _Block):
+class _Pipeline(_StreamInput, _Block):
+    """Base of the two fused handles (music_pipeline, root_pipeline): the autocorrelate front, the lanes and the test aids,
+    which their C entries share word for word (csrc/pipeline_front.hpp).  The C functions are doa_<_prefix>_<name>."""
+
+    _prefix = None
+
+    @classmethod
+    def _fn(cls, name):
+        return getattr(lib, f"doa_{cls._prefix}_{name}")
+
+    def history(self) -> int:
+        return self.overlap_size + 1                          # as doa.autocorrelate (autocorrelate_impl.cc:56-57)
+
+    def forecast(self, noutput_items: int) -> int:
+        return (self.snapshot_size - self.overlap_size) * int(noutput_items)
+
+    def input_span(self, noutput_items) -> int:
+        n = int(noutput_items)
+        return 0 if n <= 0 else (n - 1) * (self.snapshot_size - self.overlap_size) + self.snapshot_size
+
+    def fuse_antenna_correction(self, correction) -> None:
+        _fuse(self._fn("fuse_antenna_correction"), self._h, correction, self.inputs)
+
+    def set_spatial_smoothing(self, subarray_size, forward_backward=True) -> None:
+        """Spatial smoothing between K1 and the eigen stage (coherent sources), from the next work call on, in every entry:
+        the eigen stage and what follows it (scan and peak pick, or the root finder) then run for subarray_size elements
+        (num_targets < subarray_size <= inputs; for root_pipeline choose subarray_size >= num_targets + 2); the covariance
+        output stays inputs x inputs; work_dev_auto's eigenvalues are subarray_size per item.  0 switches it off
+        (doa_music_pipeline_set_spatial_smoothing, doa_root_pipeline_set_spatial_smoothing)."""
+        check(self._fn("set_spatial_smoothing")(self._h, int(subarray_size), int(forward_backward)))
+        self.subarray_size = int(subarray_size)
+        self.forward_backward = int(forward_backward) if self.subarray_size else 0
+
+    def inject_failure(self, chunk_index: int) -> None:
+        """Test aid: the next work() / work_dev_batches() call fails in chunk / batch `chunk_index` as if a HIP call had
+        (one-shot; -1 disarms)."""
+        check(self._fn("inject_failure")(self._h, int(chunk_index)))
+
+    def lanes_idle(self) -> bool:
+        """Test aid: True when neither copy/compute lane of the host-buffer entry has work pending."""
+        return bool(check(self._fn("lanes_idle")(self._h)))
+
+    def set_lanes(self, n_lanes: int) -> None:
+        check(self._fn("set_lanes")(self._h, int(n_lanes)))
+
+    def set_lane_streams(self, streams) -> None:
+        """Lanes on streams the caller created (torch.cuda.Stream objects or hipStream_t values); the caller keeps them alive."""
+        self._lane_streams = list(streams)
+        check(self._fn("set_lane_streams")(self._h, len(self._lane_streams),
+                                           ptr_array([_stream_ptr(s).value or 0 for s in self._lane_streams])))
+
+    def synchronize(self) -> None:
+        """Host-side join of the lanes (after work_dev_batches(..., stream=doa.DETACHED))."""
+        check(self._fn("synchronize")(self._h))
+
+    def _flat_inputs(self, nb, d_input_ptrs):
+        """prepare_batches: nb lists of `inputs` device pointers (or one flat list) as one pointer array."""
+        flat = [p for b in d_input_ptrs for p in b] if nb and isinstance(d_input_ptrs[0], (list, tuple)) else list(d_input_ptrs)
+        assert len(flat) == nb * self.inputs
+        return ptr_array(flat)
+
+    @staticmethod
+    def _opt_ptrs(ptrs):
+        """prepare_batches: an optional list of device pointers (0 / None = not wanted), or None."""
+        return None if ptrs is None else ptr_array([int(p or 0) for p in ptrs])
+
+
+class music_pipeline(_Pipeline):
     """autocorrelate -> MUSIC_lin_array -> find_local_max(num_targets, pspectrum_len, 0, 180) on
     device-resident streams (the wiring of apps/run_MUSIC_lin_array_simulation.grc); the batch
     entry point the benchmark drives.  Not a block of the reference."""
 
+    _prefix = "music_pipeline"
     _destroy = staticmethod(lib.doa_music_pipeline_destroy)
     _set_precision = staticmethod(lib.doa_music_pipeline_set_internal_precision)
     _set_format = staticmethod(lib.doa_music_pipeline_set_input_format)
@@ -807,12 +875,6 @@ class music_pipeline(_StreamInput, _Block):
         self.in_sig = [(_C64, 1)] * self.inputs
         self.out_sig = [(_F32, self.num_targets), (_F32, self.num_targets), (_F32, self.pspectrum_len)]
 
-    def history(self) -> int:
-        return self.overlap_size + 1                          # as doa.autocorrelate (autocorrelate_impl.cc:56-57)
-
-    def forecast(self, noutput_items: int) -> int:
-        return (self.snapshot_size - self.overlap_size) * int(noutput_items)
-
     def general_work(self, noutput_items, input_items, output_items):
         """output_items = [argmax [>=n, M], max [>=n, M], spectrum [>=n, P]] (trailing ports may be omitted).
         Returns (items produced, items consumed per input)."""
@@ -825,18 +887,6 @@ class music_pipeline(_StreamInput, _Block):
             sp = output_items[2][done:done + k] if len(output_items) > 2 else None
             done += self.work(k, [self._samples(a)[done * S:] for a in input_items], mx, am, spectrum_out=sp)
         return done, self.forecast(done)
-
-    def fuse_antenna_correction(self, correction) -> None:
-        _fuse(lib.doa_music_pipeline_fuse_antenna_correction, self._h, correction, self.inputs)
-
-    def set_spatial_smoothing(self, subarray_size, forward_backward=True) -> None:
-        """Spatial smoothing between K1 and the eigen stage (coherent sources), from the next work call on, in every entry:
-        eigen stage, scan and peak pick then run for subarray_size elements (num_targets < subarray_size <= inputs); the
-        covariance output stays inputs x inputs; work_dev_auto's eigenvalues are subarray_size per item.  0 switches it off
-        (doa_music_pipeline_set_spatial_smoothing)."""
-        check(lib.doa_music_pipeline_set_spatial_smoothing(self._h, int(subarray_size), int(forward_backward)))
-        self.subarray_size = int(subarray_size)
-        self.forward_backward = int(forward_backward) if self.subarray_size else 0
 
     def set_estimator(self, estimator, diagonal_loading=0.0) -> None:
         """ "music" (the default) or "capon": from the next work call on, the eigen launch is replaced by the Capon inverse
@@ -869,14 +919,6 @@ class music_pipeline(_StreamInput, _Block):
         """Profiling aid: drop stages from later work_dev calls (their outputs keep the previous call's values)."""
         check(lib.doa_music_pipeline_set_stages(self._h, (1 if cov else 0) | (2 if evd else 0) | (4 if scan else 0)))
 
-    def inject_failure(self, chunk_index: int) -> None:
-        """Test aid: the next work() call fails in chunk `chunk_index` as if a HIP call had (one-shot; -1 disarms)."""
-        check(lib.doa_music_pipeline_inject_failure(self._h, int(chunk_index)))
-
-    def lanes_idle(self) -> bool:
-        """Test aid: True when neither copy/compute lane of the host-buffer entry has work pending."""
-        return bool(check(lib.doa_music_pipeline_lanes_idle(self._h)))
-
     def work_dev(self, noutput_items, d_input_ptrs, d_cov_ptr, d_spec_ptr, d_max_ptr, d_argmax_ptr, stream=None) -> int:
         return check(lib.doa_music_pipeline_work_dev(
             self._h, int(noutput_items), ptr_array(d_input_ptrs), C.c_void_p(int(d_cov_ptr or 0)),
@@ -892,19 +934,6 @@ class music_pipeline(_StreamInput, _Block):
             self._h, int(noutput_items), ptr_array(d_input_ptrs), _count_method(method), _opt_ptr(d_cov_ptr), _opt_ptr(d_spec_ptr),
             _opt_ptr(d_max_ptr), _opt_ptr(d_argmax_ptr), _opt_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _stream_ptr(stream)))
 
-    def set_lanes(self, n_lanes: int) -> None:
-        check(lib.doa_music_pipeline_set_lanes(self._h, int(n_lanes)))
-
-    def set_lane_streams(self, streams) -> None:
-        """Lanes on streams the caller created (torch.cuda.Stream objects or hipStream_t values); the caller keeps them alive."""
-        self._lane_streams = list(streams)
-        check(lib.doa_music_pipeline_set_lane_streams(self._h, len(self._lane_streams),
-                                                      ptr_array([_stream_ptr(s).value or 0 for s in self._lane_streams])))
-
-    def synchronize(self) -> None:
-        """Host-side join of the lanes (after work_dev_batches(..., stream=doa.DETACHED))."""
-        check(lib.doa_music_pipeline_synchronize(self._h))
-
     def work_dev_batches(self, noutput_items, d_input_ptrs, d_cov_ptrs, d_spec_ptrs, d_max_ptrs, d_argmax_ptrs, stream=None) -> int:
         """n_batches = len(d_max_ptrs) batches in one call, overlapped over the handle's own lanes (doa_hip.h).
         d_input_ptrs: n_batches lists of `inputs` device pointers (or one flat list); d_cov_ptrs / d_spec_ptrs: lists of
@@ -915,17 +944,11 @@ class music_pipeline(_StreamInput, _Block):
         """The argument marshalling of work_dev_batches done once: returns a callable that makes the C call (a C or C++
         caller has its pointer arrays at hand; a Python caller that repeats a call should not rebuild them every time)."""
         nb = len(d_max_ptrs)
-        flat = [p for b in d_input_ptrs for p in b] if nb and isinstance(d_input_ptrs[0], (list, tuple)) else list(d_input_ptrs)
-        assert len(flat) == nb * self.inputs and len(d_argmax_ptrs) == nb
-        opt = lambda ptrs: None if ptrs is None else ptr_array([int(p or 0) for p in ptrs])
-        args = (self._h, nb, int(noutput_items), ptr_array(flat), opt(d_cov_ptrs), opt(d_spec_ptrs), ptr_array(d_max_ptrs),
-                ptr_array(d_argmax_ptrs), _stream_ptr(stream))
+        assert len(d_argmax_ptrs) == nb
+        args = (self._h, nb, int(noutput_items), self._flat_inputs(nb, d_input_ptrs), self._opt_ptrs(d_cov_ptrs),
+                self._opt_ptrs(d_spec_ptrs), ptr_array(d_max_ptrs), ptr_array(d_argmax_ptrs), _stream_ptr(stream))
         fn = lib.doa_music_pipeline_work_dev_batches
         return lambda: check(fn(*args))
-
-    def input_span(self, noutput_items) -> int:
-        n = int(noutput_items)
-        return 0 if n <= 0 else (n - 1) * (self.snapshot_size - self.overlap_size) + self.snapshot_size
 
     def work(self, noutput_items, input_items, max_out, argmax_out, cov_out=None, spectrum_out=None) -> int:
         """Host buffers in, host buffers out (numpy): input_items[k] = complex64 stream k starting at
@@ -955,12 +978,13 @@ class music_pipeline_sc16(music_pipeline):
         self.in_sig = [(_I16, 2)] * self.inputs
 
 
-class root_pipeline(_StreamInput, _Block):
+class root_pipeline(_Pipeline):
     """autocorrelate -> rootMUSIC_linear_array on device-resident streams (the wiring of
     apps/run_RootMUSIC_lin_array_simulation.grc) as ONE handle: the Root-MUSIC branch of the hot path with the same entry
     points as music_pipeline (work_dev, work_dev_batches over the handle's lanes, detached form, host-buffer work).
     Not a block of the reference."""
 
+    _prefix = "root_pipeline"
     _destroy = staticmethod(lib.doa_root_pipeline_destroy)
     _set_precision = staticmethod(lib.doa_root_pipeline_set_internal_precision)
     _set_format = staticmethod(lib.doa_root_pipeline_set_input_format)
@@ -978,16 +1002,6 @@ class root_pipeline(_StreamInput, _Block):
         self.in_sig = [(_C64, 1)] * self.inputs
         self.out_sig = [(_F32, self.num_targets)]
 
-    def history(self) -> int:
-        return self.overlap_size + 1                          # as doa.autocorrelate (autocorrelate_impl.cc:56-57)
-
-    def forecast(self, noutput_items: int) -> int:
-        return (self.snapshot_size - self.overlap_size) * int(noutput_items)
-
-    def input_span(self, noutput_items) -> int:
-        n = int(noutput_items)
-        return 0 if n <= 0 else (n - 1) * (self.snapshot_size - self.overlap_size) + self.snapshot_size
-
     def general_work(self, noutput_items, input_items, output_items):
         """output_items = [angles [>=n, M]].  Returns (items produced, items consumed per input)."""
         n, done = int(noutput_items), 0
@@ -996,18 +1010,6 @@ class root_pipeline(_StreamInput, _Block):
             k = min(self.max_batch, n - done)
             done += self.work(k, [self._samples(a)[done * S:] for a in input_items], output_items[0][done:done + k])
         return done, self.forecast(done)
-
-    def fuse_antenna_correction(self, correction) -> None:
-        _fuse(lib.doa_root_pipeline_fuse_antenna_correction, self._h, correction, self.inputs)
-
-    def set_spatial_smoothing(self, subarray_size, forward_backward=True) -> None:
-        """Spatial smoothing between K1 and the eigen stage (coherent sources), from the next work call on, in every entry:
-        eigen stage and root finder then run for subarray_size elements (num_targets < subarray_size <= inputs; choose
-        subarray_size >= num_targets + 2); the covariance output stays inputs x inputs; work_dev_auto's eigenvalues are
-        subarray_size per item.  0 switches it off (doa_root_pipeline_set_spatial_smoothing)."""
-        check(lib.doa_root_pipeline_set_spatial_smoothing(self._h, int(subarray_size), int(forward_backward)))
-        self.subarray_size = int(subarray_size)
-        self.forward_backward = int(forward_backward) if self.subarray_size else 0
 
     def set_estimator(self, estimator) -> None:
         """ "root_music" (the default) or "esprit": from the next work call on, in every entry, the eigen launch writes the
@@ -1018,13 +1020,6 @@ class root_pipeline(_StreamInput, _Block):
             raise ValueError(f"unknown estimator {estimator!r} (root_music or esprit)")
         check(lib.doa_root_pipeline_set_estimator(self._h, _GRIDFREE[estimator.lower()]))
         self.estimator = estimator.lower()
-
-    def inject_failure(self, chunk_index: int) -> None:
-        """Test aid: the next work() / work_dev_batches() call fails in chunk / batch `chunk_index` (one-shot; -1 disarms)."""
-        check(lib.doa_root_pipeline_inject_failure(self._h, int(chunk_index)))
-
-    def lanes_idle(self) -> bool:
-        return bool(check(lib.doa_root_pipeline_lanes_idle(self._h)))
 
     def work_dev(self, noutput_items, d_input_ptrs, d_cov_ptr, d_angles_ptr, d_status_ptr=None, stream=None) -> int:
         return check(lib.doa_root_pipeline_work_dev(
@@ -1041,28 +1036,14 @@ class root_pipeline(_StreamInput, _Block):
             self._h, int(noutput_items), ptr_array(d_input_ptrs), _count_method(method), _opt_ptr(d_cov_ptr), _opt_ptr(d_angles_ptr),
             _opt_ptr(d_count_ptr), _opt_ptr(d_eig_ptr), _opt_ptr(d_status_ptr), _stream_ptr(stream)))
 
-    def set_lanes(self, n_lanes: int) -> None:
-        check(lib.doa_root_pipeline_set_lanes(self._h, int(n_lanes)))
-
-    def set_lane_streams(self, streams) -> None:
-        self._lane_streams = list(streams)
-        check(lib.doa_root_pipeline_set_lane_streams(self._h, len(self._lane_streams),
-                                                     ptr_array([_stream_ptr(s).value or 0 for s in self._lane_streams])))
-
-    def synchronize(self) -> None:
-        check(lib.doa_root_pipeline_synchronize(self._h))
-
     def work_dev_batches(self, noutput_items, d_input_ptrs, d_cov_ptrs, d_angles_ptrs, d_status_ptrs=None, stream=None) -> int:
         return self.prepare_batches(noutput_items, d_input_ptrs, d_cov_ptrs, d_angles_ptrs, d_status_ptrs, stream)()
 
     def prepare_batches(self, noutput_items, d_input_ptrs, d_cov_ptrs, d_angles_ptrs, d_status_ptrs=None, stream=None):
         """The argument marshalling of work_dev_batches done once: returns a callable that makes the C call."""
         nb = len(d_angles_ptrs)
-        flat = [p for b in d_input_ptrs for p in b] if nb and isinstance(d_input_ptrs[0], (list, tuple)) else list(d_input_ptrs)
-        assert len(flat) == nb * self.inputs
-        opt = lambda ptrs: None if ptrs is None else ptr_array([int(p or 0) for p in ptrs])
-        args = (self._h, nb, int(noutput_items), ptr_array(flat), opt(d_cov_ptrs), ptr_array(d_angles_ptrs), opt(d_status_ptrs),
-                _stream_ptr(stream))
+        args = (self._h, nb, int(noutput_items), self._flat_inputs(nb, d_input_ptrs), self._opt_ptrs(d_cov_ptrs),
+                ptr_array(d_angles_ptrs), self._opt_ptrs(d_status_ptrs), _stream_ptr(stream))
         fn = lib.doa_root_pipeline_work_dev_batches
         return lambda: check(fn(*args))
 

@@ -220,37 +220,56 @@ def test_angles_only_mode_equals_the_full_pipeline(name):
     assert np.array_equal(h0, out["full"][0], equal_nan=True) and np.array_equal(h1, out["full"][1], equal_nan=True)
 
 
-@pytest.mark.parametrize("fail_chunk,small", [(0, False), (1, False), (2, False), (0, True)])
-def test_host_entry_failure_leaves_no_copy_in_flight(fail_chunk, small):
-    """VERDICT r2 #7 / ADVICE r2: a failure inside doa_music_pipeline_work -- in any chunk of the two-lane chunk loop, or
-    in the staged scheduler-sized path -- must not return while the other lane (or the staging upload) is still copying
-    to or from the caller's host buffers.  doa_music_pipeline_inject_failure makes chunk `fail_chunk` fail after its
+def _host_entry_handle(handle, N, K, d, M, P, n):
+    """One of the fused handles with its host entry in a common form: (handle, a function that makes its output arrays with
+    every optional output, a function that runs work() on them, the index of the angles among them)."""
+    if handle == "music":
+        pipe = doa.music_pipeline(N, K, 0, 0, d, M, P, max_batch=n)
+        outs = lambda: [np.full((n, M), -7.0, np.float32), np.full((n, M), -7.0, np.float32), np.zeros((n, N * N), np.complex64),
+                        np.zeros((n, P), np.float32)]
+        return pipe, outs, lambda h, x, o: h.work(n, x, o[0], o[1], cov_out=o[2], spectrum_out=o[3]), 1
+    pipe = doa.root_pipeline(N, K, 0, 0, d, M, max_batch=n)
+    if handle == "root_esprit":
+        pipe.set_estimator("esprit")
+    outs = lambda: [np.full((n, M), -7.0, np.float32), np.zeros((n, N * N), np.complex64)]
+    return pipe, outs, lambda h, x, o: h.work(n, x, o[0], cov_out=o[1]), 0
+
+
+_HOST_FAILURES = [(0, False), (1, False), (2, False), (0, True)]
+
+
+# (the music handle's cases keep the ids they had before the root handle's joined them)
+@pytest.mark.parametrize("fail_chunk,small,handle",
+                         [c + ("music",) for c in _HOST_FAILURES] + [c + ("root",) for c in _HOST_FAILURES] + [(0, True, "root_esprit")],
+                         ids=[f"{c}-{s}" for c, s in _HOST_FAILURES] + [f"root-{c}-{s}" for c, s in _HOST_FAILURES] + ["root_esprit-0-True"])
+def test_host_entry_failure_leaves_no_copy_in_flight(fail_chunk, small, handle):
+    """VERDICT r2 #7 / ADVICE r2: a failure inside doa_music_pipeline_work / doa_root_pipeline_work -- in any chunk of the
+    two-lane chunk loop, or in the staged scheduler-sized path -- must not return while the other lane (or the staging
+    upload) is still copying to or from the caller's host buffers.  inject_failure makes chunk `fail_chunk` fail after its
     uploads were enqueued; the call must report DOA_ERR_HIP, both lanes must be idle on return, and the next call on the
-    same handle must succeed and match a call on a fresh handle bit for bit."""
+    same handle must succeed and match a call on a fresh handle bit for bit.  Both handles share the transport
+    (csrc/pipeline_front.hpp); each runs the four cases, the root handle the staged one in ESPRIT mode as well."""
     N, K, P, d, M = 4, 1024, 1024, 0.5, 1
     n = 24 if small else 2 * ((32 << 20) // (K * N * 8)) + 77            # three chunks over two lanes, or one staged call
     x = doa.sim.make_streams(N, n * K, [64.0], d, snr_db=15.0, seed=11)
-    pipe = doa.music_pipeline(N, K, 0, 0, d, M, P, max_batch=n)
-    mx, am = np.full((n, M), -7.0, np.float32), np.full((n, M), -7.0, np.float32)
-    cov = np.zeros((n, N * N), np.complex64)
-    spec = np.zeros((n, P), np.float32)
+    pipe, outs, work, angles = _host_entry_handle(handle, N, K, d, M, P, n)
+    out = outs()
     pipe.inject_failure(fail_chunk)
     with pytest.raises(doa.DoaError) as ei:
-        pipe.work(n, [x[k] for k in range(N)], mx, am, cov_out=cov, spectrum_out=spec)
+        work(pipe, [x[k] for k in range(N)], out)
     assert ei.value.status == -3 and "injected failure" in str(ei.value)
     assert pipe.lanes_idle()                                           # nothing pending: the caller may reuse its buffers
     # the buffers really are the caller's again: scribble over the inputs, then run a clean call on fresh copies
     x2 = x.copy()
     x[:] = 0
-    mx2, am2 = np.empty((n, M), np.float32), np.empty((n, M), np.float32)
-    cov2, spec2 = np.empty((n, N * N), np.complex64), np.empty((n, P), np.float32)
-    assert pipe.work(n, [x2[k] for k in range(N)], mx2, am2, cov_out=cov2, spectrum_out=spec2) == n     # one-shot: disarmed
-    ref = doa.music_pipeline(N, K, 0, 0, d, M, P, max_batch=n)
-    mx3, am3 = np.empty((n, M), np.float32), np.empty((n, M), np.float32)
-    cov3, spec3 = np.empty((n, N * N), np.complex64), np.empty((n, P), np.float32)
-    assert ref.work(n, [x2[k] for k in range(N)], mx3, am3, cov_out=cov3, spectrum_out=spec3) == n
-    assert np.array_equal(mx2, mx3) and np.array_equal(am2, am3) and np.array_equal(cov2, cov3) and np.array_equal(spec2, spec3)
-    assert np.abs(am2 - 64.0).max() <= 1.0
+    out2 = outs()
+    assert work(pipe, [x2[k] for k in range(N)], out2) == n             # one-shot: disarmed
+    ref, _, _, _ = _host_entry_handle(handle, N, K, d, M, P, n)
+    out3 = outs()
+    assert work(ref, [x2[k] for k in range(N)], out3) == n
+    for got, want in zip(out2, out3):
+        assert np.array_equal(got, want)
+    assert np.abs(out2[angles] - 64.0).max() <= 1.0
 
 
 def test_host_entry_short_snapshot_long_spectrum_takes_the_chunked_path():
