@@ -334,7 +334,7 @@ int launch_find_local_max_counts(const PeakTables &t, int n_items, const void *d
     return launch_find_local_max_routes(t, n_items, d_in, (const int *)d_counts, d_max, d_argmax, st);
 }
 
-int launch_find_local_max_serial(const PeakTables &t, int n_items, const void *d_in, void *d_max, void *d_argmax,
+static int launch_find_local_max_serial(const PeakTables &t, int n_items, const void *d_in, void *d_max, void *d_argmax,
                                  void *d_scratch, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
@@ -345,7 +345,7 @@ int launch_find_local_max_serial(const PeakTables &t, int n_items, const void *d
     return DOA_OK;
 }
 
-int launch_find_local_max_serial_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
+static int launch_find_local_max_serial_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
                                         void *d_argmax, void *d_scratch, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
@@ -357,10 +357,22 @@ int launch_find_local_max_serial_counts(const PeakTables &t, int n_items, const 
     return DOA_OK;
 }
 
-bool find_local_max_fast_ok(int L, const void *d_in)
+static bool find_local_max_fast_ok(int L, const void *d_in)
 {
     (void)d_in;                                          // the streaming kernel takes any alignment
     return L >= 1 && L <= 4096;
+}
+
+int launch_peak_pick(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max, void *d_argmax,
+                     DevBuf &scratch, size_t reserve_items, size_t item_off, hipStream_t st)
+{
+    if (find_local_max_fast_ok(t.L, d_in))
+        return d_counts ? launch_find_local_max_counts(t, n_items, d_in, d_counts, d_max, d_argmax, st)
+                        : launch_find_local_max(t, n_items, d_in, d_max, d_argmax, st);
+    if (const int rc = scratch.reserve(reserve_items * t.L); rc != DOA_OK) return rc;
+    void *rows = scratch.as<char>() + item_off * t.L;
+    return d_counts ? launch_find_local_max_serial_counts(t, n_items, d_in, d_counts, d_max, d_argmax, rows, st)
+                    : launch_find_local_max_serial(t, n_items, d_in, d_max, d_argmax, rows, st);
 }
 
 }  // namespace doa
@@ -421,16 +433,8 @@ int doa_find_local_max_work_dev(doa_find_local_max_t *h, int noutput_items, cons
         return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    int rc;
-    if (doa::find_local_max_fast_ok(h->tab.L, d_input_items0)) {
-        rc = doa::launch_find_local_max(h->tab, noutput_items, d_input_items0, d_output_items0, d_output_items1, st);
-    } else {
-        rc = h->d_scratch.reserve((size_t)noutput_items * h->tab.L);
-        if (rc == DOA_OK)
-            rc = doa::launch_find_local_max_serial(h->tab, noutput_items, d_input_items0, d_output_items0,
-                                                   d_output_items1, h->d_scratch.p, st);
-    }
+    const int rc = doa::launch_peak_pick(h->tab, noutput_items, d_input_items0, nullptr, d_output_items0, d_output_items1, h->d_scratch,
+                                         (size_t)noutput_items, 0, static_cast<hipStream_t>(hip_stream));
     return rc == DOA_OK ? noutput_items : rc;
 }
 
@@ -452,16 +456,8 @@ int doa_find_local_max_work_dev_counts(doa_find_local_max_t *h, int noutput_item
         return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    int rc;
-    if (doa::find_local_max_fast_ok(h->tab.L, d_input_items0)) {
-        rc = doa::launch_find_local_max_counts(h->tab, noutput_items, d_input_items0, d_counts, d_output_items0, d_output_items1, st);
-    } else {
-        rc = h->d_scratch.reserve((size_t)noutput_items * h->tab.L);
-        if (rc == DOA_OK)
-            rc = doa::launch_find_local_max_serial_counts(h->tab, noutput_items, d_input_items0, d_counts, d_output_items0,
-                                                          d_output_items1, h->d_scratch.p, st);
-    }
+    const int rc = doa::launch_peak_pick(h->tab, noutput_items, d_input_items0, d_counts, d_output_items0, d_output_items1, h->d_scratch,
+                                         (size_t)noutput_items, 0, static_cast<hipStream_t>(hip_stream));
     return rc == DOA_OK ? noutput_items : rc;
 }
 

@@ -196,8 +196,10 @@ int launch_find_local_max(const PeakTables &t, int n_items, const void *d_in, vo
 // serial kernel (d_scratch: L bytes per item).
 int launch_find_local_max_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
                                  void *d_argmax, hipStream_t st);
-int launch_find_local_max_serial_counts(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max,
-                                        void *d_argmax, void *d_scratch, hipStream_t st);
+// K5 on whichever route takes the vector length (d_counts: optional, as above): the parallel kernels for L <= 4096, else the
+// serial kernel, for which `scratch` is grown to L bytes for each of `reserve_items` items and used from item `item_off` on
+int launch_peak_pick(const PeakTables &t, int n_items, const void *d_in, const void *d_counts, void *d_max, void *d_argmax,
+                     DevBuf &scratch, size_t reserve_items, size_t item_off, hipStream_t st);
 
 // K6 (root_music.hip): polynomial roots from the DOUBLE coefficient records -> angles.
 // d_roots (optional, diagnostics): the 2N-2 roots found per item as double2, in the kernel's lane order.

@@ -9,34 +9,27 @@
 #include "pipeline_front.hpp"
 
 #include <cmath>
-#include <string>
 #include <utility>
-#include <vector>
-
-namespace doa {
-bool find_local_max_fast_ok(int L, const void *d_in);
-int launch_find_local_max_serial(const PeakTables &t, int n_items, const void *d_in, void *d_max, void *d_argmax,
-                                 void *d_scratch, hipStream_t st);
-}  // namespace doa
 
 // the front (K1, smoothing, the host entry's transport, the lanes) is doa::PipeFront's; these are the estimator stage's
 struct doa_music_pipeline : doa::PipeFront {
     unsigned stages = 7;           // bit 0 K1, bit 1 K2+K3, bit 2 K4+K5 (doa_music_pipeline_set_stages)
     doa::MusicTables music;
     doa::PeakTables peaks;
-    doa::DevBuf d_coef, d_cheb, d_spec, d_scratch;
     int estimator = DOA_ESTIMATOR_MUSIC;    // doa_music_pipeline_set_estimator
     double loading = 0.0;           // Capon: the diagonal loading
-    doa::DevBuf d_status;           // Capon: int32 per item between the inverse launch and the NaN follow-up
     bool has_table = false;         // doa_music_pipeline_set_steering_table: an arbitrary array geometry
     doa::ArrayTable array;          // its table in the scan's form (array_scan.hip)
-    doa::DevBuf d_full;             // the full records (N * N doubles per item) between the stage in front and the scan
-    // doa_music_pipeline_work_dev_batches: a lane's buffers
-    enum { kCoef = 0, kCheb, kCov, kSpec, kWork, kScratch, kSmooth, kStatus, kFull };
+    // a lane's slots after the front's: coefficient records, their Chebyshev twins, spectrum rows nobody asked for, the serial
+    // peak pick's scratch, Capon's status words (int32 per item between the inverse launch and the NaN follow-up), a
+    // steering-table handle's full records (N * N doubles per item between the stage in front and the scan)
+    enum { kCoef = kFrontBufs, kCheb, kSpec, kScratch, kStatus, kFull };
 };
+static_assert(doa_music_pipeline::kFull < doa::PipeLane::kBufs, "a lane has a buffer per slot");
 
 // what one K1 -> EVD -> scan chain needs besides its inputs and outputs
 struct PipeWs {
+    void *cov;              // covariance items, for a chain whose caller does not ask for them
     void *coef;             // coefficient records of the chain's items
     void *cheb;             // N <= 4, double: their pre-transformed twins for the lean scan kernel (else NULL)
     void *spec_scratch;     // P floats per item, used when the caller does not want the spectrum
@@ -91,14 +84,7 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
         if (skip & 4) return n;
         rc = doa::launch_array_scan(h->array, n, ws.full, spec, nullptr, st);
         if (rc != DOA_OK) return rc;
-        if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
-            rc = doa::launch_find_local_max(h->peaks, n, spec, mx, am, st);
-        } else {
-            rc = ws.scratch->reserve((size_t)h->max_batch * h->peaks.L);
-            if (rc == DOA_OK)
-                rc = doa::launch_find_local_max_serial(h->peaks, n, spec, mx, am,
-                                                       static_cast<char *>(ws.scratch->p) + ws.scratch_item_off * h->peaks.L, st);
-        }
+        rc = doa::launch_peak_pick(h->peaks, n, spec, nullptr, mx, am, *ws.scratch, (size_t)h->max_batch, ws.scratch_item_off, st);
         if (rc == DOA_OK && capon && !(skip & 2))
             rc = doa::launch_capon_invalid_rows(h->peaks.L, h->peaks.M, n, ws.status, store_spec ? spec : nullptr, mx, am, st);
         return rc == DOA_OK ? n : rc;
@@ -114,16 +100,8 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
     if (skip & 4) return n;
     rc = doa::launch_music_scan(h->music, h->bits, n, coef, spec, nullptr, st, &h->peaks, mx, am, &peaks_done, store_spec, ws.cheb);
     if (rc != DOA_OK) return rc;
-    if (!peaks_done) {
-        if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
-            rc = doa::launch_find_local_max(h->peaks, n, spec, mx, am, st);
-        } else {
-            rc = ws.scratch->reserve((size_t)h->max_batch * h->peaks.L);
-            if (rc == DOA_OK)
-                rc = doa::launch_find_local_max_serial(h->peaks, n, spec, mx, am,
-                                                       static_cast<char *>(ws.scratch->p) + ws.scratch_item_off * h->peaks.L, st);
-        }
-    }
+    if (!peaks_done)
+        rc = doa::launch_peak_pick(h->peaks, n, spec, nullptr, mx, am, *ws.scratch, (size_t)h->max_batch, ws.scratch_item_off, st);
     // Capon: the scan wrote 0.0 dB rows (and the peak pick their peaks) for the NaN records of status-1 items (with the
     // inverse launch dropped by set_stages there is no status of this call to act on)
     if (rc == DOA_OK && capon && !(skip & 2))
@@ -137,24 +115,49 @@ static int run_ws(doa_music_pipeline *h, int n, const void *const *d_in, void *c
     return rc != DOA_OK ? rc : run_evd_scan(h, n, cov, spec, mx, am, ws, st);
 }
 
-// the handle's own single workspace (work_dev and the host-pointer entry): records / scratch rows at item offset
-// `item_off` (chunks in flight on different streams must not share them)
-static int run_dev(doa_music_pipeline *h, int n, const void *const *d_in, void *cov, void *spec, void *mx, void *am,
-                   size_t item_off, hipStream_t st, int lane = 0)
+// The workspace `ln` (the handle's own, or a lane of work_dev_batches) as a chain sees it: records and rows from item `item_off`
+// on (the host entry's chunks in flight on different streams must not share them)
+static PipeWs view(doa_music_pipeline *h, doa::PipeLane &ln, size_t item_off)
 {
-    const bool dbl = (h->bits == 64);
+    using H = doa_music_pipeline;
     PipeWs ws;
-    ws.coef = static_cast<char *>(h->d_coef.p) + item_off * doa::coef_stride(h->N) * (dbl ? sizeof(double) : sizeof(float));
-    ws.cheb = h->d_cheb.p ? static_cast<char *>(h->d_cheb.p) + item_off * doa::kChebRecord * sizeof(double) : nullptr;
-    ws.spec_scratch = static_cast<char *>(h->d_spec.p) + item_off * h->peaks.L * sizeof(float);
-    ws.work = h->d_work[lane].p;
-    ws.smooth = h->S ? h->d_smooth.as<float2>() + item_off * h->S * h->S : nullptr;
-    ws.status = h->d_status.p ? h->d_status.as<int>() + item_off : nullptr;
-    ws.full = h->d_full.p ? h->d_full.as<double>() + item_off * doa::full_record_len(h->N) : nullptr;
-    ws.scratch = &h->d_scratch;
+    ws.cov = ln.at(H::kCov, item_off, (size_t)h->N * h->N * sizeof(float2));
+    ws.coef = ln.at(H::kCoef, item_off, doa::coef_stride(h->N) * (h->bits == 64 ? sizeof(double) : sizeof(float)));
+    ws.cheb = ln.at(H::kCheb, item_off, doa::kChebRecord * sizeof(double));
+    ws.spec_scratch = ln.at(H::kSpec, item_off, h->peaks.L * sizeof(float));
+    ws.work = ln.buf[H::kWork].p;
+    ws.smooth = ln.at(H::kSmooth, item_off, (size_t)h->S * h->S * sizeof(float2));
+    ws.status = ln.at(H::kStatus, item_off, sizeof(int));
+    ws.full = ln.at(H::kFull, item_off, doa::full_record_len(h->N) * sizeof(double));
+    ws.scratch = &ln.buf[H::kScratch];
     ws.scratch_item_off = item_off;
-    return run_ws(h, n, d_in, cov, spec, mx, am, ws, st);
+    return ws;
 }
+
+// what sizes a workspace besides the create parameters; a setter passes the configuration it is about to commit, so that a
+// failure leaves the handle as it was
+struct MusicCfg {
+    int S, bits, estimator;
+    bool has_table;
+};
+static MusicCfg cfg_of(const doa_music_pipeline *h) { return {h->S, h->bits, h->estimator, h->has_table}; }
+// Sizes `ln` for configuration `c`: records and covariances of up to G batches (64-128 B per item), spectrum rows of up to
+// G_angles angles-only batches; need_cov / need_spec: some batch brings no covariance / spectrum buffer of its own.  The
+// coefficient records are sized as doubles: the group launches write none, and set_internal_precision must not have to grow them.
+static int reserve(doa_music_pipeline *h, doa::PipeLane &ln, int G, int G_angles, bool need_cov, bool need_spec, const MusicCfg &c)
+{
+    using H = doa_music_pipeline;
+    const size_t items = (size_t)h->max_batch;
+    int rc = h->reserve_front(ln, need_cov ? G : 0, c.S);
+    if (rc == DOA_OK) rc = ln.buf[H::kCoef].reserve(items * doa::coef_stride(h->N) * sizeof(double));
+    if (rc == DOA_OK && doa::music_uses_cheb(c.S ? c.S : h->N, c.bits)) rc = ln.buf[H::kCheb].reserve(G * items * doa::kChebRecord * sizeof(double));
+    if (rc == DOA_OK && need_spec) rc = ln.buf[H::kSpec].reserve(G_angles * items * h->peaks.L * sizeof(float));
+    if (rc == DOA_OK && c.estimator == DOA_ESTIMATOR_CAPON) rc = ln.buf[H::kStatus].reserve(items * sizeof(int));
+    if (rc == DOA_OK && c.has_table) rc = ln.buf[H::kFull].reserve(items * doa::full_record_len(h->N) * sizeof(double));
+    return rc;
+}
+// the handle's own workspace: one batch, every buffer
+static int reserve_self(doa_music_pipeline *h, const MusicCfg &c) { return reserve(h, h->self, 1, 1, true, true, c); }
 
 extern "C" {
 
@@ -173,9 +176,7 @@ doa_music_pipeline_t *doa_music_pipeline_create(int inputs, int snapshot_size, i
     return doa::create_pipeline<doa_music_pipeline>(inputs, snapshot_size, overlap_size, avg_method, max_batch, [&](doa_music_pipeline &h) {
         int rc = h.music.build(norm_spacing, num_targets, inputs, pspectrum_len);
         if (rc == DOA_OK) rc = h.peaks.build(num_targets, pspectrum_len, 0.0f, 180.0f);
-        if (rc == DOA_OK) rc = h.d_coef.reserve((size_t)max_batch * doa::coef_stride(inputs) * sizeof(double));
-        if (rc == DOA_OK && doa::music_uses_cheb(inputs, h.bits)) rc = h.d_cheb.reserve((size_t)max_batch * doa::kChebRecord * sizeof(double));
-        if (rc == DOA_OK) rc = h.d_spec.reserve((size_t)max_batch * pspectrum_len * sizeof(float));
+        if (rc == DOA_OK) rc = reserve_self(&h, cfg_of(&h));
         return rc;
     });
 }
@@ -217,9 +218,9 @@ int doa_music_pipeline_set_spatial_smoothing(doa_music_pipeline_t *h, int subarr
     }
     int rc = h->smoothing_reserve(S, fb);
     if (rc <= 0) return rc;
-    const int elements = S ? S : h->N;
-    rc = doa::music_uses_cheb(elements, h->bits) ? h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double)) : DOA_OK;
+    rc = reserve_self(h, {S, h->bits, h->estimator, h->has_table});
     if (rc != DOA_OK) return rc;
+    const int elements = S ? S : h->N;
     // the scan's tables for `elements` antennas (the steering phases themselves depend on norm_spacing and pspectrum_len alone)
     const int was = h->music.N;
     rc = h->music.build(h->music.norm_spacing, h->music.M, elements, h->music.P);
@@ -242,7 +243,7 @@ int doa_music_pipeline_set_estimator(doa_music_pipeline_t *h, int estimator, flo
             return DOA_ERR_INVALID_ARG;
         }
         if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-        if (int rc = h->d_status.reserve((size_t)h->max_batch * sizeof(int)); rc != DOA_OK) return rc;
+        if (int rc = reserve_self(h, {h->S, h->bits, estimator, h->has_table}); rc != DOA_OK) return rc;
         h->loading = (double)diagonal_loading;
     }
     h->estimator = estimator;
@@ -283,7 +284,7 @@ int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double 
     doa::PeakTables axis;
     int rc = table.build(N, P, steering);
     if (rc == DOA_OK) rc = axis.build(M, P, x_min, x_max);
-    if (rc == DOA_OK) rc = h->d_full.reserve((size_t)h->max_batch * doa::full_record_len(N) * sizeof(double));
+    if (rc == DOA_OK) rc = reserve_self(h, {h->S, h->bits, h->estimator, true});
     if (rc != DOA_OK) { table.release(); axis.release(); return rc; }
     h->array.release(); h->peaks.release();
     h->array = std::move(table); h->peaks = std::move(axis);
@@ -306,10 +307,10 @@ int doa_music_pipeline_work_dev(doa_music_pipeline_t *h, int noutput_items, cons
     }
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    void *cov = d_cov_out ? d_cov_out : h->d_cov.p;
-    void *spec = d_spectrum_out;                       // NULL = angles only (run_dev)
-    return run_dev(h, noutput_items, d_input_items, cov, spec, d_max_out, d_argmax_out, 0,
-                   static_cast<hipStream_t>(hip_stream));
+    const PipeWs ws = view(h, h->self, 0);
+    // (no spectrum = angles only)
+    return run_ws(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : ws.cov, d_spectrum_out, d_max_out, d_argmax_out, ws,
+                  static_cast<hipStream_t>(hip_stream));
 }
 
 // K1 as work_dev runs it, ONE eigen launch that estimates each item's count and forms its noise set from it, the scan (no
@@ -351,32 +352,24 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     const int n = noutput_items;
     const int elements = h->elements();
     const bool cheb = doa::music_uses_cheb(elements, 64);
-    // (a handle created at precision 32 and switched to 64 afterwards has no Chebyshev records yet)
-    if (cheb && !h->d_cheb.p)
-        if (int rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double)); rc != DOA_OK) return rc;
-    void *cov = d_cov_out ? d_cov_out : h->d_cov.p;
-    void *spec = d_spectrum_out ? d_spectrum_out : h->d_spec.p;
-    PipeWs ws{};
-    ws.work = h->d_work[0].p;
-    int rc = run_k1(h, n, d_input_items, cov, ws, st);
-    if (rc == DOA_OK) rc = h->run_smoothing(n, cov, h->d_smooth.p, st);
+    int rc = reserve_self(h, cfg_of(h));
+    if (rc != DOA_OK) return rc;
+    const PipeWs ws = view(h, h->self, 0);
+    void *cov = d_cov_out ? d_cov_out : ws.cov;
+    void *spec = d_spectrum_out ? d_spectrum_out : ws.spec_scratch;
+    rc = run_k1(h, n, d_input_items, cov, ws, st);
+    if (rc == DOA_OK) rc = h->run_smoothing(n, cov, ws.smooth, st);
     if (rc == DOA_OK)
-        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->music.M, h->d_coef.p,
-                                          cheb ? h->d_cheb.p : nullptr, st);
+        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->music.M, ws.coef,
+                                          cheb ? ws.cheb : nullptr, st);
     if (rc == DOA_OK)
-        rc = doa::launch_music_scan(h->music, 64, n, h->d_coef.p, spec, nullptr, st, nullptr, nullptr, nullptr, nullptr, true,
-                                    cheb ? h->d_cheb.p : nullptr);
+        rc = doa::launch_music_scan(h->music, 64, n, ws.coef, spec, nullptr, st, nullptr, nullptr, nullptr, nullptr, true,
+                                    cheb ? ws.cheb : nullptr);
     // a spectrum the caller sees: the row of a count -1 item is NaN, as MUSIC_lin_array_work_dev_counts leaves it (a fifth,
     // one-load-per-item launch; the peak pick below does not read the rows of such items)
     if (rc == DOA_OK && d_spectrum_out) rc = doa::launch_music_invalid_rows(elements, h->peaks.L, n, d_count_out, spec, st);
-    if (rc != DOA_OK) return rc;
-    if (doa::find_local_max_fast_ok(h->peaks.L, spec)) {
-        rc = doa::launch_find_local_max_counts(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, st);
-    } else {
-        rc = h->d_scratch.reserve((size_t)h->max_batch * h->peaks.L);
-        if (rc == DOA_OK)
-            rc = doa::launch_find_local_max_serial_counts(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, h->d_scratch.p, st);
-    }
+    if (rc == DOA_OK)
+        rc = doa::launch_peak_pick(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, *ws.scratch, (size_t)h->max_batch, 0, st);
     return rc == DOA_OK ? n : rc;
 }
 
@@ -414,26 +407,6 @@ static int group_first() { return DOA_LAB_ENV_INT("DOA_GROUP_FIRST", 0); }     /
 // lane's scratch rows stay within kAnglesScratchBytes (or one batch's worth)
 constexpr size_t kAnglesScratchBytes = (size_t)32 << 20;
 
-namespace {
-struct PlanGroup {
-    int b0 = 0, nb = 0, cap = 1, lane = -1, req = -1;
-    bool lean = false, store = false, vec2 = false;
-    bool sync_first = false;        // its outputs alias groups on two different lanes: the lanes are joined on the host first
-};
-// output pointer -> index of the last group that writes it (open addressing; never shrinks within a call)
-struct PtrGroups {
-    std::vector<std::pair<const void *, int>> slot;
-    size_t mask;
-    explicit PtrGroups(size_t n_ptrs) { size_t c = 16; while (c < 2 * n_ptrs) c <<= 1; slot.assign(c, {nullptr, -1}); mask = c - 1; }
-    std::pair<const void *, int> &at(const void *p)
-    {
-        size_t i = (reinterpret_cast<uintptr_t>(p) * 0x9E3779B97F4A7C15ull >> 20) & mask;
-        while (slot[i].first && slot[i].first != p) i = (i + 1) & mask;
-        return slot[i];
-    }
-};
-}  // namespace
-
 int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, int noutput_items,
                                         const void *const *d_input_items, void *const *d_cov_out,
                                         void *const *d_spectrum_out, void *const *d_max_out, void *const *d_argmax_out,
@@ -456,110 +429,37 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     if (n_batches == 0 || noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const int N = h->N, n = noutput_items, P = h->peaks.L;
-    const int fail_at = h->lanes.fail_batch;
-    h->fail_chunk = -1; h->lanes.fail_batch = -1;               // (the test aid is one-shot for whichever entry comes next)
-    const bool injected = (fail_at >= 0 && fail_at < n_batches);
-    const int n_run = injected ? fail_at : n_batches;           // batches before the injected failure are launched
-    const bool solo = (h->lanes.n_lanes == 1 && hip_stream != DOA_STREAM_DETACHED);    // nothing to overlap: the caller's stream itself, no events
-    const bool dbl = (h->bits == 64);
 
-    // ---- the plan: groups of consecutive batches and their lanes ----
+    // ---- the plan (batch_plan.hpp): what makes a batch lean, and its group cap ----
     const bool lean_shape = h->estimator == DOA_ESTIMATOR_MUSIC && !h->has_table && h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
                             (long long)doa::kMaxGroup * n <= (1 << 28);
-    const int L_all = solo ? 1 : h->lanes.n_lanes;
+    const int L_all = h->lanes.n_lanes;
     const int L = (lean_shape && group_lanes() < L_all) ? group_lanes() : L_all;
     const int G = lean_shape ? group_batches(L) : 1;
     const size_t angles_rows = kAnglesScratchBytes / ((size_t)h->max_batch * P * sizeof(float));
     const int G_angles = (int)(angles_rows < 1 ? 1 : (angles_rows > (size_t)G ? (size_t)G : angles_rows));
-    int rot = h->lanes.next_lane % L;
-    std::vector<PlanGroup> plan;
-    plan.reserve((size_t)n_run / G + 8);
-    PtrGroups writers((size_t)4 * n_run);
-    auto outputs = [&](int b, const void *(&p)[4]) {
-        p[0] = d_cov_out ? d_cov_out[b] : nullptr; p[1] = d_spectrum_out ? d_spectrum_out[b] : nullptr;
-        p[2] = d_max_out[b]; p[3] = d_argmax_out[b];
-    };
-    auto close = [&](PlanGroup &g) {
-        g.lane = (g.req >= 0) ? g.req : rot++ % L;
-    };
-    for (int b = 0; b < n_run; b++) {
-        const void *out[4];
-        outputs(b, out);
-        PlanGroup nb;
-        nb.b0 = b; nb.nb = 1;
+    auto traits = [&](int b, doa::PlanGroup &nb, const void *(&out)[4]) {
+        out[0] = d_cov_out ? d_cov_out[b] : nullptr; out[1] = d_spectrum_out ? d_spectrum_out[b] : nullptr;
+        out[2] = d_max_out[b]; out[3] = d_argmax_out[b];
         nb.store = (out[1] != nullptr);
         nb.lean = lean_shape && reinterpret_cast<uintptr_t>(out[1]) % 16 == 0;
         nb.vec2 = nb.lean && doa::autocorrelate_pair_loads(N, h->K, h->ovl, d_input_items + (size_t)b * N, h->format);
         nb.cap = !nb.lean ? 1 : (nb.store ? G : G_angles);
-        if (plan.empty() && group_first() > 0 && group_first() < nb.cap) nb.cap = group_first();
-        // which earlier groups write this batch's outputs: the open one (-> the batch starts a new group), closed ones (-> their lane)
-        const int open = plan.empty() ? -1 : (int)plan.size() - 1;
-        auto requirement = [&](int open_index, bool &in_open, bool &conflict) {
-            int req = -1;
-            in_open = conflict = false;
-            for (const void *p : out) {
-                if (!p) continue;
-                const int gi = writers.at(p).second;
-                if (gi < 0) continue;
-                if (gi == open_index) { in_open = true; continue; }
-                if (req >= 0 && req != plan[gi].lane) conflict = true;
-                req = plan[gi].lane;
-            }
-            return req;
-        };
-        bool in_open, conflict;
-        int req = requirement(open, in_open, conflict);
-        bool join = false;
-        if (open >= 0) {
-            const PlanGroup &g = plan[open];
-            join = g.lean && nb.lean && g.nb < g.cap && g.store == nb.store && g.vec2 == nb.vec2 && !in_open && !conflict &&
-                   (req < 0 || g.req < 0 || g.req == req);
-        }
-        if (join) {
-            plan[open].nb++;
-            if (req >= 0) plan[open].req = req;
-        } else {
-            if (open >= 0) {
-                close(plan[open]);
-                req = requirement(-1, in_open, conflict);       // (the group just closed has a lane now)
-            }
-            nb.req = req; nb.sync_first = conflict;
-            plan.push_back(nb);
-        }
-        for (const void *p : out)
-            if (p) writers.at(p) = {p, (int)plan.size() - 1};
-    }
-    if (!plan.empty()) close(plan.back());
-    h->lanes.next_lane = rot % L;
+        if (b == 0 && group_first() > 0 && group_first() < nb.cap) nb.cap = group_first();
+    };
 
     // ---- workspaces and launches ----
-    bool need_cov = !d_cov_out, need_spec = !d_spectrum_out;
-    for (int b = 0; b < n_batches && !(need_cov && need_spec); b++) {
-        if (d_cov_out && !d_cov_out[b]) need_cov = true;
-        if (d_spectrum_out && !d_spectrum_out[b]) need_spec = true;
-    }
-    const size_t work_bytes = doa::autocorrelate_workspace_bytes(N, h->K, h->ovl, h->max_batch);
-    using H = doa_music_pipeline;
-    // a lane's buffers hold a whole group: records and covariances are 64-128 B per item; the angles-only scratch rows are bounded (G_angles)
-    auto reserve = [&](doa::DevBuf &coef, doa::DevBuf &cheb, doa::DevBuf &cov, doa::DevBuf &spec, doa::DevBuf &work,
-                       doa::DevBuf &smooth, doa::DevBuf &status, doa::DevBuf &full) -> int {
-        int rc = coef.reserve((size_t)h->max_batch * doa::coef_stride(N) * (dbl ? sizeof(double) : sizeof(float)));
-        if (rc == DOA_OK && h->S) rc = smooth.reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
-        if (rc == DOA_OK && h->estimator == DOA_ESTIMATOR_CAPON) rc = status.reserve((size_t)h->max_batch * sizeof(int));
-        if (rc == DOA_OK && h->has_table) rc = full.reserve((size_t)h->max_batch * doa::full_record_len(N) * sizeof(double));
-        if (rc == DOA_OK && doa::music_uses_cheb(h->elements(), h->bits)) rc = cheb.reserve((size_t)G * h->max_batch * doa::kChebRecord * sizeof(double));
-        if (rc == DOA_OK && need_cov) rc = cov.reserve((size_t)G * h->max_batch * N * N * sizeof(float2));
-        if (rc == DOA_OK && need_spec) rc = spec.reserve((size_t)G_angles * h->max_batch * P * sizeof(float));
-        if (rc == DOA_OK && work_bytes) rc = work.reserve(work_bytes);
-        return rc;
-    };
-    auto launch = [&](const PlanGroup &g, const PipeWs &ws, void *lane_cov, hipStream_t st) -> int {
+    const bool need_cov = doa::PipeLanes::lacks(d_cov_out, n_batches), need_spec = doa::PipeLanes::lacks(d_spectrum_out, n_batches);
+    // a lane's buffers hold a whole group; the angles-only scratch rows are bounded (G_angles)
+    auto prepare = [&](doa::PipeLane &ln) { return reserve(h, ln, G, G_angles, need_cov, need_spec, cfg_of(h)); };
+    auto launch = [&](const doa::PlanGroup &g, doa::PipeLane &ln) -> int {
+        const PipeWs ws = view(h, ln, 0);
         if (!g.lean || g.nb == 1) {                              // one batch: the launches of work_dev
             int rc = DOA_OK;
             for (int b = g.b0; b < g.b0 + g.nb && rc >= 0; b++) {
-                void *cov = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : lane_cov;
+                void *cov = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : ws.cov;
                 rc = run_ws(h, n, d_input_items + (size_t)b * N, cov, d_spectrum_out ? d_spectrum_out[b] : nullptr, d_max_out[b],
-                            d_argmax_out[b], ws, st);
+                            d_argmax_out[b], ws, ln.st);
             }
             return rc;
         }
@@ -568,54 +468,18 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         for (int k = 0; k < g.nb; k++) {
             const int b = g.b0 + k;
             grp.in[k] = d_input_items + (size_t)b * N;
-            grp.cov[k] = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : static_cast<char *>(lane_cov) + (size_t)k * n * N * N * sizeof(float2);
+            grp.cov[k] = (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : static_cast<char *>(ws.cov) + (size_t)k * n * N * N * sizeof(float2);
             grp.spec[k] = g.store ? d_spectrum_out[b] : static_cast<char *>(ws.spec_scratch) + (size_t)k * n * P * sizeof(float);
             grp.mx[k] = d_max_out[b]; grp.am[k] = d_argmax_out[b];
         }
         const unsigned skip = ~h->stages & 7u;                   // doa_music_pipeline_set_stages
         int rc = DOA_OK;
-        if (!(skip & 1)) rc = doa::launch_autocorrelate_group(N, h->K, h->avg, grp, st, h->has_gain ? h->d_gain.p : nullptr, h->format, h->scale);
-        if (rc == DOA_OK && !(skip & 2)) rc = doa::launch_music_evd_group(N, h->music.M, grp, nullptr, ws.cheb, st);
-        if (rc == DOA_OK && !(skip & 4)) rc = doa::launch_music_scan_group(h->music, h->peaks, grp, ws.cheb, g.store, st);
+        if (!(skip & 1)) rc = doa::launch_autocorrelate_group(N, h->K, h->avg, grp, ln.st, h->has_gain ? h->d_gain.p : nullptr, h->format, h->scale);
+        if (rc == DOA_OK && !(skip & 2)) rc = doa::launch_music_evd_group(N, h->music.M, grp, nullptr, ws.cheb, ln.st);
+        if (rc == DOA_OK && !(skip & 4)) rc = doa::launch_music_scan_group(h->music, h->peaks, grp, ws.cheb, g.store, ln.st);
         return rc;
     };
-    if (solo) {
-        hipStream_t caller = static_cast<hipStream_t>(hip_stream);
-        int rc = reserve(h->d_coef, h->d_cheb, h->d_cov, h->d_spec, h->d_work[0], h->d_smooth, h->d_status, h->d_full);
-        if (rc != DOA_OK) return rc;
-        PipeWs ws;
-        ws.coef = h->d_coef.p; ws.cheb = h->d_cheb.p; ws.spec_scratch = h->d_spec.p; ws.work = h->d_work[0].p;
-        ws.smooth = h->d_smooth.p; ws.status = h->d_status.p; ws.full = h->d_full.p;
-        ws.scratch = &h->d_scratch; ws.scratch_item_off = 0;
-        for (size_t u = 0; u < plan.size() && rc >= 0; u++) rc = launch(plan[u], ws, h->d_cov.p, caller);
-        if (rc >= 0 && injected) {
-            doa::set_error("music_pipeline_work_dev_batches: injected failure in batch %d", fail_at);
-            rc = DOA_ERR_HIP;
-        }
-        if (rc < 0) {
-            const std::string msg = doa_last_error();
-            (void)hipStreamSynchronize(caller);                  // the contract of an error return: nothing of the call still runs
-            doa::set_error("%s", msg.c_str());
-            return rc;
-        }
-        return n_batches * n;
-    }
-    auto prepare = [&](doa::PipeLane &ln) -> int {
-        return reserve(ln.buf[H::kCoef], ln.buf[H::kCheb], ln.buf[H::kCov], ln.buf[H::kSpec], ln.buf[H::kWork], ln.buf[H::kSmooth],
-                       ln.buf[H::kStatus], ln.buf[H::kFull]);
-    };
-    auto launch_unit = [&](int u, doa::PipeLane &ln) -> int {
-        const PlanGroup &g = plan[u];
-        if (g.sync_first)
-            if (const int rc = h->lanes.synchronize(); rc != DOA_OK) return rc;
-        PipeWs ws;
-        ws.coef = ln.buf[H::kCoef].p; ws.cheb = ln.buf[H::kCheb].p; ws.spec_scratch = ln.buf[H::kSpec].p; ws.work = ln.buf[H::kWork].p;
-        ws.smooth = ln.buf[H::kSmooth].p; ws.status = ln.buf[H::kStatus].p; ws.full = ln.buf[H::kFull].p;
-        ws.scratch = &ln.buf[H::kScratch]; ws.scratch_item_off = 0;
-        return launch(g, ws, ln.buf[H::kCov].p, ln.st);
-    };
-    const int rc = h->lanes.run_units("music_pipeline_work_dev_batches", (int)plan.size(), injected ? fail_at : -1, hip_stream, prepare,
-                                      [&](int u) { return plan[u].lane; }, launch_unit);
+    const int rc = h->run_planned("music_pipeline_work_dev_batches", n_batches, L, hip_stream, traits, prepare, launch);
     return rc < 0 ? rc : n_batches * n;
 }
 
@@ -655,14 +519,17 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
     if (const int rc = h->host_open(who, input_items); rc != DOA_OK) return rc;
     const size_t N = h->N, M = h->music.M, P = h->peaks.L;
     // [max | argmax | cov | spectrum]; on the chunked path the peaks lie in the transport's result block, the covariances
-    // and spectra in the handle's own d_cov and d_spec at their item offsets
+    // and spectra in the handle's own workspace at their item offsets
+    using H = doa_music_pipeline;
     const doa::HostSection sec[4] = {{max_out, M * sizeof(float), nullptr}, {argmax_out, M * sizeof(float), nullptr},
-                                     {cov_out, N * N * sizeof(float2), h->d_cov.p}, {spectrum_out, P * sizeof(float), h->d_spec.p}};
+                                     {cov_out, N * N * sizeof(float2), h->self.buf[H::kCov].p},
+                                     {spectrum_out, P * sizeof(float), h->self.buf[H::kSpec].p}};
     return h->host_run(who, noutput_items, input_items, sec, 4,
                        [h](int n, const void *const *d_in, size_t item_off, void *const *d_sec, hipStream_t st, int lane) {
-                           void *cov = d_sec[2] ? d_sec[2] : h->d_cov.as<float2>() + item_off * h->N * h->N;
+                           PipeWs ws = view(h, h->self, item_off);
+                           ws.work = h->host_work(lane);
                            // (no spectrum section = angles only)
-                           return run_dev(h, n, d_in, cov, d_sec[3], d_sec[0], d_sec[1], item_off, st, lane);
+                           return run_ws(h, n, d_in, d_sec[2] ? d_sec[2] : ws.cov, d_sec[3], d_sec[0], d_sec[1], ws, st);
                        });
 }
 
@@ -684,11 +551,8 @@ int doa_music_pipeline_set_internal_precision(doa_music_pipeline_t *h, int bits)
 {
     doa::clear_error();
     if (!h || (bits != 32 && bits != 64)) { doa::set_error("music_pipeline_set_internal_precision: need a handle and bits = 32 or 64"); return DOA_ERR_INVALID_ARG; }
-    if (doa::music_uses_cheb(h->elements(), bits)) {
-        if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-        const int rc = h->d_cheb.reserve((size_t)h->max_batch * doa::kChebRecord * sizeof(double));
-        if (rc != DOA_OK) return rc;
-    }
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    if (const int rc = reserve_self(h, {h->S, bits, h->estimator, h->has_table}); rc != DOA_OK) return rc;
     h->bits = bits;
     return DOA_OK;
 }

@@ -19,8 +19,15 @@ int PipeFront::open(int dev, int inputs, int snapshot_size, int overlap_size, in
     N = inputs; K = snapshot_size; ovl = overlap_size; avg = avg_method;
     max_batch = max_batch_; device = dev;
     bits = internal_precision_bits();
-    int rc = d_cov.reserve((size_t)max_batch * N * N * sizeof(float2));
-    if (const size_t ws = autocorrelate_workspace_bytes(N, K, ovl, max_batch); ws && rc == DOA_OK) rc = d_work[0].reserve(ws);
+    self.own_stream = false;
+    return DOA_OK;
+}
+
+int PipeFront::reserve_front(PipeLane &ln, int cov_batches, int S_)
+{
+    int rc = ln.buf[kCov].reserve((size_t)cov_batches * max_batch * N * N * sizeof(float2));
+    if (const size_t ws = autocorrelate_workspace_bytes(N, K, ovl, max_batch); ws && rc == DOA_OK) rc = ln.buf[kWork].reserve(ws);
+    if (rc == DOA_OK && S_) rc = ln.buf[kSmooth].reserve((size_t)max_batch * S_ * S_ * sizeof(float2));
     return rc;
 }
 
@@ -70,10 +77,6 @@ int PipeFront::smoothing_reserve(int S_, int fb_)
 {
     if (S_ == S && fb_ == fb) return 0;
     if (int brc = bind_device(device); brc != DOA_OK) return brc;
-    // work_dev / work_dev_auto and the host entry (whose chunks lie at their item offsets) share this one; the lanes of
-    // work_dev_batches have their own
-    if (S_)
-        if (int rc = d_smooth.reserve((size_t)max_batch * S_ * S_ * sizeof(float2)); rc != DOA_OK) return rc;
     return 1;
 }
 
@@ -186,7 +189,7 @@ int PipeFront::host_run(const char *who, int n_items, const void *const *input_i
     for (auto &b : d_in)
         if (rc == DOA_OK) rc = b.reserve(stride * N);
     if (const size_t ws = autocorrelate_workspace_bytes(N, K, ovl, (int)chunk); ws && rc == DOA_OK)
-        rc = d_work[1].reserve(ws);                    // lane 0 uses the workspace create() sized for max_batch
+        rc = d_work1.reserve(ws);                      // lane 0 uses the workspace create() sized for max_batch
     if (rc != DOA_OK) return rc;
     int lane = 0, chunk_index = 0;
     // One chunk: uploads, kernels, downloads, all on its lane's stream.  A failure anywhere in it ends the loop, and the
@@ -229,3 +232,30 @@ int PipeFront::host_run(const char *who, int n_items, const void *const *input_i
 }
 
 }  // namespace doa
+
+// the plan of a work_dev_batches call on flat arrays, for the CPU tests: no handle, no device
+extern "C" int doa_hip_batch_plan_debug(int n_batches, const void *const *outputs, const unsigned char *flags, const int *caps,
+                                        int n_lanes, int rotation_in, int *group_out, int *lane_out, int *sync_first_out,
+                                        int *rotation_out)
+{
+    doa::clear_error();
+    bool ok = n_batches >= 0 && outputs && flags && caps && group_out && lane_out && sync_first_out && rotation_out &&
+              n_lanes >= 1 && n_lanes <= doa::PipeLanes::kMaxLanes && rotation_in >= 0 && rotation_in < n_lanes;
+    for (int b = 0; ok && b < n_batches; b++) ok = flags[b] < 8 && caps[b] >= 1;
+    if (!ok) {
+        doa::set_error("hip_batch_plan_debug: bad arguments (every array, 1 <= n_lanes <= %d, 0 <= rotation_in < n_lanes, flags < 8, caps >= 1)",
+                       doa::PipeLanes::kMaxLanes);
+        return DOA_ERR_INVALID_ARG;
+    }
+    std::vector<doa::PlanGroup> plan;
+    *rotation_out = doa::plan_batches(n_batches, n_lanes, rotation_in, [&](int b, doa::PlanGroup &nb, const void *(&out)[4]) {
+        for (int k = 0; k < 4; k++) out[k] = outputs[4 * b + k];
+        nb.lean = flags[b] & 1; nb.store = flags[b] & 2; nb.vec2 = flags[b] & 4;
+        nb.cap = caps[b];
+    }, plan);
+    for (size_t g = 0; g < plan.size(); g++)
+        for (int b = plan[g].b0; b < plan[g].b0 + plan[g].nb; b++) {
+            group_out[b] = (int)g; lane_out[b] = plan[g].lane; sync_first_out[b] = plan[g].sync_first;
+        }
+    return (int)plan.size();
+}

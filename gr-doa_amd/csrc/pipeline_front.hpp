@@ -21,7 +21,7 @@ struct HostSection {
 };
 // Queues a handle's chain for n items on `st`: d_in are the device copies of the input streams, item_off the offset of the
 // first item within the call (the chunks in flight on the two lanes must not share per-item records), d_sec[i] where
-// section i's items go (NULL for an absent one), lane the copy/compute lane (its K1 workspace is d_work[lane]).
+// section i's items go (NULL for an absent one), lane the copy/compute lane (its K1 workspace is host_work(lane)).
 // Returns < 0 on failure.
 using HostChain = std::function<int(int n, const void *const *d_in, size_t item_off, void *const *d_sec, hipStream_t st, int lane)>;
 
@@ -30,16 +30,21 @@ struct PipeFront {
     int max_batch = 0;
     int bits = 64;
     int device = 0;
-    DevBuf d_cov, d_gain;
+    DevBuf d_gain;
     bool has_gain = false;
     int format = DOA_SAMPLE_FC32;   // set_input_format
     float scale = 1.0f;
     int S = 0, fb = 0;              // spatial smoothing: subarray size (0 = off), forward-backward
-    DevBuf d_smooth;                // the smoothed items (S * S per item, max_batch items) between K1 and the eigen stage
+    // The handle's own workspace is a lane without a stream of its own (a call sets self.st to the caller's stream): work_dev,
+    // work_dev_auto, the host entry and a solo work_dev_batches call use it, every other work_dev_batches call the lanes below.
+    // A lane's slots: the front's three -- covariance items, K1's piece sums (overlapping windows), the smoothed items (S * S
+    // per item) between K1 and the eigen stage -- and after them the handle's.
+    enum { kCov = 0, kWork, kSmooth, kFrontBufs };
+    PipeLane self;
     // host-pointer entry point only: two copy/compute lanes
     hipStream_t hst[2] = {nullptr, nullptr};
     DevBuf d_in[2], d_res;
-    DevBuf d_work[2];               // K1's piece sums (overlapping windows), one per copy/compute lane
+    DevBuf d_work1;                 // K1's piece sums of the second copy/compute lane (the first: self.buf[kWork])
     PinnedBuf h_stage;              // scheduler-sized calls: one page-locked staging buffer, one copy each way
     int fail_chunk = -1;            // inject_failure, host-pointer entry: one-shot, cleared by every call (tests)
     PipeLanes lanes;                // work_dev_batches: the library's own overlap lanes (pipeline_lanes.hpp)
@@ -48,7 +53,7 @@ struct PipeFront {
 
     // create: the autocorrelate parameters are refused before a device is looked for
     static bool check_create(const char *who, int inputs, int snapshot_size, int overlap_size);
-    // create, after the caller's checks: the front's parameters, precision, d_cov and lane 0's K1 workspace
+    // create, after the caller's checks: the front's parameters and precision (the handle's init reserves `self`)
     int open(int dev, int inputs, int snapshot_size, int overlap_size, int avg_method, int max_batch_);
     static void destroy(PipeFront *h);
 
@@ -56,9 +61,25 @@ struct PipeFront {
     int set_input_format(const char *who, int format_, float scale_);
     // set_spatial_smoothing in two steps, with room for a handle's own refusals between them and its own tables after them.
     // smoothing_args: the range and flag check (M = the handle's source count).  smoothing_reserve: 0 = the handle has
-    // (S_, fb_) already, nothing to do; 1 = device bound and d_smooth reserved, the caller finishes and stores S and fb.
+    // (S_, fb_) already, nothing to do; 1 = device bound, the caller reserves `self` for S_, finishes and stores S and fb.
     int smoothing_args(const char *who, int M, int S_, int forward_backward) const;
     int smoothing_reserve(int S_, int fb_);
+    // the front's slots of a lane: covariance items for `cov_batches` batches (0: every batch brings its own), K1's piece
+    // sums, the smoothed items of subarray size S_ (a handle's reserve function calls this, then sizes its own slots)
+    int reserve_front(PipeLane &ln, int cov_batches, int S_);
+    void *host_work(int lane) const { return lane ? d_work1.p : self.buf[kWork].p; }
+    // work_dev_batches behind a handle's argument checks: the batches in front of an armed inject_failure are planned over L
+    // lanes (traits: batch_plan.hpp) from where the rotation stands, and the plan runs (pipeline_lanes.hpp: run_units)
+    template <class Traits, class Prepare, class Launch>
+    int run_planned(const char *who, int n_batches, int L, void *hip_stream, Traits traits, Prepare prepare, Launch launch)
+    {
+        const int fail_at = lanes.fail_batch < n_batches ? lanes.fail_batch : -1;
+        fail_chunk = -1; lanes.fail_batch = -1;             // (the test aid is one-shot for whichever entry comes next)
+        std::vector<PlanGroup> plan;
+        plan.reserve((size_t)n_batches);
+        lanes.next_lane = plan_batches(fail_at >= 0 ? fail_at : n_batches, L, lanes.next_lane % L, traits, plan);
+        return lanes.run_units(who, plan, fail_at, hip_stream, self, prepare, launch);
+    }
     int inject_failure(int chunk_index);
     int lanes_idle();
 

@@ -11,17 +11,18 @@
 struct doa_root_pipeline : doa::PipeFront {
     int M = 0;
     float norm_spacing = 0.f;
-    doa::DevBuf d_coef, d_status;
     int estimator = DOA_GRIDFREE_ROOT_MUSIC;    // doa_root_pipeline_set_estimator
-    doa::DevBuf d_rec;              // ESPRIT mode: the signal-subspace records between the eigen launch and esprit_kernel
     doa::PinnedBuf h_status;        // host-pointer entry point: the items' status words, scanned after the call's copies
-    enum { kCoef = 0, kCov, kStatus, kWork, kSmooth, kRec };    // doa_root_pipeline_work_dev_batches: a lane's buffers
+    // a lane's slots after the front's: coefficient records, status words nobody asked for, ESPRIT mode's signal-subspace
+    // records between the eigen launch and esprit_kernel
+    enum { kCoef = kFrontBufs, kStatus, kRec };
 };
 
 namespace {
 struct RootWs {
+    void *cov;        // covariance items, for a chain whose caller does not ask for them
     void *coef;       // double coefficient records of the chain's items
-    void *status;     // one int per item (1 = no root strictly inside the unit circle), or the caller's buffer
+    void *status;     // one int per item (1 = no root strictly inside the unit circle); a chain's caller may bring its own
     void *work;       // K1's piece sums (overlapping windows), or NULL
     void *smooth;     // spatial smoothing on: S * S gr_complex per item (else unused)
     void *rec;        // ESPRIT mode: signal-subspace records of the chain's items (else unused)
@@ -30,6 +31,27 @@ size_t coef_bytes(const doa_root_pipeline *h, size_t items) { return items * doa
 // (sized for the full array: a later set_spatial_smoothing only makes the records smaller)
 size_t rec_bytes(const doa_root_pipeline *h, size_t items) { return items * doa::subspace_record_len(h->N) * sizeof(double); }
 bool esprit_mode(const doa_root_pipeline *h) { return h->estimator == DOA_GRIDFREE_ESPRIT; }
+// The workspace `ln` (the handle's own, or a lane of work_dev_batches) as a chain sees it, from item `item_off` on (the host
+// entry's two copy/compute lanes write disjoint item ranges); status: the caller's buffer, or NULL for the lane's
+RootWs view(doa_root_pipeline *h, doa::PipeLane &ln, size_t item_off, void *status)
+{
+    using H = doa_root_pipeline;
+    return {ln.at(H::kCov, item_off, (size_t)h->N * h->N * sizeof(float2)), ln.at(H::kCoef, item_off, coef_bytes(h, 1)),
+            status ? status : ln.at(H::kStatus, item_off, sizeof(int)), ln.buf[H::kWork].p,
+            ln.at(H::kSmooth, item_off, (size_t)h->S * h->S * sizeof(float2)), ln.at(H::kRec, item_off, rec_bytes(h, 1))};
+}
+// Sizes `ln` for one batch with smoothing S and estimator `estimator` (a setter passes what it is about to commit);
+// need_cov / need_status: some batch brings no covariance / status buffer of its own
+int reserve(doa_root_pipeline *h, doa::PipeLane &ln, bool need_cov, bool need_status, int S, int estimator)
+{
+    using H = doa_root_pipeline;
+    const size_t items = (size_t)h->max_batch;
+    int rc = h->reserve_front(ln, need_cov ? 1 : 0, S);
+    if (rc == DOA_OK) rc = ln.buf[H::kCoef].reserve(coef_bytes(h, items));
+    if (rc == DOA_OK && need_status) rc = ln.buf[H::kStatus].reserve(items * sizeof(int));
+    if (rc == DOA_OK && estimator == DOA_GRIDFREE_ESPRIT) rc = ln.buf[H::kRec].reserve(rec_bytes(h, items));
+    return rc;
+}
 int esprit_precision(const char *who, const doa_root_pipeline *h)
 {
     if (!esprit_mode(h) || h->bits == 64) return DOA_OK;
@@ -89,9 +111,7 @@ doa_root_pipeline_t *doa_root_pipeline_create(int inputs, int snapshot_size, int
     }
     return doa::create_pipeline<doa_root_pipeline>(inputs, snapshot_size, overlap_size, avg_method, max_batch, [&](doa_root_pipeline &h) {
         h.M = num_targets; h.norm_spacing = norm_spacing;
-        int rc = h.d_coef.reserve(coef_bytes(&h, (size_t)max_batch));
-        if (rc == DOA_OK) rc = h.d_status.reserve((size_t)max_batch * sizeof(int));
-        return rc;
+        return reserve(&h, h.self, true, true, h.S, h.estimator);
     });
 }
 
@@ -118,6 +138,7 @@ int doa_root_pipeline_set_spatial_smoothing(doa_root_pipeline_t *h, int subarray
     const int S = subarray_size, fb = S ? forward_backward : 0;
     if (int rc = h->smoothing_args("root_pipeline_set_spatial_smoothing", h->M, S, forward_backward); rc != DOA_OK) return rc;
     if (int rc = h->smoothing_reserve(S, fb); rc <= 0) return rc;
+    if (int rc = reserve(h, h->self, true, true, S, h->estimator); rc != DOA_OK) return rc;
     h->S = S; h->fb = fb;
     return DOA_OK;
 }
@@ -131,10 +152,8 @@ int doa_root_pipeline_set_estimator(doa_root_pipeline_t *h, int estimator)
     }
     if (estimator == h->estimator) return DOA_OK;
     if (estimator == DOA_GRIDFREE_ESPRIT) {
-        // work_dev / work_dev_auto and the host entry (whose chunks lie at their item offsets) share this one; the lanes of
-        // work_dev_batches have their own (kRec)
         if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-        if (int rc = h->d_rec.reserve(rec_bytes(h, (size_t)h->max_batch)); rc != DOA_OK) return rc;
+        if (int rc = reserve(h, h->self, true, true, h->S, estimator); rc != DOA_OK) return rc;
     }
     h->estimator = estimator;
     return DOA_OK;
@@ -155,8 +174,8 @@ int doa_root_pipeline_work_dev(doa_root_pipeline_t *h, int noutput_items, const 
     if (int prc = esprit_precision("root_pipeline_work_dev", h); prc != DOA_OK) return prc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    RootWs ws{h->d_coef.p, d_status_out ? (void *)d_status_out : h->d_status.p, h->d_work[0].p, h->d_smooth.p, h->d_rec.p};
-    return run_chain(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : h->d_cov.p, d_angles_out, ws,
+    const RootWs ws = view(h, h->self, 0, d_status_out);
+    return run_chain(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : ws.cov, d_angles_out, ws,
                      static_cast<hipStream_t>(hip_stream));
 }
 
@@ -189,22 +208,21 @@ int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int noutput_items, c
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const int n = noutput_items;
     const int elements = h->elements();
-    void *cov = d_cov_out ? d_cov_out : h->d_cov.p;
-    int rc = h->run_k1(n, d_input_items, cov, h->d_work[0].p, st);
-    if (rc == DOA_OK) rc = h->run_smoothing(n, cov, h->d_smooth.p, st);
+    const RootWs ws = view(h, h->self, 0, d_status_out);
+    void *cov = d_cov_out ? d_cov_out : ws.cov;
+    int rc = h->run_k1(n, d_input_items, cov, ws.work, st);
+    if (rc == DOA_OK) rc = h->run_smoothing(n, cov, ws.smooth, st);
     if (rc == DOA_OK && esprit_mode(h)) {       // one estimating eigen launch (counts, eigenvalues, record), the counted ESPRIT kernel
         rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, nullptr, nullptr, st,
-                                          h->d_rec.p);
+                                          ws.rec);
         if (rc == DOA_OK)
-            rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, h->d_rec.p, d_count_out, d_angles_out,
-                                    d_status_out ? (void *)d_status_out : h->d_status.p, st);
+            rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, ws.rec, d_count_out, d_angles_out, ws.status, st);
         return rc == DOA_OK ? n : rc;
     }
     if (rc == DOA_OK)
-        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, h->d_coef.p, nullptr, st);
+        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, ws.coef, nullptr, st);
     if (rc == DOA_OK)
-        rc = doa::launch_root_music_counts(elements, h->M, h->norm_spacing, n, h->d_coef.p, d_count_out, d_angles_out,
-                                           d_status_out ? (void *)d_status_out : h->d_status.p, st);
+        rc = doa::launch_root_music_counts(elements, h->M, h->norm_spacing, n, ws.coef, d_count_out, d_angles_out, ws.status, st);
     return rc == DOA_OK ? n : rc;
 }
 
@@ -259,48 +277,19 @@ int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, in
     if (n_batches == 0 || noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const int N = h->N;
-    const int fail_at = h->lanes.fail_batch;
-    h->fail_chunk = -1;
-    if (h->lanes.n_lanes == 1 && hip_stream != DOA_STREAM_DETACHED) {     // nothing to overlap: the caller's stream itself, no events
-        hipStream_t caller = static_cast<hipStream_t>(hip_stream);
-        h->lanes.fail_batch = -1;
-        for (int b = 0; b < n_batches; b++) {
-            if (fail_at == b) {
-                doa::set_error("root_pipeline_work_dev_batches: injected failure in batch %d", b);
-                (void)hipStreamSynchronize(caller);
-                return DOA_ERR_HIP;
-            }
-            RootWs ws{h->d_coef.p, (d_status_out && d_status_out[b]) ? (void *)d_status_out[b] : h->d_status.p, h->d_work[0].p,
-                      h->d_smooth.p, h->d_rec.p};
-            const int rc = run_chain(h, noutput_items, d_input_items + (size_t)b * N,
-                                     (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : h->d_cov.p, d_angles_out[b], ws, caller);
-            if (rc < 0) { (void)hipStreamSynchronize(caller); return rc; }
-        }
-        return n_batches * noutput_items;
-    }
-    bool need_cov = !d_cov_out, need_status = !d_status_out;
-    for (int b = 0; b < n_batches && !(need_cov && need_status); b++) {
-        if (d_cov_out && !d_cov_out[b]) need_cov = true;
-        if (d_status_out && !d_status_out[b]) need_status = true;
-    }
-    const size_t work_bytes = doa::autocorrelate_workspace_bytes(N, h->K, h->ovl, h->max_batch);
-    using H = doa_root_pipeline;
-    auto prepare = [&](doa::PipeLane &ln) -> int {
-        int rc = ln.buf[H::kCoef].reserve(coef_bytes(h, (size_t)h->max_batch));
-        if (rc == DOA_OK && need_cov) rc = ln.buf[H::kCov].reserve((size_t)h->max_batch * N * N * sizeof(float2));
-        if (rc == DOA_OK && need_status) rc = ln.buf[H::kStatus].reserve((size_t)h->max_batch * sizeof(int));
-        if (rc == DOA_OK && work_bytes) rc = ln.buf[H::kWork].reserve(work_bytes);
-        if (rc == DOA_OK && h->S) rc = ln.buf[H::kSmooth].reserve((size_t)h->max_batch * h->S * h->S * sizeof(float2));
-        if (rc == DOA_OK && esprit_mode(h)) rc = ln.buf[H::kRec].reserve(rec_bytes(h, (size_t)h->max_batch));
-        return rc;
+    // the plan (batch_plan.hpp): no groups here, and a batch that writes what an earlier one wrote follows it on its lane
+    auto traits = [&](int b, doa::PlanGroup &, const void *(&out)[4]) {
+        out[0] = d_cov_out ? d_cov_out[b] : nullptr; out[1] = d_angles_out[b]; out[2] = d_status_out ? d_status_out[b] : nullptr;
     };
-    auto launch = [&](int b, doa::PipeLane &ln) -> int {
-        RootWs ws{ln.buf[H::kCoef].p, (d_status_out && d_status_out[b]) ? (void *)d_status_out[b] : ln.buf[H::kStatus].p,
-                  ln.buf[H::kWork].p, ln.buf[H::kSmooth].p, ln.buf[H::kRec].p};
-        return run_chain(h, noutput_items, d_input_items + (size_t)b * N,
-                         (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : ln.buf[H::kCov].p, d_angles_out[b], ws, ln.st);
+    const bool need_cov = doa::PipeLanes::lacks(d_cov_out, n_batches), need_status = doa::PipeLanes::lacks(d_status_out, n_batches);
+    auto prepare = [&](doa::PipeLane &ln) { return reserve(h, ln, need_cov, need_status, h->S, h->estimator); };
+    auto launch = [&](const doa::PlanGroup &g, doa::PipeLane &ln) -> int {
+        const int b = g.b0;                                          // (groups of one)
+        const RootWs ws = view(h, ln, 0, d_status_out ? d_status_out[b] : nullptr);
+        return run_chain(h, noutput_items, d_input_items + (size_t)b * N, (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : ws.cov,
+                         d_angles_out[b], ws, ln.st);
     };
-    const int rc = h->lanes.run_batches("root_pipeline_work_dev_batches", n_batches, hip_stream, prepare, launch);
+    const int rc = h->run_planned("root_pipeline_work_dev_batches", n_batches, h->lanes.n_lanes, hip_stream, traits, prepare, launch);
     return rc < 0 ? rc : n_batches * noutput_items;
 }
 
@@ -323,17 +312,14 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
     if (const int rc = h->h_status.reserve((size_t)noutput_items * sizeof(int)); rc != DOA_OK) return rc;
     const size_t N = h->N;
     // [angles | status | cov]; on the chunked path angles and status words lie in the transport's result block, the
-    // covariances in the handle's own d_cov at their item offsets
+    // covariances in the handle's own workspace at their item offsets
     const doa::HostSection sec[3] = {{angles_out, h->M * sizeof(float), nullptr}, {h->h_status.p, sizeof(int), nullptr},
-                                     {cov_out, N * N * sizeof(float2), h->d_cov.p}};
+                                     {cov_out, N * N * sizeof(float2), h->self.buf[doa_root_pipeline::kCov].p}};
     const int rc = h->host_run(who, noutput_items, input_items, sec, 3,
                                [h](int n, const void *const *d_in, size_t item_off, void *const *d_sec, hipStream_t st, int lane) {
-        // (the two copy/compute lanes write disjoint item ranges of the handle's records and smoothed items)
-        RootWs ws{h->d_coef.as<char>() + coef_bytes(h, item_off), d_sec[1], h->d_work[lane].p,
-                  h->S ? (void *)(h->d_smooth.as<float2>() + item_off * h->S * h->S) : nullptr,
-                  esprit_mode(h) ? (void *)(h->d_rec.as<char>() + rec_bytes(h, item_off)) : nullptr};
-        void *cov = d_sec[2] ? d_sec[2] : h->d_cov.as<float2>() + item_off * h->N * h->N;
-        return run_chain(h, n, d_in, cov, d_sec[0], ws, st);
+        RootWs ws = view(h, h->self, item_off, d_sec[1]);
+        ws.work = h->host_work(lane);
+        return run_chain(h, n, d_in, d_sec[2] ? d_sec[2] : ws.cov, d_sec[0], ws, st);
     });
     if (rc < 0) return rc;
     // the other items' outputs are valid

@@ -652,7 +652,8 @@ DOA_HIP_API int doa_root_pipeline_work_dev(doa_root_pipeline_t *h, int noutput_i
                                            const void *const *d_input_items, void *d_cov_out,
                                            void *d_angles_out, int *d_status_out, void *hip_stream);
 /* n_batches independent batches in ONE call, overlapped over the handle's lanes; arguments, stream semantics
- * (DOA_STREAM_DETACHED included), error contract and return value as doa_music_pipeline_work_dev_batches.
+ * (DOA_STREAM_DETACHED included), error contract and return value as doa_music_pipeline_work_dev_batches.  Every batch is a
+ * group of its own, and ORDER (above) holds with the covariance, angle and status pointers as the output buffers.
  *   d_cov_out, d_status_out   HOST arrays of n_batches DEVICE pointers; the array or single entries may be NULL
  *   d_angles_out              HOST array of n_batches DEVICE pointers (required) */
 DOA_HIP_API int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, int noutput_items,

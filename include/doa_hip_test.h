@@ -106,6 +106,18 @@ DOA_HIP_API int doa_hip_evd_fallback_counter_device_debug(void);
 DOA_HIP_API int doa_hip_lane_streams_verified_debug(void);
 DOA_HIP_API int doa_hip_lane_streams_set_aside_debug(void);
 
+/* The plan of a doa_*_pipeline_work_dev_batches call (gr-doa_amd/csrc/batch_plan.hpp; doa_hip.h, GROUPS and ORDER) on flat
+ * host arrays: no handle, no device.  Per batch b: outputs[4 b .. 4 b + 3] its output pointers (values only, never
+ * dereferenced; NULL = absent), flags[b] (bit 0 lean: the batch may share a group's launches, bit 1 store: it wants its
+ * spectrum, bit 2 vec2: its K1 takes the pair-load route), caps[b] >= 1 (how many batches a group that starts with b may
+ * hold).  n_lanes (1 .. 8) and rotation_in (0 .. n_lanes - 1): the lanes of the call and where their rotation stands.
+ * Written per batch: the index of its group, the group's lane, and whether the group joins all lanes on the host before it
+ * is launched (sync_first_out, 0 / 1); *rotation_out: where the rotation stands afterwards.  Returns the number of groups,
+ * or DOA_ERR_INVALID_ARG. */
+DOA_HIP_API int doa_hip_batch_plan_debug(int n_batches, const void *const *outputs, const unsigned char *flags, const int *caps,
+                                         int n_lanes, int rotation_in, int *group_out, int *lane_out, int *sync_first_out,
+                                         int *rotation_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,3 +73,21 @@ def test_without_a_device_create_fails_loudly(handle):
         pytest.skip("a HIP device is present")
     assert not getattr(_lib.lib, f"doa_{handle}_create")(*HANDLES[handle][1])
     assert "no CPU fallback" in _lib.last_error()
+
+
+def test_the_batch_plan_entry_refuses_bad_arguments():
+    """doa_hip_batch_plan_debug (the plan both handles' work_dev_batches run; no handle, so neither count above includes it)"""
+    nb = 3
+    outs = (C.c_void_p * (4 * nb))(*[0x1000 + 16 * i for i in range(4 * nb)])
+    flags, caps = (C.c_ubyte * nb)(3, 3, 0), (C.c_int * nb)(4, 4, 1)
+    grp, lane, sync, rot = (C.c_int * nb)(), (C.c_int * nb)(), (C.c_int * nb)(), C.c_int(0)
+    good = [nb, outs, flags, caps, 2, 1, grp, lane, sync, C.byref(rot)]
+    f = _lib.lib.doa_hip_batch_plan_debug
+    assert f(*good) == 2 and list(grp) == [0, 0, 1] and _lib.last_error() == ""
+    bad = [(0, -1), (4, 0), (4, 9), (5, -1), (5, 2), (2, (C.c_ubyte * nb)(1, 8, 0)), (3, (C.c_int * nb)(4, 0, 1))]
+    bad += [(i, None) for i in (1, 2, 3, 6, 7, 8, 9)]
+    for i, value in bad:
+        args = list(good)
+        args[i] = value
+        assert f(*args) == DOA_ERR_INVALID_ARG, (i, value)
+        assert "hip_batch_plan_debug" in _lib.last_error()
