@@ -29,78 +29,15 @@ namespace doa {
 
 namespace {
 
-constexpr int kPeaks2dThreads = 256;
 constexpr int kPeaks2dStagedMax = 16384;     // floats of LDS row: 64 KiB, two workgroups per CU
 constexpr int kLoads = 8;                    // the global form: values a thread fetches before it looks at any
-
-struct Grid2d {
-    int n_az, n_el, P, wrap;
-    unsigned inv_az;                         // floor(2^32 / n_az), saturated: split() needs one correction step
-};
-
-// i = e n_az + a, 0 <= i < 2^24: q = umulhi(i, inv_az) is floor(i / n_az) or one less
-__device__ __forceinline__ void split(const Grid2d &g, int i, int &e, int &a)
-{
-    int q = (int)__umulhi((unsigned)i, g.inv_az);
-    int r = i - q * g.n_az;
-    if (r >= g.n_az) { q++; r -= g.n_az; }
-    e = q; a = r;
-}
-
-// The peak test of the rule; row(j) = the value of cell j.  One compare per neighbour: a neighbour BEFORE the cell (j < i) must
-// be strictly smaller, !(w >= c), one AFTER it may be equal, !(w > c); a NaN neighbour passes both, and so does the NaN that
-// stands in for a neighbour that does not exist.  The row above lies before the cell and the row below after it, whatever
-// the wrap does; in the cell's own row the left neighbour lies before it unless it is the wrapped one (a == 0), the right
-// one after it unless wrapped.  n_az == 1: the wrapped azimuth neighbours are the cell itself and the cells above and
-// below it, which the middle column covers.  EARLY (the global form): leave after the first row that rules the cell out.
-template <bool EARLY, class Row> __device__ __forceinline__ bool is_peak(const Row &row, const Grid2d &g, int i, float c)
-{
-    int e, a;
-    split(g, i, e, a);
-    const bool first = a == 0, last = a == g.n_az - 1, side = g.n_az > 1;
-    const bool vl = side && (!first || g.wrap), vr = side && (!last || g.wrap);
-    const int dl = first ? g.n_az - 1 : -1, dr = last ? 1 - g.n_az : 1;
-    // the global form never reads a cell that does not exist; the LDS form reads the cell itself in its place and discards it,
-    // which keeps its nine reads unconditional and in flight together
-    const auto val = [&](bool exists, int j) {
-        if constexpr (EARLY) return exists ? row(j) : NAN;
-        else { const float w = row(exists ? j : i); return exists ? w : NAN; }
-    };
-    const bool vu = e > 0, vd = e < g.n_el - 1;
-    const int ju = i - g.n_az, jd = i + g.n_az;
-    const float wl = val(vl, i + dl), wr = val(vr, i + dr);
-    bool ok = (c == c) & (first ? !(wl > c) : !(wl >= c)) & (last ? !(wr >= c) : !(wr > c));
-    if (EARLY && !ok) return false;
-    const float u0 = val(vu && vl, ju + dl), u1 = val(vu, ju), u2 = val(vu && vr, ju + dr);
-    ok = ok & !(u0 >= c) & !(u1 >= c) & !(u2 >= c);
-    if (EARLY && !ok) return false;
-    const float d0 = val(vd && vl, jd + dl), d1 = val(vd, jd), d2 = val(vd && vr, jd + dr);
-    return ok & !(d0 > c) & !(d1 > c) & !(d2 > c);
-}
-
-// strictly after (pv, pi) in the order (value descending, index ascending)
-__device__ __forceinline__ bool key_after(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
-
-// the workgroup's best (value, index), uniform in every thread.  The wave results alternate between two LDS slots by round,
-// so one barrier per round is enough: a wave reaches round r + 2 only after every wave has read round r's slot.
-__device__ __forceinline__ void block_argbest(float &v, int &i, float (&sv)[2][4], int (&si)[2][4], int round)
-{
-    wave_argbest(v, i);
-    const int wib = threadIdx.x / kWave, buf = round & 1;
-    if ((threadIdx.x & (kWave - 1)) == 0) { sv[buf][wib] = v; si[buf][wib] = i; }
-    __syncthreads();
-    v = sv[buf][0]; i = si[buf][0];
-#pragma unroll
-    for (int w = 1; w < kPeaks2dThreads / kWave; w++)
-        if (cand_better(sv[buf][w], si[buf][w], v, i)) { v = sv[buf][w]; i = si[buf][w]; }
-}
 
 // PMAX > 0: the staged form for grids of up to PMAX cells (a multiple of 64, at most 64 * 256); PMAX == 0: the global form
 template <int PMAX>
 __global__ __launch_bounds__(kPeaks2dThreads) void find_local_max_2d_kernel(const float *__restrict__ in, const float *__restrict__ az,
                                                                             const float *__restrict__ el, float *__restrict__ out_val,
                                                                             float *__restrict__ out_az, float *__restrict__ out_el,
-                                                                            Grid2d g, int M, int vec4)
+                                                                            Grid2d g, int M, int vec4, int stride)
 {
     constexpr bool kStaged = PMAX > 0;
     static_assert(PMAX % 64 == 0 && PMAX <= 64 * kPeaks2dThreads, "one flag word per thread");
@@ -113,7 +50,10 @@ __global__ __launch_bounds__(kPeaks2dThreads) void find_local_max_2d_kernel(cons
     const int P = g.P;
     const float *v_in = in + item * (size_t)P;
 
-    unsigned long long mine = 0ull;          // staged: the flags of cells 64 tid .. 64 tid + 63
+    // only the global form takes an output stride (its one caller with one is the grid mode's two-launch route, which starts
+    // where the staged forms end); the staged forms write M floats per item and pay nothing for it
+    const Peaks2dOut o{az, el, out_val, out_az, out_el, M, kStaged ? M : stride};
+    const auto best = [&](float &v, int &i, int round) { block_argbest(v, i, sv, si, round); };
     if constexpr (kStaged) {
         if (vec4) {                          // P % 4 == 0 and 16-byte aligned rows
             for (int q = tid; q < (P >> 2); q += kPeaks2dThreads)
@@ -130,25 +70,13 @@ __global__ __launch_bounds__(kPeaks2dThreads) void find_local_max_2d_kernel(cons
             if (lane == 0) flags[base >> 6] = m;
         }
         __syncthreads();
-        if (64 * tid < P) mine = flags[tid];
-    }
-
-    float *ov = out_val + item * (size_t)M;
-    float *oa = out_az + item * (size_t)M, *oe = out_el + item * (size_t)M;
-    float pv = 0.f;
-    int pi = -1, r = 0;
-    for (; r < M; r++) {
-        float bv = 0.f;
-        int bi = INT_MAX;
-        if constexpr (kStaged) {
-            for (unsigned long long m = mine; m != 0ull; m &= m - 1ull) {
-                const int i = 64 * tid + (int)__builtin_ctzll(m);
-                const float c = row[i];
-                if ((r == 0 || key_after(c, i, pv, pi)) && cand_better(c, i, bv, bi)) { bv = c; bi = i; }
-            }
-        } else {
+        const unsigned long long mine = (64 * tid < P) ? flags[tid] : 0ull;      // the flags of cells 64 tid .. 64 tid + 63
+        peaks2d_rounds(g, o, item, tid,
+                       [&](bool first, float pv, int pi, float &bv, int &bi) { flagged_best(row, mine, tid, first, pv, pi, bv, bi); }, best);
+    } else {
+        const auto glb = [&](int j) { return v_in[j]; };
+        peaks2d_rounds(g, o, item, tid, [&](bool first, float pv, int pi, float &bv, int &bi) {
             // kLoads values in flight per thread before any is looked at: the walk is a chain of load latencies otherwise
-            const auto glb = [&](int j) { return v_in[j]; };
             for (int i0 = tid; i0 < P; i0 += kLoads * kPeaks2dThreads) {
                 float c[kLoads];
 #pragma unroll
@@ -159,30 +87,21 @@ __global__ __launch_bounds__(kPeaks2dThreads) void find_local_max_2d_kernel(cons
 #pragma unroll
                 for (int u = 0; u < kLoads; u++) {
                     const int i = i0 + u * kPeaks2dThreads;
-                    if (i < P && (r == 0 || key_after(c[u], i, pv, pi)) && cand_better(c[u], i, bv, bi) && is_peak<true>(glb, g, i, c[u])) {
+                    if (i < P && (first || key_after(c[u], i, pv, pi)) && cand_better(c[u], i, bv, bi) && is_peak<true>(glb, g, i, c[u])) {
                         bv = c[u]; bi = i;
                     }
                 }
             }
-        }
-        block_argbest(bv, bi, sv, si, r);
-        if (bi == INT_MAX) break;            // uniform: no peak is left
-        pv = bv; pi = bi;
-        if (tid == 0) {
-            int e, a;
-            split(g, bi, e, a);
-            ov[r] = bv; oa[r] = az[a]; oe[r] = el[e];
-        }
+        }, best);
     }
-    if (tid >= r && tid < M) { ov[tid] = NAN; oa[tid] = NAN; oe[tid] = NAN; }
 }
 
 template <int PMAX>
 void launch_form(const Peaks2dTables &t, const Grid2d &g, int n_items, const void *d_in, void *d_val, void *d_az, void *d_el,
-                 int vec4, hipStream_t st)
+                 int vec4, int stride, hipStream_t st)
 {
     hipLaunchKernelGGL((find_local_max_2d_kernel<PMAX>), dim3(n_items), dim3(kPeaks2dThreads), 0, st, (const float *)d_in,
-                       t.d_az.as<float>(), t.d_el.as<float>(), (float *)d_val, (float *)d_az, (float *)d_el, g, t.M, vec4);
+                       t.d_az.as<float>(), t.d_el.as<float>(), (float *)d_val, (float *)d_az, (float *)d_el, g, t.M, vec4, stride);
 }
 
 }  // namespace
@@ -226,23 +145,23 @@ int Peaks2dTables::build(int num_max_vals, int n_az_, int n_el_, float az_min, f
 }
 
 int launch_find_local_max_2d(const Peaks2dTables &t, int n_items, const void *d_in, void *d_val, void *d_az, void *d_el,
-                             hipStream_t st)
+                             hipStream_t st, int stride_az_el)
 {
     if (n_items <= 0) return DOA_OK;
     const long long cells = (long long)t.n_az * t.n_el;
-    if (t.M < 1 || t.M > DOA_MAX_PEAKS || t.n_az < 1 || t.n_el < 1 || cells > kPeaks2dMaxCells || !t.d_az.p ||
+    const bool stride_ok = stride_az_el <= 0 || stride_az_el == t.M || (stride_az_el > t.M && cells > kPeaks2dStagedMax);
+    if (t.M < 1 || t.M > DOA_MAX_PEAKS || t.n_az < 1 || t.n_el < 1 || cells > kPeaks2dMaxCells || !stride_ok || !t.d_az.p ||
         !t.d_el.p || !d_in || !d_val || !d_az || !d_el) {
         set_error("find_local_max_2d: bad arguments of the launch (M=%d, grid %d x %d)", t.M, t.n_az, t.n_el);
         return DOA_ERR_INVALID_ARG;
     }
-    const int P = (int)cells;
-    const unsigned long long inv = (1ull << 32) / (unsigned)t.n_az;
-    const Grid2d g{t.n_az, t.n_el, P, t.wrap, inv > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)inv};
+    const int P = (int)cells, stride = stride_az_el > 0 ? stride_az_el : t.M;
+    const Grid2d g = make_grid2d(t.n_az, t.n_el, t.wrap);
     const int vec4 = (P % 4 == 0 && reinterpret_cast<uintptr_t>(d_in) % 16 == 0) ? 1 : 0;
     // two staged sizes, so that a small grid does not take a large grid's 64 KiB of LDS and its two workgroups per CU
-    if (P <= 2048) launch_form<2048>(t, g, n_items, d_in, d_val, d_az, d_el, vec4, st);
-    else if (P <= kPeaks2dStagedMax) launch_form<kPeaks2dStagedMax>(t, g, n_items, d_in, d_val, d_az, d_el, vec4, st);
-    else launch_form<0>(t, g, n_items, d_in, d_val, d_az, d_el, 0, st);
+    if (P <= 2048) launch_form<2048>(t, g, n_items, d_in, d_val, d_az, d_el, vec4, stride, st);
+    else if (P <= kPeaks2dStagedMax) launch_form<kPeaks2dStagedMax>(t, g, n_items, d_in, d_val, d_az, d_el, vec4, stride, st);
+    else launch_form<0>(t, g, n_items, d_in, d_val, d_az, d_el, 0, stride, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }

@@ -212,9 +212,18 @@ struct Peaks2dTables {
 // the argument checks of every entry that takes a grid (who: for the message); false with the error set
 bool peaks2d_args_ok(const char *who, int num_max_vals, int n_az, int n_el, double az_min, double az_max, double el_min,
                      double el_max);
-// d_val, d_az, d_el: t.M floats per item each
+// d_val, d_az, d_el: t.M floats per item each.  stride_az_el > t.M, grids above 16384 cells (the global form) only: item i's
+// azimuths and elevations start stride_az_el floats after item i - 1's (the pipeline's grid mode keeps both in one [n][2 M]
+// buffer, and needs this launch only for such grids)
 int launch_find_local_max_2d(const Peaks2dTables &t, int n_items, const void *d_in, void *d_val, void *d_az, void *d_el,
-                             hipStream_t st);
+                             hipStream_t st, int stride_az_el = 0);
+// The steering-table scan with find_local_max_2d's pick on its LDS row (array_scan.hip): per item the spectrum row (stored
+// only if d_spec is given) and the 3 t.M outputs are bit for bit those of launch_array_scan followed by
+// launch_find_local_max_2d on the same full records.  pk.cells() == t.P.  Grids of up to kArrayGridFusedMax cells are one
+// launch and write no row without d_spec; larger ones are the two launches named, and need d_spec (the caller's scratch).
+constexpr int kArrayGridFusedMax = 16384;
+int launch_array_scan_peaks2d(const ArrayTable &t, const Peaks2dTables &pk, int n_items, const void *d_full, void *d_spec,
+                              void *d_val, void *d_az, void *d_el, int stride_az_el, hipStream_t st);
 
 // K6 (root_music.hip): polynomial roots from the DOUBLE coefficient records -> angles.
 // d_roots (optional, diagnostics): the 2N-2 roots found per item as double2, in the kernel's lane order.

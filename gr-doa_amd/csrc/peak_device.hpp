@@ -418,4 +418,122 @@ __device__ __forceinline__ void peak_pick_stream(Fetch v_at, int L, int M, const
     }
 }
 
+// ---- the two-dimensional rule (find_local_max_2d; stated in include/doa_hip.h) -----------------------------------------------
+// Shared by find_local_max_2d_kernel (find_local_max_2d.hip) and the steering-table scan that ends in the same pick on its
+// LDS row (array_scan.hip): one copy of the peak test, the index split and the ranking key, so the two cannot drift apart.
+constexpr int kPeaks2dThreads = 256;         // both kernels: one workgroup of four waves
+
+struct Grid2d {
+    int n_az, n_el, P, wrap;
+    unsigned inv_az;                         // floor(2^32 / n_az), saturated: split() needs one correction step
+};
+
+// i = e n_az + a, 0 <= i < 2^24: q = umulhi(i, inv_az) is floor(i / n_az) or one less
+__device__ __forceinline__ void split(const Grid2d &g, int i, int &e, int &a)
+{
+    int q = (int)__umulhi((unsigned)i, g.inv_az);
+    int r = i - q * g.n_az;
+    if (r >= g.n_az) { q++; r -= g.n_az; }
+    e = q; a = r;
+}
+
+// The peak test of the rule; row(j) = the value of cell j.  One compare per neighbour: a neighbour BEFORE the cell (j < i) must
+// be strictly smaller, !(w >= c), one AFTER it may be equal, !(w > c); a NaN neighbour passes both, and so does the NaN that
+// stands in for a neighbour that does not exist.  The row above lies before the cell and the row below after it, whatever
+// the wrap does; in the cell's own row the left neighbour lies before it unless it is the wrapped one (a == 0), the right
+// one after it unless wrapped.  n_az == 1: the wrapped azimuth neighbours are the cell itself and the cells above and
+// below it, which the middle column covers.  EARLY (the global form): leave after the first row that rules the cell out.
+template <bool EARLY, class Row> __device__ __forceinline__ bool is_peak(const Row &row, const Grid2d &g, int i, float c)
+{
+    int e, a;
+    split(g, i, e, a);
+    const bool first = a == 0, last = a == g.n_az - 1, side = g.n_az > 1;
+    const bool vl = side && (!first || g.wrap), vr = side && (!last || g.wrap);
+    const int dl = first ? g.n_az - 1 : -1, dr = last ? 1 - g.n_az : 1;
+    // the global form never reads a cell that does not exist; the LDS form reads the cell itself in its place and discards it,
+    // which keeps its nine reads unconditional and in flight together
+    const auto val = [&](bool exists, int j) {
+        if constexpr (EARLY) return exists ? row(j) : NAN;
+        else { const float w = row(exists ? j : i); return exists ? w : NAN; }
+    };
+    const bool vu = e > 0, vd = e < g.n_el - 1;
+    const int ju = i - g.n_az, jd = i + g.n_az;
+    const float wl = val(vl, i + dl), wr = val(vr, i + dr);
+    bool ok = (c == c) & (first ? !(wl > c) : !(wl >= c)) & (last ? !(wr >= c) : !(wr > c));
+    if (EARLY && !ok) return false;
+    const float u0 = val(vu && vl, ju + dl), u1 = val(vu, ju), u2 = val(vu && vr, ju + dr);
+    ok = ok & !(u0 >= c) & !(u1 >= c) & !(u2 >= c);
+    if (EARLY && !ok) return false;
+    const float d0 = val(vd && vl, jd + dl), d1 = val(vd, jd), d2 = val(vd && vr, jd + dr);
+    return ok & !(d0 > c) & !(d1 > c) & !(d2 > c);
+}
+
+// strictly after (pv, pi) in the order (value descending, index ascending)
+__device__ __forceinline__ bool key_after(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
+
+// the workgroup's best (value, index), uniform in every thread.  The wave results alternate between two LDS slots by round,
+// so one barrier per round is enough: a wave reaches round r + 2 only after every wave has read round r's slot.
+__device__ __forceinline__ void block_argbest(float &v, int &i, float (&sv)[2][4], int (&si)[2][4], int round)
+{
+    wave_argbest(v, i);
+    const int wib = threadIdx.x / kWave, buf = round & 1;
+    if ((threadIdx.x & (kWave - 1)) == 0) { sv[buf][wib] = v; si[buf][wib] = i; }
+    __syncthreads();
+    v = sv[buf][0]; i = si[buf][0];
+#pragma unroll
+    for (int w = 1; w < kPeaks2dThreads / kWave; w++)
+        if (cand_better(sv[buf][w], si[buf][w], v, i)) { v = sv[buf][w]; i = si[buf][w]; }
+}
+
+// Where a pick writes: M values per item; azimuths and elevations, read from the two axes, `stride` >= M floats apart per item
+struct Peaks2dOut {
+    const float *az, *el;
+    float *val, *oaz, *oel;
+    int M, stride;
+};
+
+// The top M peaks of one item by a GROUP of threads (a wave, or the workgroup), straight to the outputs: up to M rounds with
+// the key (value descending, index ascending), each strictly after the previous round's key, NaN beyond the number of peaks.
+//   scan(first, pv, pi, bv, bi)   the calling thread's best peak cell into (bv, bi): any peak if `first`, else one after (pv, pi)
+//   best(bv, bi, round)           the group's best pair, uniform in the group (wave_argbest, block_argbest)
+//   id                            the thread's index in the group: thread 0 stores a round's peak, threads r .. M - 1 the NaN
+template <class Scan, class Best>
+__device__ __forceinline__ void peaks2d_rounds(const Grid2d &g, const Peaks2dOut &o, size_t item, int id, Scan &&scan, Best &&best)
+{
+    float *ov = o.val + item * (size_t)o.M, *oa = o.oaz + item * (size_t)o.stride, *oe = o.oel + item * (size_t)o.stride;
+    float pv = 0.f;
+    int pi = -1, r = 0;
+    for (; r < o.M; r++) {
+        float bv = 0.f;
+        int bi = INT_MAX;
+        scan(r == 0, pv, pi, bv, bi);
+        best(bv, bi, r);
+        if (bi == INT_MAX) break;            // uniform in the group: no peak is left
+        pv = bv; pi = bi;
+        if (id == 0) {
+            int e, a;
+            split(g, bi, e, a);
+            ov[r] = bv; oa[r] = o.az[a]; oe[r] = o.el[e];
+        }
+    }
+    if (id >= r && id < o.M) { ov[id] = NAN; oa[id] = NAN; oe[id] = NAN; }
+}
+// scan() over peak flags: `mine` = the flags of cells 64 own .. 64 own + 63 of `row`
+__device__ __forceinline__ void flagged_best(const float *row, unsigned long long mine, int own, bool first, float pv, int pi,
+                                             float &bv, int &bi)
+{
+    for (unsigned long long m = mine; m != 0ull; m &= m - 1ull) {
+        const int i = 64 * own + (int)__builtin_ctzll(m);
+        const float c = row[i];
+        if ((first || key_after(c, i, pv, pi)) && cand_better(c, i, bv, bi)) { bv = c; bi = i; }
+    }
+}
+
+// host: the grid as the kernels take it (n_az * n_el <= 2^24)
+inline Grid2d make_grid2d(int n_az, int n_el, int wrap)
+{
+    const unsigned long long inv = (1ull << 32) / (unsigned)n_az;
+    return Grid2d{n_az, n_el, n_az * n_el, wrap ? 1 : 0, inv > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)inv};
+}
+
 }  // namespace doa

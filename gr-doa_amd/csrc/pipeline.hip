@@ -20,6 +20,8 @@ struct doa_music_pipeline : doa::PipeFront {
     double loading = 0.0;           // Capon: the diagonal loading
     bool has_table = false;         // doa_music_pipeline_set_steering_table: an arbitrary array geometry
     doa::ArrayTable array;          // its table in the scan's form (array_scan.hip)
+    bool has_grid = false;          // doa_pipeline_set_steering_grid: the table's rows are an azimuth x elevation grid (has_table
+    doa::Peaks2dTables grid;        // is set too) and the pick is find_local_max_2d's on these axes; argmax is [n][2 M]
     // a lane's slots after the front's: coefficient records, their Chebyshev twins, spectrum rows nobody asked for, the serial
     // peak pick's scratch, Capon's status words (int32 per item between the inverse launch and the NaN follow-up), a
     // steering-table handle's full records (N * N doubles per item between the stage in front and the scan)
@@ -82,6 +84,22 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
         }
         if (rc != DOA_OK) return rc;
         if (skip & 4) return n;
+        if (h->has_grid) {
+            // grid mode: the scan and find_local_max_2d's pick on the row in LDS are ONE launch, which stores a row only for a
+            // caller that asked for it (a grid too large for LDS is two launches and borrows the scratch rows); argmax holds
+            // M azimuths, then M elevations per item
+            const int M = h->grid.M;
+            void *rows = store_spec ? spec : (h->array.P > doa::kArrayGridFusedMax ? ws.spec_scratch : nullptr);
+            float *am_az = static_cast<float *>(am);
+            rc = doa::launch_array_scan_peaks2d(h->array, h->grid, n, ws.full, rows, mx, am_az, am_az + M, 2 * M, st);
+            // Capon: a status-1 item's NaN record gave a 0.0 dB row and its one peak; the chain of blocks ends with a NaN row
+            // and 3 M NaN for it (the second launch covers the 2 M wide argmax)
+            if (rc == DOA_OK && capon && !(skip & 2))
+                rc = doa::launch_capon_invalid_rows(h->array.P, M, n, ws.status, store_spec ? spec : nullptr, mx, nullptr, st);
+            if (rc == DOA_OK && capon && !(skip & 2))
+                rc = doa::launch_capon_invalid_rows(0, 2 * M, n, ws.status, nullptr, nullptr, am, st);
+            return rc == DOA_OK ? n : rc;
+        }
         rc = doa::launch_array_scan(h->array, n, ws.full, spec, nullptr, st);
         if (rc != DOA_OK) return rc;
         rc = doa::launch_peak_pick(h->peaks, n, spec, nullptr, mx, am, *ws.scratch, (size_t)h->max_batch, ws.scratch_item_off, st);
@@ -263,6 +281,7 @@ int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double 
         h->peaks.release();
         h->peaks = std::move(axis);
         h->has_table = false;
+        h->has_grid = false; h->grid = doa::Peaks2dTables{};
         return DOA_OK;
     }
     if (!std::isfinite(x_min) || !std::isfinite(x_max) || !(x_max > x_min)) {
@@ -289,6 +308,41 @@ int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double 
     h->array.release(); h->peaks.release();
     h->array = std::move(table); h->peaks = std::move(axis);
     h->has_table = true;
+    h->has_grid = false; h->grid = doa::Peaks2dTables{};     // a plain table replaces a grid
+    return DOA_OK;
+}
+
+int doa_pipeline_set_steering_grid(doa_music_pipeline_t *h, const double *steering, int n_az, int n_el, float az_min, float az_max,
+                                   float el_min, float el_max, int wrap_az)
+{
+    doa::clear_error();
+    const char *who = "pipeline_set_steering_grid";
+    if (!h) { doa::set_error("%s: bad arguments (NULL handle)", who); return DOA_ERR_INVALID_ARG; }
+    const int N = h->N, P = h->music.P, M = h->music.M;
+    if (!doa::peaks2d_args_ok(who, M, n_az, n_el, az_min, az_max, el_min, el_max)) return DOA_ERR_INVALID_ARG;
+    if ((long long)n_az * n_el != P) {
+        doa::set_error("%s: the grid %d x %d does not have the handle's pspectrum_len = %d cells", who, n_az, n_el, P);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (!doa::steering_table_finite(steering, N, P)) {
+        doa::set_error("%s: the table (%d rows of %d complex doubles) is NULL or holds a value that is not finite", who, P, N);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (h->S) {
+        doa::set_error("%s: spatial smoothing is on, and it assumes a translation-invariant (uniform linear) array", who);
+        return DOA_ERR_UNSUPPORTED;
+    }
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    // built aside and swapped in at the end: a failure leaves the handle as it was.  The one-dimensional axis (h->peaks) stays:
+    // nothing reads it in grid mode but its length, and both ways out of grid mode rebuild it
+    doa::ArrayTable table;
+    doa::Peaks2dTables axes;
+    int rc = table.build(N, P, steering);
+    if (rc == DOA_OK) rc = axes.build(M, n_az, n_el, az_min, az_max, el_min, el_max, wrap_az);
+    if (rc == DOA_OK) rc = reserve_self(h, {h->S, h->bits, h->estimator, true});
+    if (rc != DOA_OK) return rc;
+    h->array = std::move(table); h->grid = std::move(axes);
+    h->has_table = true; h->has_grid = true;
     return DOA_OK;
 }
 
@@ -521,7 +575,8 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
     // [max | argmax | cov | spectrum]; on the chunked path the peaks lie in the transport's result block, the covariances
     // and spectra in the handle's own workspace at their item offsets
     using H = doa_music_pipeline;
-    const doa::HostSection sec[4] = {{max_out, M * sizeof(float), nullptr}, {argmax_out, M * sizeof(float), nullptr},
+    const size_t am_floats = h->has_grid ? 2 * M : M;           // grid mode: M azimuths, then M elevations
+    const doa::HostSection sec[4] = {{max_out, M * sizeof(float), nullptr}, {argmax_out, am_floats * sizeof(float), nullptr},
                                      {cov_out, N * N * sizeof(float2), h->self.buf[H::kCov].p},
                                      {spectrum_out, P * sizeof(float), h->self.buf[H::kSpec].p}};
     return h->host_run(who, noutput_items, input_items, sec, 4,

@@ -48,7 +48,7 @@ no HIP device is usable.  There is no CPU fallback.
 from ._lib import DoaError, LIB_PATH, last_error  # noqa: F401
 from .blocks import (autocorrelate, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, rootMUSIC_linear_array,  # noqa: F401
                      esprit_linear_array,
-                     MUSIC_array, capon_array, planar_steering_table, uca_positions, planar_steering_grid, find_local_max_2d,
+                     MUSIC_array, capon_array, planar_steering_table, uca_positions, planar_steering_grid, find_local_max_2d, array_grid_debug,
                      music_pipeline, root_pipeline, root_music_pipeline, autocorrelate_sc16, music_pipeline_sc16,
                      root_music_pipeline_sc16, compass_mean, sim_source, set_internal_precision, get_internal_precision, device_count,
                      evd_fallback_count, DETACHED,

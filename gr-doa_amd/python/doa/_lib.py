@@ -202,11 +202,14 @@ SIGNATURES = {
     "doa_esprit_linear_array_work_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_esprit_linear_array_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "doa_root_pipeline_set_estimator": (C.c_int, [_vp, C.c_int]),
+    "doa_pipeline_set_steering_grid": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_capon_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_esprit_linear_array_record_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_hip_array_grid_debug": (C.c_int, [C.c_int, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                                           C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_root_pipeline_inject_failure": (C.c_int, [_vp, C.c_int]),
     "doa_root_pipeline_lanes_idle": (C.c_int, [_vp]),
     "doa_hip_evd_fallback_counter_device_debug": (C.c_int, []),

@@ -553,6 +553,23 @@ def planar_steering_grid(positions, n_az, n_el, az_min=0.0, az_max=360.0, el_min
     return out
 
 
+def array_grid_debug(table, n_az, n_el, records, num_max_vals, fused=True, az_min=0.0, az_max=360.0, el_min=0.0, el_max=90.0,
+                     wrap_az=True, spectrum=True):
+    """Test hook (doa_hip_array_grid_debug): the steering-table scan that ends in find_local_max_2d's pick, on supplied full
+    records [n, inputs^2] float64 (the packing of csrc/kernels.hpp).  fused: the one launch of music_pipeline's grid mode, else the
+    two launches it replaces.  Returns (spectrum [n, P] or None, values, azimuths, elevations [n, num_max_vals])."""
+    a = _steering(table)
+    rec = np.ascontiguousarray(records, np.float64)
+    n, M = rec.shape[0], int(num_max_vals)
+    assert rec.shape == (n, a.shape[1] ** 2) and a.shape[0] == int(n_az) * int(n_el)
+    spec = np.empty((n, a.shape[0]), _F32) if spectrum else None
+    val, az, el = (np.empty((n, M), _F32) for _ in range(3))
+    check(lib.doa_hip_array_grid_debug(a.shape[1], _vp(a), int(n_az), int(n_el), float(az_min), float(az_max), float(el_min),
+                                       float(el_max), int(bool(wrap_az)), M, n, _vp(rec), int(bool(fused)),
+                                       _vp(spec) if spectrum else C.c_void_p(0), _vp(val), _vp(az), _vp(el)))
+    return spec, val, az, el
+
+
 class find_local_max_2d(_ItemBlock):
     """doa.find_local_max_2d(num_max_vals, n_az, n_el, az_min, az_max, el_min, el_max, wrap_az) — the num_max_vals largest
     local maxima of an azimuth x elevation grid (items of n_az * n_el floats, cell (e, a) at e * n_az + a) as three paired
@@ -915,7 +932,8 @@ class music_pipeline(_Pipeline):
         self.num_targets, self.pspectrum_len, self.max_batch = int(num_targets), int(pspectrum_len), int(max_batch)
         self.subarray_size, self.forward_backward = 0, 0            # set_spatial_smoothing
         self.estimator, self.diagonal_loading = "music", 0.0        # set_estimator
-        self.steering_table = None                                  # set_steering_table
+        self.steering_table = None                                  # set_steering_table / set_steering_grid
+        self.steering_grid = None                                   # set_steering_grid: (n_az, n_el), argmax is [n, 2 M]
         self._h = check_handle(lib.doa_music_pipeline_create(self.inputs, self.snapshot_size, self.overlap_size,
                                                              self.avg_method, self.norm_spacing, self.num_targets,
                                                              self.pspectrum_len, self.max_batch), "music_pipeline")
@@ -956,13 +974,28 @@ class music_pipeline(_Pipeline):
         work_dev_auto (doa_music_pipeline_set_steering_table)."""
         if table is None:
             check(lib.doa_music_pipeline_set_steering_table(self._h, C.c_void_p(0), 0.0, 180.0))
-            self.steering_table = None
+            self.steering_table = self.steering_grid = None
             return
         a = _steering(table)
         if a.shape != (self.pspectrum_len, self.inputs):
             raise ValueError(f"the steering table must be [pspectrum_len, inputs] = [{self.pspectrum_len}, {self.inputs}], got {list(a.shape)}")
         check(lib.doa_music_pipeline_set_steering_table(self._h, _vp(a), float(x_min), float(x_max)))
-        self.steering_table = a
+        self.steering_table, self.steering_grid = a, None
+
+    def set_steering_grid(self, table, n_az, n_el, az_min=0.0, az_max=360.0, el_min=0.0, el_max=90.0, wrap_az=True) -> None:
+        """Grid mode, from the next work call on: table is a [n_az * n_el, inputs] complex steering table whose row e * n_az + a
+        is the direction (azimuth a, elevation e) (planar_steering_grid builds one; n_az * n_el == pspectrum_len), and the peak
+        pick is find_local_max_2d(num_targets, n_az, n_el, az_min, az_max, el_min, el_max, wrap_az) on each row while the scan
+        still holds it on chip.  max stays [n, M]; argmax becomes [n, 2 M]: argmax[:, :M] the azimuths and argmax[:, M:] the
+        elevations, in the order of max, NaN beyond the number of peaks.  The outputs are those of autocorrelate -> MUSIC_array |
+        capon_array -> find_local_max_2d, bit for bit.  Limits as for set_steering_table: no spatial smoothing, no work_dev_auto,
+        internal precision 64.  set_steering_table(None) leaves grid mode (doa_pipeline_set_steering_grid)."""
+        a = _steering(table)
+        if a.shape != (self.pspectrum_len, self.inputs):
+            raise ValueError(f"the steering table must be [pspectrum_len, inputs] = [{self.pspectrum_len}, {self.inputs}], got {list(a.shape)}")
+        check(lib.doa_pipeline_set_steering_grid(self._h, _vp(a), int(n_az), int(n_el), float(az_min), float(az_max), float(el_min),
+                                                 float(el_max), int(bool(wrap_az))))
+        self.steering_table, self.steering_grid = a, (int(n_az), int(n_el))
 
     def set_stages(self, cov=True, evd=True, scan=True) -> None:
         """Profiling aid: drop stages from later work_dev calls (their outputs keep the previous call's values)."""
@@ -1002,10 +1035,13 @@ class music_pipeline(_Pipeline):
     def work(self, noutput_items, input_items, max_out, argmax_out, cov_out=None, spectrum_out=None) -> int:
         """Host buffers in, host buffers out (numpy): input_items[k] = complex64 stream k starting at
         its first history sample; max_out / argmax_out [>=n, M] float32; cov_out [>=n, N*N] complex64
-        and spectrum_out [>=n, P] float32 are optional."""
+        and spectrum_out [>=n, P] float32 are optional.  In grid mode (set_steering_grid) argmax_out is [n, 2 M]."""
         n = int(noutput_items)
         arrs = self._host_streams(input_items, self.input_span(n))
-        for o, dt, per in ((max_out, _F32, self.num_targets), (argmax_out, _F32, self.num_targets),
+        if self.steering_grid is not None and (argmax_out.ndim != 2 or argmax_out.shape[0] < n or argmax_out.shape[1] != 2 * self.num_targets):
+            raise ValueError(f"grid mode: argmax_out must be [>= {n}, 2 * num_targets = {2 * self.num_targets}], got {list(argmax_out.shape)}")
+        am_width = self.num_targets * (2 if self.steering_grid is not None else 1)
+        for o, dt, per in ((max_out, _F32, self.num_targets), (argmax_out, _F32, am_width),
                            (cov_out, _C64, self.inputs ** 2), (spectrum_out, _F32, self.pspectrum_len)):
             if o is not None:
                 assert o.dtype == dt and o.flags.c_contiguous and o.size >= n * per

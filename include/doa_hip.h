@@ -656,6 +656,31 @@ DOA_HIP_API long long doa_find_local_max_2d_items_total(const doa_find_local_max
 DOA_HIP_API int doa_planar_steering_grid(int num_ant_ele, const double *xy, int n_az, double az_min_deg, double az_max_deg,
                                          int n_el, double el_min_deg, double el_max_deg, double *table_out);
 
+/* music_pipeline in GRID MODE: a steering table whose rows are an azimuth x elevation grid, and directions reported as pairs.
+ * A per-handle setting like doa_music_pipeline_set_steering_table, taking effect from the next work call.  (The name does
+ * not begin with doa_music_pipeline_ on purpose: the suite pins the number of entries with that prefix, and this one has a
+ * test of its own.)
+ *   steering    HOST pointer: n_az * n_el rows of `inputs` complex doubles, row e * n_az + a, as doa_planar_steering_grid
+ *               writes them; n_az * n_el must equal the handle's pspectrum_len; every value finite.
+ *   grid, axes  checked as doa_find_local_max_2d_create checks them, with num_max_vals = num_targets.
+ * The chain of a work call is then K1 -> the eigen launch | the Capon inverse (full records) -> ONE launch that scans the
+ * table and runs find_local_max_2d's rule on each item's row while it is in LDS (grids above 16384 cells: the scan and the
+ * pick as two launches).  Outputs of work_dev, work_dev_batches and work, whose signatures do not change:
+ *   spectrum    [n][pspectrum_len], as with a table; optional: without it no row is written to memory at all
+ *   max         [n][num_targets]: the peak values
+ *   argmax      [n][2 num_targets]: argmax[i][0 .. M-1] the azimuths, argmax[i][M .. 2M-1] the elevations, both in the order
+ *               of max (the one order of find_local_max_2d; NaN beyond the number of peaks).  TWICE as wide as in every
+ *               other mode: size the buffer for it; the host entry moves 2 num_targets floats per item.
+ * All of it bit-identical to autocorrelate -> MUSIC_array | capon_array -> find_local_max_2d(num_targets, n_az, n_el, ...)
+ * chained on the device.  A Capon status-1 item ends with a NaN row and 3 num_targets NaN and does not disturb its
+ * neighbours.  Limits as for a table handle: work_dev_auto and switching spatial smoothing on (or setting a grid while it is
+ * on) return DOA_ERR_UNSUPPORTED, so does every work entry at internal precision 32; work_dev_batches runs one chain per
+ * batch.  DOA_ERR_INVALID_ARG for a NULL handle or table, a grid that does not match pspectrum_len, bad limits or a value
+ * that is not finite.  A refused call leaves the handle exactly as it was.  doa_music_pipeline_set_steering_table(h, NULL,
+ * ...) clears the grid with the table; setting a plain table replaces the grid by the table mode (argmax M wide again). */
+DOA_HIP_API int doa_pipeline_set_steering_grid(doa_music_pipeline_t *h, const double *steering, int n_az, int n_el,
+                                               float az_min, float az_max, float el_min, float el_max, int wrap_az);
+
 /* rootMUSIC_linear_array with a count per item: counts = one int32 m_i per item, used in place of the handle's num_targets
  * W.  Items stay W floats wide.  With top = min(W, num_ant_ele - 1):
  *   1 <= m_i <= top   the first m_i slots are what rootMUSIC_linear_array(norm_spacing, m_i, num_ant_ele) writes for the

@@ -64,6 +64,19 @@ DOA_HIP_API int doa_MUSIC_array_debug(doa_MUSIC_array_t *h, int noutput_items, c
 DOA_HIP_API int doa_capon_array_debug(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *inverse_out,
                                       void *null_spectrum_out);
 
+/* The steering-table scan that ends in the two-dimensional peak pick (what music_pipeline's grid mode launches), on
+ * CALLER-SUPPLIED full records: no handle, host buffers, synchronous.  steering: n_az * n_el rows of num_ant_ele complex
+ * doubles; the grid, the limits, wrap_az and num_max_vals as doa_find_local_max_2d_create takes them; records: n_items x
+ * num_ant_ele^2 doubles, the full-record packing ([r + r N] = X[r][r]; r < c: [r + c N] = Re X[r][c], [c + r N] = Im X[r][c]).
+ * fused = 1 runs the one launch, fused = 0 the two launches it replaces (the scan of MUSIC_array / capon_array, then
+ * find_local_max_2d's kernel) on the same records: the outputs must agree bit for bit.  spectrum_out (n_items x n_az n_el
+ * floats) may be NULL, and the fused launch then stores no row; val_out, az_out, el_out: n_items x num_max_vals floats each.
+ * Every argument is validated before the device is touched.  Returns n_items, or DOA_ERR_INVALID_ARG. */
+DOA_HIP_API int doa_hip_array_grid_debug(int num_ant_ele, const double *steering, int n_az, int n_el, float az_min, float az_max,
+                                         float el_min, float el_max, int wrap_az, int num_max_vals, int n_items,
+                                         const double *records, int fused, float *spectrum_out, float *val_out, float *az_out,
+                                         float *el_out);
+
 /* Diagnostics of esprit_linear_array (host buffers, synchronous): ONLY esprit_kernel, the very launch the work entries end
  * in, on CALLER-SUPPLIED signal-subspace records in place of the eigen stage's (records: noutput_items x 2 num_ant_ele^2
  * doubles, [2 (k N + row)] = Re, [.. + 1] = Im of entry `row` of column k; the kernel reads the first m columns of an item
