@@ -62,9 +62,9 @@ template <int G, int S> struct SkewMac {
 };
 
 // returns true when the item's records were written by the fast path; false = the caller must run the Jacobi kernel body
+// out: coef, coef_d and (PN) pn_out
 template <int G, int MC, bool PN>
-__device__ __forceinline__ bool evd_subspace_item(const float2 *__restrict__ Ri, int item, float *__restrict__ coef,
-                                                  double *__restrict__ coef_d, float2 *__restrict__ pn_out, int N,
+__device__ __forceinline__ bool evd_subspace_item(const float2 *__restrict__ Ri, int item, const EvdOut &out, int N,
                                                   double *__restrict__ sXr, double *__restrict__ sXi)
 {
     static_assert(G == 8 || G == 16, "rows per column");
@@ -284,22 +284,15 @@ __device__ __forceinline__ bool evd_subspace_item(const float2 *__restrict__ Ri,
         tr += shfl_d(tr, lane ^ 1); ti += shfl_d(ti, lane ^ 1);
         tr += shfl_d(tr, lane ^ 2); ti += shfl_d(ti, lane ^ 2);
         if (c4 == 0 && l < N) {
-            float *co = coef ? coef + (size_t)item * (2 * N) : nullptr;
-            double *cd = coef_d ? coef_d + (size_t)item * (2 * N) : nullptr;
-            if (l == 0) {
-                const double u0 = (double)N - tr;
-                if (co) { co[0] = (float)u0; co[2 * N - 1] = 0.f; }
-                if (cd) { cd[0] = u0; cd[2 * N - 1] = 0.0; }
-            } else {
-                if (co) { co[2 * l - 1] = (float)-tr; co[2 * l] = (float)-ti; }
-                if (cd) { cd[2 * l - 1] = -tr; cd[2 * l] = -ti; }
-            }
+            float *co = out.coef ? out.coef + (size_t)item * (2 * N) : nullptr;
+            double *cd = out.coef_d ? out.coef_d + (size_t)item * (2 * N) : nullptr;
+            store_coef_entry(co, cd, N, l, (l == 0) ? (double)N - tr : -tr, -ti);
         }
     }
     if constexpr (PN) {
-        if (pn_out) {
+        if (out.pn_out) {
             // P_N[a][b] = delta_ab - sum_c X[a][c] conj(X[b][c]), column-major N x N
-            float2 *po = pn_out + (size_t)item * (N * N);
+            float2 *po = out.pn_out + (size_t)item * (N * N);
             for (int e = lane; e < N * N; e += kWave) {
                 const int a = e % N, b = e / N;
                 double pr = (a == b) ? 1.0 : 0.0, pi = 0.0;
@@ -315,10 +308,6 @@ __device__ __forceinline__ bool evd_subspace_item(const float2 *__restrict__ Ri,
     }
     return true;
 }
-
-}  // namespace doa
-
-namespace doa {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // N <= 4: the same signal-subspace iteration with ONE LANE per covariance item, everything in that lane's registers and no

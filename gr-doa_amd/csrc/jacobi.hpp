@@ -4,7 +4,7 @@
 // Replaces eig_sym (LAPACK cheevd 'V','U') + U_N U_N^H of the reference (lib/MUSIC_lin_array_impl.cc:128-133,
 // lib/rootMUSIC_linear_array_impl.cc:112-116) and the diagonal sums of lib/rootMUSIC_linear_array_impl.cc:74-79.
 #pragma once
-#include "common.hpp"
+#include "kernels.hpp"
 
 namespace doa {
 
@@ -111,16 +111,7 @@ template <typename T> __device__ __forceinline__ T jacobi_prescale(float m)
 }
 
 // ---- per-item source count (doa_source_count, launch_music_evd_counts) ----------------------------------------------
-// Cnt of the EVD bodies: EvdFixedM = the launch-uniform num_targets of every existing entry (no code added); EvdCounts = a
-// count per item, estimated from the item's eigenvalues (counts_in == nullptr: written to count_out) or supplied by the
-// caller (counts_in), plus the optional eigenvalue output.  Double only.
-struct EvdFixedM {};
-struct EvdCounts {
-    const int *counts_in;   // forced mode: M_i per item; nullptr = estimate
-    int *count_out;         // estimate mode: int32 per item
-    float *eig_out;         // optional: N floats per item, ascending, true scale
-    int K, method, kmax;    // num_snapshots, DOA_SOURCE_COUNT_MDL / _AIC, largest count considered
-};
+// Cnt of the EVD bodies: EvdFixedM / EvdCounts (kernels.hpp)
 template <class Cnt> inline constexpr bool kPerItemCounts = false;
 template <> inline constexpr bool kPerItemCounts<EvdCounts> = true;
 

@@ -72,23 +72,47 @@ struct MusicTables {
 // coefficient record per item: [u0, Re u1, Im u1, ..., Re u_{N-1}, Im u_{N-1}, pad] = 2N floats
 inline int coef_stride(int N) { return 2 * N; }
 
-// K2+K3: batched Hermitian EVD + noise projector + diagonal sums.  d_coef (float records, for the
-// scan), d_coef_d (double records, same layout, for the root finder) and d_pn may each be NULL.
-// d_cheb (optional; N <= 4, evd_bits == 64): a second record per item, 8 doubles, holding the null spectrum's polynomial
-// in the form the lean scan kernel evaluates, Q = A(c) + s B(c): [a0, a1, a2, a3, b0, b1, b2, 0] (music_scan_impl.hpp,
-// ChebQ) -- the change of basis is per item, so it belongs to the kernel that runs once per item.
-int launch_music_evd(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,
-                     int evd_bits, hipStream_t st, void *d_cheb = nullptr);
+// ---- K2+K3: batched Hermitian EVD + noise projector + diagonal sums (music_evd.hip) ---------------------------------------
+// The outputs of the eigen stage, every one optional: an entry or a kernel body writes those that are set and that it
+// names below, and ignores the others.  Device pointers; set the fields by name.
+struct EvdOut {
+    float *__restrict__ coef = nullptr;          // float coefficient records, for the float scan
+    double *__restrict__ coef_d = nullptr;       // double coefficient records, same layout: the root finder, the double scan
+    float2 *__restrict__ pn_out = nullptr;       // diagnostics: P_N itself, N x N float2 per item, column-major
+    const float2 *__restrict__ pilot = nullptr;  // calibrate mode: the pilot steering vector, N float2 (read)
+    float2 *__restrict__ cal_out = nullptr;      // calibrate mode: the de-rotated top eigenvector, N float2 per item
+    // (N <= 4, double) a second record per item, 8 doubles, holding the null spectrum's polynomial in the form the lean scan
+    // kernel evaluates, Q = A(c) + s B(c): [a0, a1, a2, a3, b0, b1, b2, 0] (music_scan_impl.hpp, ChebQ) -- the change of
+    // basis is per item, so it belongs to the kernel that runs once per item
+    double *__restrict__ cheb_d = nullptr;
+    double *__restrict__ pn_d = nullptr;         // P_N as a full record (below: launch_music_evd_full), before any rounding
+    double *__restrict__ es_rec = nullptr;       // the signal-subspace record (below: launch_music_evd_record)
+};
+// Cnt of the EVD bodies: EvdFixedM = the launch-uniform num_targets of every existing entry (no code added); EvdCounts = a
+// count per item, estimated from the item's eigenvalues (counts_in == nullptr: written to count_out) or supplied by the
+// caller (counts_in), plus the optional eigenvalue output.  Double only.
+struct EvdFixedM {};
+struct EvdCounts {
+    const int *counts_in;   // forced mode: M_i per item; nullptr = estimate
+    int *count_out;         // estimate mode: int32 per item
+    float *eig_out;         // optional: N floats per item, ascending, true scale
+    int K, method, kmax;    // num_snapshots, DOA_SOURCE_COUNT_MDL / _AIC, largest count considered
+};
+inline EvdCounts evd_counts_forced(const int *counts_in) { return {counts_in, nullptr, nullptr, 0, 0, 0}; }
+inline EvdCounts evd_counts_estimate(int *count_out, float *eig_out, int K, int method, int kmax)
+{
+    return {nullptr, count_out, eig_out, K, method, kmax};
+}
+// Uses out.coef, coef_d, pn_out and cheb_d (N <= 4, evd_bits == 64).
+int launch_music_evd(int N, int M, int n_items, const void *d_R, const EvdOut &out, int evd_bits, hipStream_t st);
 // The same stage with a count PER ITEM (double, always the Jacobi forms: one lane per item for N <= 4, 8 lanes for N <= 8,
-// one wave for N <= 16).  Estimate mode (d_counts_in == NULL): the count comes from the item's eigenvalues (jacobi.hpp:
-// source_count_from_eigenvalues; K snapshots, method DOA_SOURCE_COUNT_*, counts 0..kmax) and is written to d_count_out
-// (int32).  Forced mode: the count is read from d_counts_in (int32).  d_eig_out (optional): N floats per item, ascending, at
-// the item's scale.  d_coef_d (double records) and d_cheb (N <= 4) may be NULL (count / eigenvalues only).  Count 0: the
-// record of P_N = I; a count outside 0..N-1: a NaN record.
-// d_rec (optional): the signal-subspace record (below); with it the launch is the group form at every N (4 lanes per item
-// for N <= 4: the form that holds the eigenvectors by rows) and d_coef_d may be NULL.
-int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_counts_in, void *d_count_out, void *d_eig_out,
-                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st, void *d_rec = nullptr);
+// one wave for N <= 16).  Estimate mode (evd_counts_estimate): the count comes from the item's eigenvalues (jacobi.hpp:
+// source_count_from_eigenvalues; K snapshots, method DOA_SOURCE_COUNT_*, counts 0..kmax) and is written to count_out.
+// Forced mode (evd_counts_forced): the count is read from counts_in.  eig_out (optional): at the item's scale.
+// Uses out.coef_d, cheb_d (N <= 4) and es_rec; with none of them: count / eigenvalues only.  Count 0: the record of
+// P_N = I; a count outside 0..N-1: a NaN record.  With es_rec the launch is the group form at every N (4 lanes per item
+// for N <= 4: the form that holds the eigenvectors by rows).
+int launch_music_evd_counts(int N, int n_items, const void *d_R, const EvdCounts &cnt, const EvdOut &out, hipStream_t st);
 // ---- ESPRIT (esprit.hip; definition in include/doa_hip.h) -----------------------------------------------------------------
 // SIGNAL-SUBSPACE RECORD of an item: all N eigenvectors of H as columns ordered by DESCENDING eigenvalue (the eig_sym
 // ranking reversed), 2 N^2 doubles: [2 (k N + row)] = Re V[row][k], [2 (k N + row) + 1] = Im V[row][k].  A consumer takes
@@ -121,6 +145,18 @@ __device__ __forceinline__ void write_cheb_record(double *__restrict__ o, const 
 {
     o[0] = ux[0] - 2 * ux[2]; o[1] = 2 * ux[1] - 6 * ux[3]; o[2] = 4 * ux[2]; o[3] = 8 * ux[3];
     o[4] = 2 * uy[3] - 2 * uy[1]; o[5] = -4 * uy[2]; o[6] = -8 * uy[3]; o[7] = 0.0;
+}
+// entry l of an item's coefficient records (above: coef_stride), u_l = tr + j ti; l = 0 also writes the pad.  co (float
+// record) and cd (double record): the item's own, either may be NULL
+template <typename T> __device__ __forceinline__ void store_coef_entry(float *co, double *cd, int N, int l, T tr, T ti)
+{
+    if (l == 0) {
+        if (co) { co[0] = (float)tr; co[2 * N - 1] = 0.f; }
+        if (cd) { cd[0] = (double)tr; cd[2 * N - 1] = 0.0; }
+    } else {
+        if (co) { co[2 * l - 1] = (float)tr; co[2 * l] = (float)ti; }
+        if (cd) { cd[2 * l - 1] = (double)tr; cd[2 * l] = (double)ti; }
+    }
 }
 // Capon (capon.hip; definition in include/doa_hip.h): the records of W = (H / mu + loading I)^-1 per item, in place of the
 // eigen stage's -- u_l = sum_r W[r+l, r] in the double coefficient record (d_coef_d, required) and, for N <= 4, the

@@ -208,9 +208,11 @@ int doa_MUSIC_lin_array_work_dev(doa_MUSIC_lin_array_t *h, int noutput_items, co
     const bool cheb = doa::music_uses_cheb(N, h->bits);
     if (rc == DOA_OK && cheb) rc = h->d_cheb.reserve((size_t)noutput_items * doa::kChebRecord * sizeof(double));
     if (rc != DOA_OK) return rc;
-    const bool dbl = (h->bits == 64);
-    rc = doa::launch_music_evd(N, h->tab.M, noutput_items, d_input_items0, dbl ? nullptr : h->d_coef.p,
-                               dbl ? h->d_coef.p : nullptr, nullptr, h->bits, st, cheb ? h->d_cheb.p : nullptr);
+    doa::EvdOut out;
+    if (h->bits == 64) out.coef_d = h->d_coef.as<double>();
+    else out.coef = h->d_coef.as<float>();
+    if (cheb) out.cheb_d = h->d_cheb.as<double>();
+    rc = doa::launch_music_evd(N, h->tab.M, noutput_items, d_input_items0, out, h->bits, st);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_music_scan(h->tab, h->bits, noutput_items, h->d_coef.p, d_output_items0, nullptr, st, nullptr, nullptr, nullptr,
                                 nullptr, true, cheb ? h->d_cheb.p : nullptr);
@@ -247,8 +249,10 @@ int doa_MUSIC_lin_array_work_dev_counts(doa_MUSIC_lin_array_t *h, int noutput_it
     const bool cheb = doa::music_uses_cheb(N, 64);
     if (rc == DOA_OK && cheb) rc = h->d_cheb.reserve((size_t)noutput_items * doa::kChebRecord * sizeof(double));
     if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_evd_counts(N, noutput_items, d_cov_items, d_counts, nullptr, nullptr, 0, 0, 0, h->d_coef.p,
-                                      cheb ? h->d_cheb.p : nullptr, st);
+    doa::EvdOut out;
+    out.coef_d = h->d_coef.as<double>();
+    if (cheb) out.cheb_d = h->d_cheb.as<double>();
+    rc = doa::launch_music_evd_counts(N, noutput_items, d_cov_items, doa::evd_counts_forced((const int *)d_counts), out, st);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_music_scan(h->tab, 64, noutput_items, h->d_coef.p, d_spectrum_out, nullptr, st, nullptr, nullptr, nullptr,
                                 nullptr, true, cheb ? h->d_cheb.p : nullptr);
@@ -289,10 +293,11 @@ int doa_MUSIC_lin_array_debug(doa_MUSIC_lin_array_t *h, int noutput_items, const
     io.out(h->d_pn, projector_out, in_bytes);
     io.out(h->d_coef, nullptr, (size_t)noutput_items * doa::coef_stride(N) * sizeof(double));
     int rc = io.status();
-    const bool dbl = (h->bits == 64);
-    if (rc == DOA_OK)
-        rc = doa::launch_music_evd(N, h->tab.M, noutput_items, h->d_in.p, dbl ? nullptr : h->d_coef.p,
-                                   dbl ? h->d_coef.p : nullptr, h->d_pn.p, h->bits, h->stream);
+    doa::EvdOut out;
+    if (h->bits == 64) out.coef_d = h->d_coef.as<double>();
+    else out.coef = h->d_coef.as<float>();
+    out.pn_out = h->d_pn.as<float2>();
+    if (rc == DOA_OK) rc = doa::launch_music_evd(N, h->tab.M, noutput_items, h->d_in.p, out, h->bits, h->stream);
     if (rc == DOA_OK) rc = doa::launch_music_scan(h->tab, h->bits, noutput_items, h->d_coef.p, h->d_out.p, h->d_q.p, h->stream);
     return io.finish(rc == DOA_OK ? noutput_items : rc);
 }

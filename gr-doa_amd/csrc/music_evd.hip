@@ -10,16 +10,12 @@
 // Rotations: jacobi_rotation (float angle, T-precision unitarity); matrices pre-scaled to max |entry| in [1, 2).
 // Output: one 2N-value coefficient record per item ([u0, Re u1, Im u1, ...]); P_N itself on request.
 #include "jacobi.hpp"
-#include "kernels.hpp"
+#include "evd_subspace.hpp"
 #include <mutex>
 #include <type_traits>
 
 #include <cstdlib>
 
-namespace doa {
-
-}  // namespace doa
-#include "evd_subspace.hpp"
 namespace doa {
 
 // Where item g's covariance matrix lives: one array (EvdOne), or the arrays of a group of batches (EvdGroup: kernels.hpp,
@@ -233,15 +229,17 @@ template <int G, typename T, int ROUND> struct RoundLoop {
 // Cnt = EvdCounts: the group's own count M (jacobi.hpp) -- every lane gathers the eigenvalues by rank, brings them back to
 // the item's scale (inv_sc = 1 / prescale, a power of two) and evaluates the criterion redundantly; poison = 0, or NaN for a
 // non-finite item.
+// out: every field (cheb_d: G == 4 only).
 template <int G, typename T, class Cnt = EvdFixedM>
 __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam, bool real_col, int r, int base, int lane,
-                                                   int item, bool real_item, int N, int M, float *__restrict__ coef,
-                                                   double *__restrict__ coef_d, float2 *__restrict__ pn_out,
-                                                   const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                                   double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{},
-                                                   T inv_sc = (T)1, T poison = (T)0, double *__restrict__ pn_d = nullptr,
-                                                   double *__restrict__ es_rec = nullptr)
+                                                   int item, bool real_item, int N, int M, const EvdOut &out,
+                                                   const Cnt &cnt = Cnt{}, T inv_sc = (T)1, T poison = (T)0)
 {
+    float *const __restrict__ coef = out.coef;
+    double *const __restrict__ coef_d = out.coef_d, *const __restrict__ cheb_d = out.cheb_d;
+    double *const __restrict__ pn_d = out.pn_d, *const __restrict__ es_rec = out.es_rec;
+    float2 *const __restrict__ pn_out = out.pn_out, *const __restrict__ cal_out = out.cal_out;
+    const float2 *const __restrict__ pilot = out.pilot;
     // eigenvalue of lane r = A[r][r]; ascending rank inside the group; noise set = ranks < N-M
     int rank = 0;
 #pragma unroll
@@ -370,15 +368,7 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
             if (count_zero) { tr = ((l == 0) ? (T)N : (T)0) + poison; ti = poison; }
             if (count_bad) { tr = (T)NAN; ti = (T)NAN; }
         }
-        if (r == 0) {
-            if (l == 0) {
-                if (co) co[0] = (float)tr;
-                if (cd) cd[0] = (double)tr;
-            } else {
-                if (co) { co[2 * l - 1] = (float)tr; co[2 * l] = (float)ti; }
-                if (cd) { cd[2 * l - 1] = (double)tr; cd[2 * l] = (double)ti; }
-            }
-        }
+        if (r == 0) store_coef_entry(co, cd, N, l, tr, ti);
     };
     if constexpr (G == 4) {                                  // unrolled: the record copy keeps static indices
 #pragma unroll
@@ -395,43 +385,15 @@ __device__ __forceinline__ void evd_group_epilogue(T (&vr)[G], T (&vi)[G], T lam
             diagonal_sum(l, tr, ti);
         }
     }
-    if (r == 0) {
-        if (co) co[2 * N - 1] = 0.f;
-        if (cd) cd[2 * N - 1] = 0.0;
-        if constexpr (G == 4) {
-            if (cheb_d && real_item) write_cheb_record(cheb_d + (size_t)item * kChebRecord, ux, uy);
-        }
+    if constexpr (G == 4) {
+        if (r == 0 && cheb_d && real_item) write_cheb_record(cheb_d + (size_t)item * kChebRecord, ux, uy);
     }
 }
 
 // the whole group Jacobi of one wave: G lanes per item, `real_item` = this lane's group stores its results
 template <int G, typename T, class Cnt = EvdFixedM>
 __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, int item, bool real_item, int N, int M,
-                                               float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
-                                               const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                               double *__restrict__ cheb_d = nullptr, const Cnt &cnt = Cnt{},
-                                               double *__restrict__ pn_d = nullptr, double *__restrict__ es_rec = nullptr);
-
-template <int G, typename T>
-__global__ __launch_bounds__(64) void music_evd_group_kernel(const float2 *__restrict__ R, float *__restrict__ coef,
-                                                             double *__restrict__ coef_d, float2 *__restrict__ pn_out,
-                                                             int n_items, int N, int M,
-                                                             const float2 *__restrict__ pilot, float2 *__restrict__ cal_out)
-{
-    constexpr int IPW = kWave / G;                       // items per wave
-    const int lane = threadIdx.x & (kWave - 1);
-    int item = blockIdx.x * IPW + lane / G;
-    const bool real_item = item < n_items;
-    if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
-    evd_group_wave<G, T>(R + (size_t)item * (N * N), item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out);
-}
-
-template <int G, typename T, class Cnt>
-__device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, int item, bool real_item, int N, int M,
-                                               float *__restrict__ coef, double *__restrict__ coef_d, float2 *__restrict__ pn_out,
-                                               const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
-                                               double *__restrict__ cheb_d, const Cnt &cnt, double *__restrict__ pn_d,
-                                               double *__restrict__ es_rec)
+                                               const EvdOut &out, const Cnt &cnt = Cnt{})
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int r = lane % G, base = lane - r;
@@ -493,11 +455,31 @@ __device__ __forceinline__ void evd_group_wave(const float2 *__restrict__ Ri, in
 #pragma unroll
     for (int k = 0; k < G; k++) vr[k] += poison;
     if constexpr (kPerItemCounts<Cnt>)
-        evd_group_epilogue<G, T, Cnt>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out,
-                                      cheb_d, cnt, (T)1 / sc, poison, nullptr, es_rec);
+        evd_group_epilogue<G, T, Cnt>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, out, cnt, (T)1 / sc, poison);
     else
-    evd_group_epilogue<G, T>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, coef, coef_d, pn_out, pilot, cal_out, cheb_d,
-                             EvdFixedM{}, (T)1, (T)0, pn_d, es_rec);
+        evd_group_epilogue<G, T>(vr, vi, lam, r < N, r, base, lane, item, real_item, N, M, out);
+}
+
+// This lane's item in a launch of kWave / G items per wave (G lanes each).  Idle groups shadow the last item and store
+// nothing (real_item = false).
+template <int G> __device__ __forceinline__ int evd_group_item(int n_items, bool &real_item)
+{
+    const int item = blockIdx.x * (kWave / G) + (threadIdx.x & (kWave - 1)) / G;
+    real_item = item < n_items;
+    return real_item ? item : n_items - 1;
+}
+
+template <int G, typename T>
+__global__ __launch_bounds__(64) void music_evd_group_kernel(const float2 *__restrict__ R, float *__restrict__ coef,
+                                                             double *__restrict__ coef_d, float2 *__restrict__ pn_out,
+                                                             int n_items, int N, int M,
+                                                             const float2 *__restrict__ pilot, float2 *__restrict__ cal_out)
+{
+    bool real_item;
+    const int item = evd_group_item<G>(n_items, real_item);
+    EvdOut out;
+    out.coef = coef; out.coef_d = coef_d; out.pn_out = pn_out; out.pilot = pilot; out.cal_out = cal_out;
+    evd_group_wave<G, T>(R + (size_t)item * (N * N), item, real_item, N, M, out);
 }
 
 // the group Jacobi with a count per item (launch_music_evd_counts; double)
@@ -506,13 +488,11 @@ __global__ __launch_bounds__(64) void music_evd_group_counts_kernel(const float2
                                                                     int n_items, int N, EvdCounts cnt,
                                                                     double *__restrict__ es_rec)
 {
-    constexpr int IPW = kWave / G;
-    const int lane = threadIdx.x & (kWave - 1);
-    int item = blockIdx.x * IPW + lane / G;
-    const bool real_item = item < n_items;
-    if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
-    evd_group_wave<G, double, EvdCounts>(R + (size_t)item * (N * N), item, real_item, N, 0, nullptr, coef_d, nullptr, nullptr,
-                                         nullptr, nullptr, cnt, nullptr, es_rec);
+    bool real_item;
+    const int item = evd_group_item<G>(n_items, real_item);
+    EvdOut out;
+    out.coef_d = coef_d; out.es_rec = es_rec;
+    evd_group_wave<G, double, EvdCounts>(R + (size_t)item * (N * N), item, real_item, N, 0, out, cnt);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -769,11 +749,9 @@ __global__ __launch_bounds__(64) void music_evd_quad_kernel(const float2 *__rest
                                                             int N, double *__restrict__ cheb_d,
                                                             unsigned long long *__restrict__ fallback_count)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int r = lane & 3;
-    int item = blockIdx.x * 16 + (lane >> 2);
-    const bool real_item = item < n_items;
-    if (!real_item) item = n_items - 1;                        // idle quads shadow the last item (no stores)
+    const int r = threadIdx.x & 3;
+    bool real_item;
+    const int item = evd_group_item<4>(n_items, real_item);
     const float2 *Ri = R + (size_t)item * (N * N);
     double xcr[MC], xci[MC];
     const bool fast = evd_quad_subspace<MC>(Ri, N, r, xcr, xci);
@@ -801,19 +779,8 @@ __global__ __launch_bounds__(64) void music_evd_quad_kernel(const float2 *__rest
             float *co = coef ? coef + (size_t)item * (2 * N) : nullptr;
             double *cd = coef_d ? coef_d + (size_t)item * (2 * N) : nullptr;
 #pragma unroll
-            for (int l = 0; l < 4; l++) {
-                if (l < N) {
-                    if (l == 0) {
-                        if (co) co[0] = (float)ux[0];
-                        if (cd) cd[0] = ux[0];
-                    } else {
-                        if (co) { co[2 * l - 1] = (float)ux[l]; co[2 * l] = (float)uy[l]; }
-                        if (cd) { cd[2 * l - 1] = ux[l]; cd[2 * l] = uy[l]; }
-                    }
-                }
-            }
-            if (co) co[2 * N - 1] = 0.f;
-            if (cd) cd[2 * N - 1] = 0.0;
+            for (int l = 0; l < 4; l++)
+                if (l < N) store_coef_entry(co, cd, N, l, ux[l], uy[l]);
             if (cheb_d) write_cheb_record(cheb_d + (size_t)item * kChebRecord, ux, uy);
         }
         if constexpr (PN) {
@@ -843,7 +810,9 @@ __global__ __launch_bounds__(64) void music_evd_quad_kernel(const float2 *__rest
     const bool need = real_item && !fast;
     if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
         if (fallback_count && need && r == 0) atomicAdd(fallback_count, 1ull);
-        evd_group_wave<4, double>(Ri, item, need, N, MC, coef, coef_d, PN ? pn_out : nullptr, nullptr, nullptr, cheb_d);
+        EvdOut out;
+        out.coef = coef; out.coef_d = coef_d; out.pn_out = PN ? pn_out : nullptr; out.cheb_d = cheb_d;
+        evd_group_wave<4, double>(Ri, item, need, N, MC, out);
     }
 }
 
@@ -900,14 +869,14 @@ __device__ __forceinline__ unsigned caterpillar_mask(unsigned m)
 // sVr / sVi / sLam: 16 x 16 + 16 values of LDS owned by this wave.
 // Cnt = EvdCounts (LEAN only): the item's own count, every lane evaluating the criterion on the eigenvalues the ranking lanes
 // leave sorted in sLam.
+// out: LEAN: coef, coef_d and es_rec; !LEAN: what evd_group_epilogue takes.
 template <typename T, bool LEAN, class Cnt = EvdFixedM>
-__device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, int item, float *__restrict__ coef,
-                                                 double *__restrict__ coef_d, float2 *__restrict__ pn_out, int N, int M,
-                                                 const float2 *__restrict__ pilot, float2 *__restrict__ cal_out,
+__device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, int item, int N, int M, const EvdOut &out,
                                                  T *__restrict__ sVr, T *__restrict__ sVi, T *__restrict__ sLam,
-                                                 const Cnt &cnt = Cnt{}, double *__restrict__ pn_d = nullptr,
-                                                 double *__restrict__ es_rec = nullptr)
+                                                 const Cnt &cnt = Cnt{})
 {
+    float *const __restrict__ coef = out.coef;
+    double *const __restrict__ coef_d = out.coef_d, *const __restrict__ es_rec = out.es_rec;
     constexpr int G = 16;
     const int lane = threadIdx.x & (kWave - 1);
     // lane = 16 (a >> 1) + 2 b + (a & 1): the two block rows that share a 16-lane DPP row are interleaved, so that
@@ -1118,20 +1087,13 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
         if (c4 == 0 && l < N) {
             float *co = coef ? coef + (size_t)item * (2 * N) : nullptr;
             double *cd = coef_d ? coef_d + (size_t)item * (2 * N) : nullptr;
-            if (l == 0) {
-                if (co) { co[0] = (float)tr; co[2 * N - 1] = 0.f; }
-                if (cd) { cd[0] = (double)tr; cd[2 * N - 1] = 0.0; }
-            } else {
-                if (co) { co[2 * l - 1] = (float)tr; co[2 * l] = (float)ti; }
-                if (cd) { cd[2 * l - 1] = (double)tr; cd[2 * l] = (double)ti; }
-            }
+            store_coef_entry(co, cd, N, l, tr, ti);
         }
     } else if (lane < G) {
         T er[G], ei[G];
 #pragma unroll
         for (int k = 0; k < G; k++) { er[k] = sVr[lane * G + k]; ei[k] = sVi[lane * G + k]; }
-        evd_group_epilogue<G, T>(er, ei, sLam[lane], !((pad >> lane) & 1u), lane, 0, lane, item, true, N, M, coef, coef_d,
-                                 pn_out, pilot, cal_out, nullptr, EvdFixedM{}, (T)1, (T)0, pn_d);      // (the record: LEAN only)
+        evd_group_epilogue<G, T>(er, ei, sLam[lane], !((pad >> lane) & 1u), lane, 0, lane, item, true, N, M, out);
     }
 }
 
@@ -1143,7 +1105,9 @@ __global__ __launch_bounds__(64) void music_evd_block16_kernel(const float2 *__r
 {
     __shared__ T sVr[16 * 16], sVi[16 * 16], sLam[16];
     const int item = blockIdx.x;                         // grid = n_items
-    evd_block16_item<T, LEAN>(R + (size_t)item * (N * N), item, coef, coef_d, pn_out, N, M, pilot, cal_out, sVr, sVi, sLam);
+    EvdOut out;
+    out.coef = coef; out.coef_d = coef_d; out.pn_out = pn_out; out.pilot = pilot; out.cal_out = cal_out;
+    evd_block16_item<T, LEAN>(R + (size_t)item * (N * N), item, N, M, out, sVr, sVi, sLam);
 }
 
 // the block Jacobi with a count per item (launch_music_evd_counts; double)
@@ -1153,8 +1117,9 @@ __global__ __launch_bounds__(64) void music_evd_block16_counts_kernel(const floa
 {
     __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
     const int item = blockIdx.x;                         // grid = n_items
-    evd_block16_item<double, true, EvdCounts>(R + (size_t)item * (N * N), item, nullptr, coef_d, nullptr, N, 0, nullptr, nullptr,
-                                              sVr, sVi, sLam, cnt, nullptr, es_rec);
+    EvdOut out;
+    out.coef_d = coef_d; out.es_rec = es_rec;
+    evd_block16_item<double, true, EvdCounts>(R + (size_t)item * (N * N), item, N, 0, out, sVr, sVi, sLam, cnt);
 }
 
 // One wave per item: the signal-subspace iteration (evd_subspace.hpp) first; whatever it does not certify takes the
@@ -1167,22 +1132,19 @@ __global__ __launch_bounds__(64) void music_evd_subspace_kernel(const float2 *__
     __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
     const int item = blockIdx.x;                         // grid = n_items
     const float2 *Ri = R + (size_t)item * (N * N);
-    if (evd_subspace_item<G, MC, PN>(Ri, item, coef, coef_d, pn_out, N, sVr, sVi)) return;
+    EvdOut out;
+    out.coef = coef; out.coef_d = coef_d; out.pn_out = PN ? pn_out : nullptr;
+    if (evd_subspace_item<G, MC, PN>(Ri, item, out, N, sVr, sVi)) return;
     if (fallback_count && (threadIdx.x & (kWave - 1)) == 0) atomicAdd(fallback_count, 1ull);
-    if constexpr (PN) evd_block16_item<double, false>(Ri, item, coef, coef_d, pn_out, N, MC, nullptr, nullptr, sVr, sVi, sLam);
-    else evd_block16_item<double, true>(Ri, item, coef, coef_d, nullptr, N, MC, nullptr, nullptr, sVr, sVi, sLam);
+    evd_block16_item<double, !PN>(Ri, item, N, MC, out, sVr, sVi, sLam);      // (LEAN unless P_N is wanted)
 }
 
 template <int G, int MC>
-static void launch_evd_subspace_gm(int N, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn, hipStream_t st,
+static void launch_evd_subspace_gm(int N, int n_items, const float2 *R, const EvdOut &out, hipStream_t st,
                                    unsigned long long *d_fallback_count)
 {
-    if (d_pn)
-        hipLaunchKernelGGL((music_evd_subspace_kernel<G, MC, true>), dim3(n_items), dim3(64), 0, st, (const float2 *)d_R,
-                           (float *)d_coef, (double *)d_coef_d, (float2 *)d_pn, n_items, N, d_fallback_count);
-    else
-        hipLaunchKernelGGL((music_evd_subspace_kernel<G, MC, false>), dim3(n_items), dim3(64), 0, st, (const float2 *)d_R,
-                           (float *)d_coef, (double *)d_coef_d, nullptr, n_items, N, d_fallback_count);
+    hipLaunchKernelGGL((out.pn_out ? music_evd_subspace_kernel<G, MC, true> : music_evd_subspace_kernel<G, MC, false>), dim3(n_items),
+                       dim3(64), 0, st, R, out.coef, out.coef_d, out.pn_out, n_items, N, d_fallback_count);
 }
 // Diagnostics: items of subspace-kernel launches that took the Jacobi fall-back.  ONE COUNTER PER DEVICE, allocated on first use
 // with that device current (the launchers run with the handle's device bound: bind_device): a kernel only ever adds into
@@ -1242,80 +1204,81 @@ long long evd_fallback_count(bool reset)
 }
 
 // 4 < N <= 16, 1 <= M <= 4, 2 M <= N (the iteration pays when the signal subspace is the small one)
-static bool launch_evd_subspace(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,
-                                hipStream_t st, unsigned long long *d_fallback_count = nullptr)
+static bool launch_evd_subspace(int N, int M, int n_items, const float2 *R, const EvdOut &out, hipStream_t st,
+                                unsigned long long *d_fallback_count)
 {
     if (N <= 4 || N > 16 || M < 1 || M > 4 || 2 * M > N) return false;
-#define DOA_SUB(G_, M_) launch_evd_subspace_gm<G_, M_>(N, n_items, d_R, d_coef, d_coef_d, d_pn, st, d_fallback_count)
+#define DOA_SUB(G_, M_) launch_evd_subspace_gm<G_, M_>(N, n_items, R, out, st, d_fallback_count)
     if (N <= 8) { if (M == 1) DOA_SUB(8, 1); else if (M == 2) DOA_SUB(8, 2); else if (M == 3) DOA_SUB(8, 3); else DOA_SUB(8, 4); }
     else { if (M == 1) DOA_SUB(16, 1); else if (M == 2) DOA_SUB(16, 2); else if (M == 3) DOA_SUB(16, 3); else DOA_SUB(16, 4); }
 #undef DOA_SUB
     return true;
 }
 
-template <typename T>
-static void launch_evd_block16(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,
-                               hipStream_t st, const void *d_pilot = nullptr, void *d_cal = nullptr)
+static int evd_check_size(int N)
 {
-    if (!d_pn && !d_cal)
-        hipLaunchKernelGGL((music_evd_block16_kernel<T, true>), dim3(n_items), dim3(64), 0, st, (const float2 *)d_R,
-                           (float *)d_coef, (double *)d_coef_d, nullptr, n_items, N, M, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((music_evd_block16_kernel<T, false>), dim3(n_items), dim3(64), 0, st, (const float2 *)d_R,
-                           (float *)d_coef, (double *)d_coef_d, (float2 *)d_pn, n_items, N, M, (const float2 *)d_pilot,
-                           (float2 *)d_cal);
+    if (N >= 2 && N <= DOA_MAX_ANT_ELE) return DOA_OK;
+    set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
+    return DOA_ERR_UNSUPPORTED;
 }
 
-template <int G, typename T>
-static void launch_evd_group(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,
-                             hipStream_t st, const void *d_pilot = nullptr, void *d_cal = nullptr)
+// The Jacobi form of an array size, and its grid: one wave per item above 8 elements (G = 16), else 8 lanes per item above 4,
+// else 4 lanes per item.  launch(G as an integral_constant, grid) launches that form's kernel.
+template <class Launch> static void evd_jacobi_form(int N, int n_items, Launch &&launch)
 {
-    constexpr int IPW = kWave / G;
-    dim3 block(64), grid((n_items + IPW - 1) / IPW);
-    hipLaunchKernelGGL((music_evd_group_kernel<G, T>), grid, block, 0, st, (const float2 *)d_R, (float *)d_coef,
-                       (double *)d_coef_d, (float2 *)d_pn, n_items, N, M, (const float2 *)d_pilot, (float2 *)d_cal);
+    if (N > 8) launch(std::integral_constant<int, 16>{}, dim3(n_items));
+    else if (N > 4) launch(std::integral_constant<int, 8>{}, dim3((n_items + 7) / 8));
+    else launch(std::integral_constant<int, 4>{}, dim3((n_items + 15) / 16));
+}
+
+// music_evd_block16_kernel / music_evd_group_kernel; out: coef, coef_d, pn_out, or pilot and cal_out (calibrate mode)
+template <typename T> static void launch_evd_jacobi(int N, int M, int n_items, const float2 *R, const EvdOut &out, hipStream_t st)
+{
+    evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
+        constexpr int G = decltype(g)::value;
+        if constexpr (G < 16)
+            hipLaunchKernelGGL((music_evd_group_kernel<G, T>), grid, dim3(64), 0, st, R, out.coef, out.coef_d, out.pn_out, n_items, N,
+                               M, out.pilot, out.cal_out);
+        else {
+            const bool lean = !out.pn_out && !out.cal_out;
+            hipLaunchKernelGGL((lean ? music_evd_block16_kernel<T, true> : music_evd_block16_kernel<T, false>), grid, dim3(64), 0, st,
+                               R, out.coef, out.coef_d, out.pn_out, n_items, N, M, out.pilot, out.cal_out);
+        }
+    });
 }
 
 // calibrate_lin_array: top eigenvector of each covariance item, de-rotated by the pilot steering vector
 int launch_calibrate(int N, int n_items, const void *d_R, const void *d_pilot, void *d_out, int bits, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    const bool f32 = (bits == 32);
-    if (N > 8) { if (f32) launch_evd_block16<float>(N, 1, n_items, d_R, nullptr, nullptr, nullptr, st, d_pilot, d_out); else launch_evd_block16<double>(N, 1, n_items, d_R, nullptr, nullptr, nullptr, st, d_pilot, d_out); }
-    else if (N > 4) { if (f32) launch_evd_group<8, float>(N, 1, n_items, d_R, nullptr, nullptr, nullptr, st, d_pilot, d_out); else launch_evd_group<8, double>(N, 1, n_items, d_R, nullptr, nullptr, nullptr, st, d_pilot, d_out); }
-    else { if (f32) launch_evd_group<4, float>(N, 1, n_items, d_R, nullptr, nullptr, nullptr, st, d_pilot, d_out); else launch_evd_group<4, double>(N, 1, n_items, d_R, nullptr, nullptr, nullptr, st, d_pilot, d_out); }
+    EvdOut out;
+    out.pilot = (const float2 *)d_pilot;
+    out.cal_out = (float2 *)d_out;
+    if (bits == 32) launch_evd_jacobi<float>(N, 1, n_items, (const float2 *)d_R, out, st);
+    else launch_evd_jacobi<double>(N, 1, n_items, (const float2 *)d_R, out, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
 
 // N <= 4, two or three sources, double: four lanes per item (music_evd_quad_kernel)
-static bool launch_evd_quad(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn, hipStream_t st,
-                            void *d_cheb)
+static bool launch_evd_quad(int N, int M, int n_items, const float2 *R, const EvdOut &out, hipStream_t st)
 {
     // two sources only: with three (N = 4: ONE noise eigenvalue) 1.6 % of random-direction items fall back and take their
     // waves with them -- 26 against the Jacobi's 11 us per 4096 items (profiles/r04_lab_evd_quad.txt)
     // and four antennas only: at N = 3 the one-lane Jacobi is the faster one by far (5.4 against 14.7 us per 4096 random-direction
     // items: a 3 x 3 sweep is three rotations, and the quad spends a lane on padding; profiles/r04_lab_evd_noise_vector.txt)
     if (N != 4 || M != 2) return false;
-    const dim3 grid((n_items + 15) / 16), block(64);
-#define DOA_QUAD(M_, PN_)                                                                                                    \
-    hipLaunchKernelGGL((music_evd_quad_kernel<M_, PN_>), grid, block, 0, st, (const float2 *)d_R, (float *)d_coef,              \
-                       (double *)d_coef_d, (float2 *)d_pn, n_items, N, (double *)d_cheb, evd_fallback_counter())
-    if (d_pn) DOA_QUAD(2, true); else DOA_QUAD(2, false);
-#undef DOA_QUAD
+    hipLaunchKernelGGL((out.pn_out ? music_evd_quad_kernel<2, true> : music_evd_quad_kernel<2, false>), dim3((n_items + 15) / 16),
+                       dim3(64), 0, st, R, out.coef, out.coef_d, out.pn_out, n_items, N, out.cheb_d, evd_fallback_counter());
     return true;
 }
 
-template <int N> static void launch_evd_n(int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,
-                                          int bits, hipStream_t st, void *d_cheb)
+template <int N> static void launch_evd_n(int M, int n_items, const float2 *R, const EvdOut &out, int bits, hipStream_t st)
 {
     dim3 block(64), grid((n_items + 63) / 64);
-    if (bits == 32)
-        hipLaunchKernelGGL((music_evd_kernel<N, float>), grid, block, 0, st, EvdOne{(const float2 *)d_R}, (float *)d_coef,
-                           (double *)d_coef_d, (float2 *)d_pn, n_items, M, (double *)nullptr, (unsigned long long *)nullptr);
-    else
-        hipLaunchKernelGGL((music_evd_kernel<N, double>), grid, block, 0, st, EvdOne{(const float2 *)d_R}, (float *)d_coef,
-                           (double *)d_coef_d, (float2 *)d_pn, n_items, M, (double *)d_cheb, evd_fallback_counter());
+    const bool f32 = (bits == 32);                       // float: no Chebyshev record, and no subspace iteration to count
+    hipLaunchKernelGGL((f32 ? music_evd_kernel<N, float> : music_evd_kernel<N, double>), grid, block, 0, st, EvdOne{R}, out.coef,
+                       out.coef_d, out.pn_out, n_items, M, f32 ? nullptr : out.cheb_d, f32 ? nullptr : evd_fallback_counter());
 }
 
 // the one-lane kernel over a group of batches (music_group_shape_ok shapes: double, and not the quad kernel's N = 4, M = 2)
@@ -1346,50 +1309,43 @@ int launch_music_evd_group(int N, int M, const BatchGroup &grp, void *d_coef_d, 
     return DOA_OK;
 }
 
-template <int N> static void launch_evd_counts_n(int n_items, const void *d_R, const EvdCounts &cnt, void *d_coef_d, void *d_cheb,
-                                                 hipStream_t st)
+template <int N> static void launch_evd_counts_n(int n_items, const float2 *R, const EvdCounts &cnt, const EvdOut &out, hipStream_t st)
 {
     dim3 block(64), grid((n_items + 63) / 64);
-    hipLaunchKernelGGL((music_evd_kernel<N, double, EvdOneCounts>), grid, block, 0, st, EvdOneCounts{(const float2 *)d_R, cnt},
-                       (float *)nullptr, (double *)d_coef_d, (float2 *)nullptr, n_items, 0, (double *)d_cheb,
-                       (unsigned long long *)nullptr);
+    hipLaunchKernelGGL((music_evd_kernel<N, double, EvdOneCounts>), grid, block, 0, st, EvdOneCounts{R, cnt}, (float *)nullptr,
+                       out.coef_d, (float2 *)nullptr, n_items, 0, out.cheb_d, (unsigned long long *)nullptr);
 }
 
-int launch_music_evd_counts(int N, int n_items, const void *d_R, const void *d_counts_in, void *d_count_out, void *d_eig_out,
-                            int K, int method, int kmax, void *d_coef_d, void *d_cheb, hipStream_t st, void *d_rec)
+int launch_music_evd_counts(int N, int n_items, const void *d_R, const EvdCounts &cnt, const EvdOut &out, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    if (N < 2 || N > DOA_MAX_ANT_ELE) {
-        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    if (!d_counts_in && (!d_count_out || K < 2 || kmax < 0 || kmax > N - 1 ||
-                         (method != DOA_SOURCE_COUNT_MDL && method != DOA_SOURCE_COUNT_AIC))) {
-        set_error("source count: bad arguments (K=%d, method=%d, kmax=%d, N=%d)", K, method, kmax, N);
+    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
+    if (!cnt.counts_in && (!cnt.count_out || cnt.K < 2 || cnt.kmax < 0 || cnt.kmax > N - 1 ||
+                           (cnt.method != DOA_SOURCE_COUNT_MDL && cnt.method != DOA_SOURCE_COUNT_AIC))) {
+        set_error("source count: bad arguments (K=%d, method=%d, kmax=%d, N=%d)", cnt.K, cnt.method, cnt.kmax, N);
         return DOA_ERR_INVALID_ARG;
     }
-    const EvdCounts cnt{(const int *)d_counts_in, (int *)d_count_out, (float *)d_eig_out, K, method, kmax};
+    const float2 *R = (const float2 *)d_R;
     // always the Jacobi forms (the subspace iterations never form the noise eigenvalues)
-    if (N > 8) {
-        hipLaunchKernelGGL(music_evd_block16_counts_kernel, dim3(n_items), dim3(64), 0, st, (const float2 *)d_R, (double *)d_coef_d,
-                           n_items, N, cnt, (double *)d_rec);
-    } else if (N > 4) {
-        hipLaunchKernelGGL((music_evd_group_counts_kernel<8>), dim3((n_items + 7) / 8), dim3(64), 0, st, (const float2 *)d_R,
-                           (double *)d_coef_d, n_items, N, cnt, (double *)d_rec);
-    } else if (d_rec) {
-        // the record needs the eigenvectors by rows: four lanes per item (no Chebyshev record from this form's count mode)
-        if (d_cheb) {
+    if (N <= 4 && !out.es_rec) {
+        switch (N) {
+        case 2: launch_evd_counts_n<2>(n_items, R, cnt, out, st); break;
+        case 3: launch_evd_counts_n<3>(n_items, R, cnt, out, st); break;
+        default: launch_evd_counts_n<4>(n_items, R, cnt, out, st); break;
+        }
+    } else {
+        // N <= 4: the record needs the eigenvectors by rows: four lanes per item (no Chebyshev record from this form's count mode)
+        if (N <= 4 && out.cheb_d) {
             set_error("MUSIC: the signal-subspace record and the Chebyshev record do not come from one launch");
             return DOA_ERR_INVALID_ARG;
         }
-        hipLaunchKernelGGL((music_evd_group_counts_kernel<4>), dim3((n_items + 15) / 16), dim3(64), 0, st, (const float2 *)d_R,
-                           (double *)d_coef_d, n_items, N, cnt, (double *)d_rec);
-    } else {
-        switch (N) {
-        case 2: launch_evd_counts_n<2>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
-        case 3: launch_evd_counts_n<3>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
-        default: launch_evd_counts_n<4>(n_items, d_R, cnt, d_coef_d, d_cheb, st); break;
-        }
+        evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
+            constexpr int G = decltype(g)::value;
+            if constexpr (G < 16)
+                hipLaunchKernelGGL((music_evd_group_counts_kernel<G>), grid, dim3(64), 0, st, R, out.coef_d, n_items, N, cnt, out.es_rec);
+            else
+                hipLaunchKernelGGL(music_evd_block16_counts_kernel, grid, dim3(64), 0, st, R, out.coef_d, n_items, N, cnt, out.es_rec);
+        });
     }
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
@@ -1401,13 +1357,11 @@ template <int G>
 __global__ __launch_bounds__(64) void music_evd_group_full_kernel(const float2 *__restrict__ R, double *__restrict__ full,
                                                                   float2 *__restrict__ pn_out, int n_items, int N, int M)
 {
-    constexpr int IPW = kWave / G;                       // items per wave
-    const int lane = threadIdx.x & (kWave - 1);
-    int item = blockIdx.x * IPW + lane / G;
-    const bool real_item = item < n_items;
-    if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
-    evd_group_wave<G, double>(R + (size_t)item * (N * N), item, real_item, N, M, nullptr, nullptr, pn_out, nullptr, nullptr, nullptr,
-                              EvdFixedM{}, full);
+    bool real_item;
+    const int item = evd_group_item<G>(n_items, real_item);
+    EvdOut out;
+    out.pn_out = pn_out; out.pn_d = full;
+    evd_group_wave<G, double>(R + (size_t)item * (N * N), item, real_item, N, M, out);
 }
 
 __global__ __launch_bounds__(64) void music_evd_block16_full_kernel(const float2 *__restrict__ R, double *__restrict__ full,
@@ -1415,8 +1369,9 @@ __global__ __launch_bounds__(64) void music_evd_block16_full_kernel(const float2
 {
     __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
     const int item = blockIdx.x;                         // grid = n_items
-    evd_block16_item<double, false>(R + (size_t)item * (N * N), item, nullptr, nullptr, pn_out, N, M, nullptr, nullptr, sVr, sVi, sLam,
-                                    EvdFixedM{}, full);
+    EvdOut out;
+    out.pn_out = pn_out; out.pn_d = full;
+    evd_block16_item<double, false>(R + (size_t)item * (N * N), item, N, M, out, sVr, sVi, sLam);
 }
 
 // The Jacobi forms writing the signal-subspace record only (kernels.hpp): ESPRIT's eigen launch.
@@ -1424,13 +1379,11 @@ template <int G>
 __global__ __launch_bounds__(64) void music_evd_group_record_kernel(const float2 *__restrict__ R, double *__restrict__ es_rec,
                                                                     int n_items, int N)
 {
-    constexpr int IPW = kWave / G;                       // items per wave
-    const int lane = threadIdx.x & (kWave - 1);
-    int item = blockIdx.x * IPW + lane / G;
-    const bool real_item = item < n_items;
-    if (!real_item) item = n_items - 1;                  // idle groups shadow the last item (no stores)
-    evd_group_wave<G, double>(R + (size_t)item * (N * N), item, real_item, N, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              EvdFixedM{}, nullptr, es_rec);
+    bool real_item;
+    const int item = evd_group_item<G>(n_items, real_item);
+    EvdOut out;
+    out.es_rec = es_rec;
+    evd_group_wave<G, double>(R + (size_t)item * (N * N), item, real_item, N, 1, out);
 }
 
 __global__ __launch_bounds__(64) void music_evd_block16_record_kernel(const float2 *__restrict__ R, double *__restrict__ es_rec,
@@ -1438,30 +1391,26 @@ __global__ __launch_bounds__(64) void music_evd_block16_record_kernel(const floa
 {
     __shared__ double sVr[16 * 16], sVi[16 * 16], sLam[16];
     const int item = blockIdx.x;                         // grid = n_items
-    evd_block16_item<double, true>(R + (size_t)item * (N * N), item, nullptr, nullptr, nullptr, N, 1, nullptr, nullptr, sVr, sVi, sLam,
-                                   EvdFixedM{}, nullptr, es_rec);
+    EvdOut out;
+    out.es_rec = es_rec;
+    evd_block16_item<double, true>(R + (size_t)item * (N * N), item, N, 1, out, sVr, sVi, sLam);
 }
 
 int launch_music_evd_record(int N, int n_items, const void *d_R, void *d_rec, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    if (N < 2 || N > DOA_MAX_ANT_ELE) {
-        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
-        return DOA_ERR_UNSUPPORTED;
-    }
+    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
     if (!d_R || !d_rec) {
         set_error("MUSIC: bad arguments of the record eigen launch (N=%d)", N);
         return DOA_ERR_INVALID_ARG;
     }
-    if (N > 8)
-        hipLaunchKernelGGL(music_evd_block16_record_kernel, dim3(n_items), dim3(64), 0, st, (const float2 *)d_R, (double *)d_rec,
-                           n_items, N);
-    else if (N > 4)
-        hipLaunchKernelGGL((music_evd_group_record_kernel<8>), dim3((n_items + 7) / 8), dim3(64), 0, st, (const float2 *)d_R,
-                           (double *)d_rec, n_items, N);
-    else
-        hipLaunchKernelGGL((music_evd_group_record_kernel<4>), dim3((n_items + 15) / 16), dim3(64), 0, st, (const float2 *)d_R,
-                           (double *)d_rec, n_items, N);
+    evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
+        constexpr int G = decltype(g)::value;
+        if constexpr (G < 16)
+            hipLaunchKernelGGL((music_evd_group_record_kernel<G>), grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_rec, n_items, N);
+        else
+            hipLaunchKernelGGL(music_evd_block16_record_kernel, grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_rec, n_items, N);
+    });
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
@@ -1469,58 +1418,51 @@ int launch_music_evd_record(int N, int n_items, const void *d_R, void *d_rec, hi
 int launch_music_evd_full(int N, int M, int n_items, const void *d_R, void *d_full, void *d_pn, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    if (N < 2 || N > DOA_MAX_ANT_ELE) {
-        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
-        return DOA_ERR_UNSUPPORTED;
-    }
+    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
     if (!d_R || !d_full || M < 1 || M >= N) {
         set_error("MUSIC: bad arguments of the full-record eigen launch (N=%d, M=%d)", N, M);
         return DOA_ERR_INVALID_ARG;
     }
-    if (N > 8)
-        hipLaunchKernelGGL(music_evd_block16_full_kernel, dim3(n_items), dim3(64), 0, st, (const float2 *)d_R, (double *)d_full,
-                           (float2 *)d_pn, n_items, N, M);
-    else if (N > 4)
-        hipLaunchKernelGGL((music_evd_group_full_kernel<8>), dim3((n_items + 7) / 8), dim3(64), 0, st, (const float2 *)d_R,
-                           (double *)d_full, (float2 *)d_pn, n_items, N, M);
-    else
-        hipLaunchKernelGGL((music_evd_group_full_kernel<4>), dim3((n_items + 15) / 16), dim3(64), 0, st, (const float2 *)d_R,
-                           (double *)d_full, (float2 *)d_pn, n_items, N, M);
+    evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
+        constexpr int G = decltype(g)::value;
+        if constexpr (G < 16)
+            hipLaunchKernelGGL((music_evd_group_full_kernel<G>), grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_full,
+                               (float2 *)d_pn, n_items, N, M);
+        else
+            hipLaunchKernelGGL(music_evd_block16_full_kernel, grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_full,
+                               (float2 *)d_pn, n_items, N, M);
+    });
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
 
-int launch_music_evd(int N, int M, int n_items, const void *d_R, void *d_coef, void *d_coef_d, void *d_pn,
-                     int evd_bits, hipStream_t st, void *d_cheb)
+int launch_music_evd(int N, int M, int n_items, const void *d_R, const EvdOut &out, int evd_bits, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    if (N < 2 || N > DOA_MAX_ANT_ELE) {
-        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
-        return DOA_ERR_UNSUPPORTED;
-    }
+    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
+    const float2 *R = (const float2 *)d_R;
     // N <= 4: one lane per item, everything in registers (measured 10.5 us vs 11.0 us for the
     // 4-lane group kernel at batch 4096: at this size the cross-lane traffic eats the shorter
     // dependency chain).  N > 4: 8 lanes per item (N <= 8) or one wave per item (block Jacobi), 15x / 17x faster than
     // one lane per item with the matrices in scratch.
     const bool f32 = (evd_bits == 32);
     // wide arrays, few sources, double: signal-subspace iteration with the block Jacobi as its per-item fall-back
-    if (!f32 && launch_evd_subspace(N, M, n_items, d_R, d_coef, d_coef_d, d_pn, st, evd_fallback_counter())) {
+    if (!f32 && launch_evd_subspace(N, M, n_items, R, out, st, evd_fallback_counter())) {
         DOA_HIP_TRY(hipGetLastError());
         return DOA_OK;
     }
-    if (N > 8) {
-        if (f32) launch_evd_block16<float>(N, M, n_items, d_R, d_coef, d_coef_d, d_pn, st);
-        else launch_evd_block16<double>(N, M, n_items, d_R, d_coef, d_coef_d, d_pn, st);
-    } else if (N > 4) {
-        if (f32) launch_evd_group<8, float>(N, M, n_items, d_R, d_coef, d_coef_d, d_pn, st);
-        else launch_evd_group<8, double>(N, M, n_items, d_R, d_coef, d_coef_d, d_pn, st);
-    } else if (!f32 && DOA_LAB_ENV_INT("DOA_EVD_QUAD", 1) && launch_evd_quad(N, M, n_items, d_R, d_coef, d_coef_d, d_pn, st, d_cheb)) {
+    if (N > 4) {
+        EvdOut jac;                                     // (no pilot, no cal_out: not the calibrate mode)
+        jac.coef = out.coef; jac.coef_d = out.coef_d; jac.pn_out = out.pn_out;
+        if (f32) launch_evd_jacobi<float>(N, M, n_items, R, jac, st);
+        else launch_evd_jacobi<double>(N, M, n_items, R, jac, st);
+    } else if (!f32 && DOA_LAB_ENV_INT("DOA_EVD_QUAD", 1) && launch_evd_quad(N, M, n_items, R, out, st)) {
         // (N <= 4 with M >= 2 in double; M = 1 keeps the one-lane iteration below)
     } else {
         switch (N) {
-        case 2: launch_evd_n<2>(M, n_items, d_R, d_coef, d_coef_d, d_pn, evd_bits, st, d_cheb); break;
-        case 3: launch_evd_n<3>(M, n_items, d_R, d_coef, d_coef_d, d_pn, evd_bits, st, d_cheb); break;
-        default: launch_evd_n<4>(M, n_items, d_R, d_coef, d_coef_d, d_pn, evd_bits, st, d_cheb); break;
+        case 2: launch_evd_n<2>(M, n_items, R, out, evd_bits, st); break;
+        case 3: launch_evd_n<3>(M, n_items, R, out, evd_bits, st); break;
+        default: launch_evd_n<4>(M, n_items, R, out, evd_bits, st); break;
         }
     }
     DOA_HIP_TRY(hipGetLastError());

@@ -108,10 +108,15 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
         return rc == DOA_OK ? n : rc;
     }
     if (!(skip & 2)) {
-        if (capon)
+        if (capon) {
             rc = doa::launch_capon_inverse(h->elements(), n, cov, h->loading, coef, ws.cheb, nullptr, ws.status, st);
-        else
-            rc = doa::launch_music_evd(h->elements(), h->music.M, n, cov, dbl ? nullptr : coef, dbl ? coef : nullptr, nullptr, h->bits, st, ws.cheb);
+        } else {
+            doa::EvdOut out;
+            if (dbl) out.coef_d = (double *)coef;
+            else out.coef = (float *)coef;
+            out.cheb_d = (double *)ws.cheb;
+            rc = doa::launch_music_evd(h->elements(), h->music.M, n, cov, out, h->bits, st);
+        }
     }
     if (rc != DOA_OK) return rc;
     bool peaks_done = false;
@@ -413,9 +418,11 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     void *spec = d_spectrum_out ? d_spectrum_out : ws.spec_scratch;
     rc = run_k1(h, n, d_input_items, cov, ws, st);
     if (rc == DOA_OK) rc = h->run_smoothing(n, cov, ws.smooth, st);
-    if (rc == DOA_OK)
-        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->music.M, ws.coef,
-                                          cheb ? ws.cheb : nullptr, st);
+    doa::EvdOut out;
+    out.coef_d = (double *)ws.coef;
+    if (cheb) out.cheb_d = (double *)ws.cheb;
+    const doa::EvdCounts cnt = doa::evd_counts_estimate((int *)d_count_out, (float *)d_eig_out, h->K, method, h->music.M);
+    if (rc == DOA_OK) rc = doa::launch_music_evd_counts(elements, n, cov, cnt, out, st);
     if (rc == DOA_OK)
         rc = doa::launch_music_scan(h->music, 64, n, ws.coef, spec, nullptr, st, nullptr, nullptr, nullptr, nullptr, true,
                                     cheb ? ws.cheb : nullptr);

@@ -527,7 +527,9 @@ int doa_rootMUSIC_linear_array_work_dev(doa_rootMUSIC_linear_array_t *h, int nou
     int rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
     if (rc == DOA_OK) rc = h->d_status.reserve((size_t)noutput_items * sizeof(int));
     if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_evd(h->N, h->M, noutput_items, d_input_items0, nullptr, h->d_coef.p, nullptr, h->bits, st);
+    doa::EvdOut out;
+    out.coef_d = h->d_coef.as<double>();
+    rc = doa::launch_music_evd(h->N, h->M, noutput_items, d_input_items0, out, h->bits, st);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_root_music(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, d_output_items0,
                                 h->d_status.p, st);
@@ -568,7 +570,9 @@ int doa_rootMUSIC_linear_array_work_dev_counts(doa_rootMUSIC_linear_array_t *h, 
     if (rc != DOA_OK) return rc;
     // forced-count mode: each item's record for its own noise set (a count outside 0..N-1: a NaN record, which the root
     // kernel does not read)
-    rc = doa::launch_music_evd_counts(h->N, noutput_items, d_cov_items, d_counts, nullptr, nullptr, 0, 0, 0, h->d_coef.p, nullptr, st);
+    doa::EvdOut out;
+    out.coef_d = h->d_coef.as<double>();
+    rc = doa::launch_music_evd_counts(h->N, noutput_items, d_cov_items, doa::evd_counts_forced((const int *)d_counts), out, st);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_root_music_counts(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, d_counts, d_angles_out,
                                        d_status_out ? (void *)d_status_out : h->d_status.p, st);
@@ -610,7 +614,9 @@ int doa_rootMUSIC_linear_array_debug(doa_rootMUSIC_linear_array_t *h, int noutpu
     io.out(h->d_status, status_out, (size_t)noutput_items * sizeof(int));
     io.out(h->d_coef, nullptr, (size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
     int rc = io.status();
-    if (rc == DOA_OK) rc = doa::launch_music_evd(h->N, h->M, noutput_items, h->d_in.p, nullptr, h->d_coef.p, nullptr, h->bits, h->stream);
+    doa::EvdOut out;
+    out.coef_d = h->d_coef.as<double>();
+    if (rc == DOA_OK) rc = doa::launch_music_evd(h->N, h->M, noutput_items, h->d_in.p, out, h->bits, h->stream);
     if (rc == DOA_OK)
         rc = doa::launch_root_music(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, h->d_out.p, h->d_status.p,
                                     h->stream, h->d_roots.p);

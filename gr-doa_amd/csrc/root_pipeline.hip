@@ -72,7 +72,9 @@ int run_chain(doa_root_pipeline *h, int n, const void *const *d_in, void *cov, v
         rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, ws.rec, nullptr, angles, ws.status, st);
         return rc == DOA_OK ? n : rc;
     }
-    rc = doa::launch_music_evd(elements, h->M, n, cov, nullptr, ws.coef, nullptr, h->bits, st);
+    doa::EvdOut out;
+    out.coef_d = (double *)ws.coef;
+    rc = doa::launch_music_evd(elements, h->M, n, cov, out, h->bits, st);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_root_music(elements, h->M, h->norm_spacing, n, ws.coef, angles, ws.status, st);
     return rc == DOA_OK ? n : rc;
@@ -212,15 +214,17 @@ int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int noutput_items, c
     void *cov = d_cov_out ? d_cov_out : ws.cov;
     int rc = h->run_k1(n, d_input_items, cov, ws.work, st);
     if (rc == DOA_OK) rc = h->run_smoothing(n, cov, ws.smooth, st);
+    const doa::EvdCounts cnt = doa::evd_counts_estimate((int *)d_count_out, (float *)d_eig_out, h->K, method, h->M);
+    doa::EvdOut out;
     if (rc == DOA_OK && esprit_mode(h)) {       // one estimating eigen launch (counts, eigenvalues, record), the counted ESPRIT kernel
-        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, nullptr, nullptr, st,
-                                          ws.rec);
+        out.es_rec = (double *)ws.rec;
+        rc = doa::launch_music_evd_counts(elements, n, cov, cnt, out, st);
         if (rc == DOA_OK)
             rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, ws.rec, d_count_out, d_angles_out, ws.status, st);
         return rc == DOA_OK ? n : rc;
     }
-    if (rc == DOA_OK)
-        rc = doa::launch_music_evd_counts(elements, n, cov, nullptr, d_count_out, d_eig_out, h->K, method, h->M, ws.coef, nullptr, st);
+    out.coef_d = (double *)ws.coef;
+    if (rc == DOA_OK) rc = doa::launch_music_evd_counts(elements, n, cov, cnt, out, st);
     if (rc == DOA_OK)
         rc = doa::launch_root_music_counts(elements, h->M, h->norm_spacing, n, ws.coef, d_count_out, d_angles_out, ws.status, st);
     return rc == DOA_OK ? n : rc;

@@ -43,8 +43,8 @@ int doa_source_count_work_dev(doa_source_count_t *h, int noutput_items, const vo
     if (int rc = doa::need_bits64("source_count_work_dev", h->bits, "the criterion"); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int rc = doa::launch_music_evd_counts(h->N, noutput_items, d_cov_items, nullptr, d_count_out, d_eig_out, h->K, h->method,
-                                                h->kmax, nullptr, nullptr, static_cast<hipStream_t>(hip_stream));
+    const doa::EvdCounts cnt = doa::evd_counts_estimate((int *)d_count_out, (float *)d_eig_out, h->K, h->method, h->kmax);
+    const int rc = doa::launch_music_evd_counts(h->N, noutput_items, d_cov_items, cnt, doa::EvdOut{}, static_cast<hipStream_t>(hip_stream));
     return rc == DOA_OK ? noutput_items : rc;
 }
 
