@@ -1,6 +1,6 @@
 // array_scan.hip — spectra for an ARBITRARY array geometry on gfx950: the steering-table scan kernel, the host-built table,
-// doa_planar_steering_table and the C ABI of doa_MUSIC_array / doa_capon_array.  Not blocks of the reference; the definition
-// is stated once in include/doa_hip.h.
+// doa_planar_steering_table.  The C ABI of doa_MUSIC_array / doa_capon_array is in spectrum_blocks.hip.  Not blocks of the
+// reference; the definition is stated once in include/doa_hip.h.
 //
 // The ULA scans (music_scan_impl.hpp) never see a matrix, only its 2N-1 diagonal sums, which summarise a^H X a only for
 // a_n = z^n.  Here the stage in front (the Jacobi forms of the eigen stage, the Capon inverse) writes the FULL RECORD of its
@@ -308,22 +308,7 @@ int launch_array_scan_peaks2d(const ArrayTable &t, const Peaks2dTables &pk, int 
 // ---------------------------------------------------------------------------------------------
 #include "block_host.hpp"
 
-// what the two steering-table handles share (bits: the work entries need 64)
-struct ArrayBlock : doa::BlockBase {
-    doa::ArrayTable tab;
-    doa::DevBuf d_in, d_out, d_full, d_q;
-};
-struct doa_MUSIC_array : ArrayBlock {
-    int M = 0;
-};
-struct doa_capon_array : ArrayBlock {
-    double loading = 0.0;
-    doa::DevBuf d_status;
-};
-
-namespace {
-
-int array_validate(const char *who, int num_ant_ele, int pspectrum_len, const double *steering)
+int doa::steering_table_args(const char *who, int num_ant_ele, int pspectrum_len, const double *steering)
 {
     if (num_ant_ele < 2 || num_ant_ele > DOA_MAX_ANT_ELE) {
         doa::set_error("%s: need 2 <= num_ant_ele <= %d (got %d)", who, DOA_MAX_ANT_ELE, num_ant_ele);
@@ -344,56 +329,7 @@ int array_validate(const char *who, int num_ant_ele, int pspectrum_len, const do
     return DOA_OK;
 }
 
-int array_work_args(const char *who, const ArrayBlock *h, int n, std::initializer_list<const void *> required, int min_n = 0)
-{
-    if (int rc = doa::work_args(who, h, n, required, min_n); rc != DOA_OK) return rc;
-    return doa::need_bits64(who, h->bits, "the steering-table scan");
-}
-
-int capon_array_reserve(doa_capon_array *h, int n)
-{
-    return h->d_full.reserve((size_t)n * doa::full_record_len(h->tab.N) * sizeof(double));
-}
-
-// full records (host) -> N x N complex128, column-major
-void unpack_full_records(const std::vector<double> &rec, int N, int n, double *out)
-{
-    const size_t NN = (size_t)N * N;
-    for (int it = 0; it < n; it++) {
-        const double *f = rec.data() + (size_t)it * NN;
-        double *o = out + 2 * (size_t)it * NN;
-        for (int c = 0; c < N; c++) {
-            o[2 * (c + c * N)] = f[c + c * N]; o[2 * (c + c * N) + 1] = 0.0;
-            for (int r = 0; r < c; r++) {
-                const double re = f[r + c * N], im = f[c + r * N];
-                o[2 * (r + c * N)] = re; o[2 * (r + c * N) + 1] = im;
-                o[2 * (c + r * N)] = re; o[2 * (c + r * N) + 1] = -im;
-            }
-        }
-    }
-}
-
-// the two debug entries: items up, the block's full records (front), the scan with its null spectrum, then the records
-// unpacked into matrix_out and the null spectrum down; either output may be NULL
-template <class Front>
-int array_debug(ArrayBlock *h, int n, const void *cov_items, void *matrix_out, void *null_spectrum_out, Front &&front)
-{
-    const int N = h->tab.N, P = h->tab.P;
-    const size_t sp_bytes = (size_t)n * P * sizeof(float);
-    const size_t full_bytes = (size_t)n * doa::full_record_len(N) * sizeof(double);
-    std::vector<double> rec(matrix_out ? full_bytes / sizeof(double) : 0);
-    doa::HostCall io(*h);
-    io.in(h->d_in, cov_items, (size_t)n * N * N * sizeof(float2));
-    io.out(h->d_out, nullptr, sp_bytes);
-    io.out(h->d_q, null_spectrum_out, sp_bytes);
-    io.out(h->d_full, matrix_out ? rec.data() : nullptr, full_bytes);
-    int rc = io.status();
-    if (rc == DOA_OK) rc = front(h->stream);
-    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, h->d_out.p, h->d_q.p, h->stream);
-    rc = io.finish(rc == DOA_OK ? n : rc);
-    if (rc >= 0 && matrix_out) unpack_full_records(rec, N, n, static_cast<double *>(matrix_out));
-    return rc;
-}
+namespace {
 
 // the rows of doa_planar_steering_table (include/doa_hip.h): n_az directions at one elevation; arguments already validated
 void planar_steering_rows(int num_ant_ele, const double *xy, int n_az, double az_min_deg, double az_max_deg, double elevation_deg,
@@ -461,134 +397,6 @@ int doa_planar_steering_grid(int num_ant_ele, const double *xy, int n_az, double
     return DOA_OK;
 }
 
-// ---- MUSIC_array --------------------------------------------------------------------------------------------------------
-doa_MUSIC_array_t *doa_MUSIC_array_create(int num_targets, int num_ant_ele, int pspectrum_len, const double *steering)
-{
-    doa::clear_error();
-    if (array_validate("MUSIC_array", num_ant_ele, pspectrum_len, steering) != DOA_OK) return nullptr;
-    if (num_targets < 1 || num_targets >= num_ant_ele) {
-        doa::set_error("MUSIC_array: need 0 < num_targets < num_ant_ele (got %d, %d)", num_targets, num_ant_ele);
-        return nullptr;
-    }
-    return doa::create_block<doa_MUSIC_array>("MUSIC_array", [&](doa_MUSIC_array &h) {
-        h.M = num_targets;
-        return h.tab.build(num_ant_ele, pspectrum_len, steering);
-    });
-}
-
-void doa_MUSIC_array_destroy(doa_MUSIC_array_t *h) { doa::destroy_block(h); }
-
-long long doa_MUSIC_array_items_total(const doa_MUSIC_array_t *h) { return h ? h->items_total : 0; }
-
-int doa_MUSIC_array_set_internal_precision(doa_MUSIC_array_t *h, int bits)
-{
-    doa::clear_error();
-    if (!h || (bits != 32 && bits != 64)) { doa::set_error("MUSIC_array_set_internal_precision: need a handle and bits = 32 or 64"); return DOA_ERR_INVALID_ARG; }
-    h->bits = bits;
-    return DOA_OK;
-}
-
-int doa_MUSIC_array_work_dev(doa_MUSIC_array_t *h, int noutput_items, const void *d_cov_items, void *d_spectrum_out, void *hip_stream)
-{
-    doa::clear_error();
-    if (int rc = array_work_args("MUSIC_array_work_dev", h, noutput_items, {d_cov_items, d_spectrum_out}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int N = h->tab.N, n = noutput_items;
-    int rc = h->d_full.reserve((size_t)n * doa::full_record_len(N) * sizeof(double));
-    if (rc == DOA_OK) rc = doa::launch_music_evd_full(N, h->M, n, d_cov_items, h->d_full.p, nullptr, st);
-    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, d_spectrum_out, nullptr, st);
-    if (rc != DOA_OK) return rc;
-    h->items_total += n;
-    return n;
-}
-
-int doa_MUSIC_array_work(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out)
-{
-    doa::clear_error();
-    if (int rc = array_work_args("MUSIC_array_work", h, noutput_items, {cov_items, spectrum_out}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    doa::HostCall io(*h);
-    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
-    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
-    int rc = io.status();
-    if (rc == DOA_OK) rc = doa_MUSIC_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
-    return io.finish(rc);
-}
-
-int doa_MUSIC_array_debug(doa_MUSIC_array_t *h, int noutput_items, const void *cov_items, void *projector_out, void *null_spectrum_out)
-{
-    doa::clear_error();
-    if (int rc = array_work_args("MUSIC_array_debug", h, noutput_items, {cov_items}, 1); rc != DOA_OK) return rc;
-    return array_debug(h, noutput_items, cov_items, projector_out, null_spectrum_out, [&](hipStream_t st) {
-        return doa::launch_music_evd_full(h->tab.N, h->M, noutput_items, h->d_in.p, h->d_full.p, nullptr, st);
-    });
-}
-
-// ---- capon_array --------------------------------------------------------------------------------------------------------
-doa_capon_array_t *doa_capon_array_create(int num_ant_ele, int pspectrum_len, const double *steering, float diagonal_loading)
-{
-    doa::clear_error();
-    if (array_validate("capon_array", num_ant_ele, pspectrum_len, steering) != DOA_OK) return nullptr;
-    if (!std::isfinite(diagonal_loading) || diagonal_loading < 0.0f) {
-        doa::set_error("capon_array: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
-        return nullptr;
-    }
-    return doa::create_block<doa_capon_array>("capon_array", [&](doa_capon_array &h) {
-        h.loading = (double)diagonal_loading;
-        return h.tab.build(num_ant_ele, pspectrum_len, steering);
-    });
-}
-
-void doa_capon_array_destroy(doa_capon_array_t *h) { doa::destroy_block(h); }
-
-long long doa_capon_array_items_total(const doa_capon_array_t *h) { return h ? h->items_total : 0; }
-
-int doa_capon_array_work_dev(doa_capon_array_t *h, int noutput_items, const void *d_cov_items, void *d_spectrum_out,
-                             void *d_status_out, void *hip_stream)
-{
-    doa::clear_error();
-    if (int rc = array_work_args("capon_array_work_dev", h, noutput_items, {d_cov_items, d_spectrum_out}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int N = h->tab.N, n = noutput_items;
-    int rc = capon_array_reserve(h, n);
-    if (rc == DOA_OK && !d_status_out) rc = h->d_status.reserve((size_t)n * sizeof(int));
-    if (rc != DOA_OK) return rc;
-    void *status = d_status_out ? d_status_out : h->d_status.p;
-    rc = doa::launch_capon_inverse(N, n, d_cov_items, h->loading, nullptr, nullptr, nullptr, status, st, h->d_full.p);
-    if (rc == DOA_OK) rc = doa::launch_array_scan(h->tab, n, h->d_full.p, d_spectrum_out, nullptr, st);
-    if (rc == DOA_OK) rc = doa::launch_capon_invalid_rows(h->tab.P, 0, n, status, d_spectrum_out, nullptr, nullptr, st);
-    if (rc != DOA_OK) return rc;
-    h->items_total += n;
-    return n;
-}
-
-int doa_capon_array_work(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out, void *status_out)
-{
-    doa::clear_error();
-    if (int rc = array_work_args("capon_array_work", h, noutput_items, {cov_items, spectrum_out}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    doa::HostCall io(*h);
-    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
-    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
-    io.out(h->d_status, status_out, (size_t)noutput_items * sizeof(int));
-    int rc = io.status();
-    if (rc == DOA_OK) rc = doa_capon_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->d_status.p, h->stream);
-    return io.finish(rc);
-}
-
-int doa_capon_array_debug(doa_capon_array_t *h, int noutput_items, const void *cov_items, void *inverse_out, void *null_spectrum_out)
-{
-    doa::clear_error();
-    if (int rc = array_work_args("capon_array_debug", h, noutput_items, {cov_items}, 1); rc != DOA_OK) return rc;
-    return array_debug(h, noutput_items, cov_items, inverse_out, null_spectrum_out, [&](hipStream_t st) {
-        return doa::launch_capon_inverse(h->tab.N, noutput_items, h->d_in.p, h->loading, nullptr, nullptr, nullptr, nullptr, st, h->d_full.p);
-    });
-}
-
 // ---- the scan with the two-dimensional pick, on supplied full records (include/doa_hip_test.h) ----------------------------
 int doa_hip_array_grid_debug(int num_ant_ele, const double *steering, int n_az, int n_el, float az_min, float az_max, float el_min,
                              float el_max, int wrap_az, int num_max_vals, int n_items, const double *records, int fused,
@@ -598,7 +406,7 @@ int doa_hip_array_grid_debug(int num_ant_ele, const double *steering, int n_az, 
     const char *who = "hip_array_grid_debug";
     if (!doa::peaks2d_args_ok(who, num_max_vals, n_az, n_el, az_min, az_max, el_min, el_max)) return DOA_ERR_INVALID_ARG;
     const int P = n_az * n_el, N = num_ant_ele, M = num_max_vals, n = n_items;
-    if (int rc = array_validate(who, N, P, steering); rc != DOA_OK) return rc;
+    if (int rc = doa::steering_table_args(who, N, P, steering); rc != DOA_OK) return rc;
     if (n < 1 || !records || !val_out || !az_out || !el_out || (fused != 0 && fused != 1)) {
         doa::set_error("%s: need n_items >= 1, the records, the three outputs and fused = 0 or 1 (got %d items, fused %d)", who, n, fused);
         return DOA_ERR_INVALID_ARG;

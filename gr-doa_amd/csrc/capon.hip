@@ -1,5 +1,5 @@
-// capon.hip — the Capon (MVDR) spectrum of a uniform linear array on gfx950: capon_inverse_kernel and the C ABI of
-// doa_capon_lin_array.  Not a block of the reference; the definition is stated once in include/doa_hip.h.
+// capon.hip — the Capon (MVDR) spectrum of a uniform linear array on gfx950: capon_inverse_kernel (the C ABI of
+// doa_capon_lin_array: spectrum_blocks.hip).  Not a block of the reference; the definition is stated once in include/doa_hip.h.
 //
 // For a ULA the scan kernels (music_scan_impl.hpp) never see a matrix, only its diagonal sums u_l = sum_r W[r+l, r]
 // (music.hip:8-13), and they output 1/Q normalised to the row maximum.  So the Capon spectrum 1 / (a^H R^-1 a) is the MUSIC
@@ -330,35 +330,32 @@ __global__ __launch_bounds__(256) void capon_invalid_rows_kernel(const int *__re
     if (am && lane < M) am[(size_t)item * M + lane] = NAN;
 }
 
-template <int N> void launch_capon_lane(int n_items, const void *d_R, double loading, void *d_coef_d, void *d_cheb, void *d_w_out,
-                                        void *d_status, hipStream_t st, void *d_full)
+template <int N> void launch_capon_lane(int n_items, const void *d_R, double loading, const CaponOut &out, hipStream_t st)
 {
     const dim3 grid((n_items + 63) / 64), block(64);
-    if (d_w_out || d_full)
-        hipLaunchKernelGGL((capon_inverse_lane_kernel<N, true>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (double *)d_cheb, (float2 *)d_w_out, (int *)d_status, n_items, (double *)d_full);
+    if (out.w_out || out.full)
+        hipLaunchKernelGGL((capon_inverse_lane_kernel<N, true>), grid, block, 0, st, (const float2 *)d_R, loading, out.coef_d, out.cheb_d,
+                           out.w_out, out.status, n_items, out.full);
     else
-        hipLaunchKernelGGL((capon_inverse_lane_kernel<N, false>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (double *)d_cheb, (float2 *)nullptr, (int *)d_status, n_items, (double *)nullptr);
+        hipLaunchKernelGGL((capon_inverse_lane_kernel<N, false>), grid, block, 0, st, (const float2 *)d_R, loading, out.coef_d, out.cheb_d,
+                           (float2 *)nullptr, out.status, n_items, (double *)nullptr);
 }
 
-template <int G> void launch_capon_group(int N, int n_items, const void *d_R, double loading, void *d_coef_d, void *d_w_out,
-                                         void *d_status, hipStream_t st, void *d_full)
+template <int G> void launch_capon_group(int N, int n_items, const void *d_R, double loading, const CaponOut &out, hipStream_t st)
 {
     constexpr int IPW = kWave / G;
     const dim3 grid((n_items + IPW - 1) / IPW), block(64);
-    if (d_w_out || d_full)
-        hipLaunchKernelGGL((capon_inverse_group_kernel<G, true>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (float2 *)d_w_out, (int *)d_status, n_items, N, (double *)d_full);
+    if (out.w_out || out.full)
+        hipLaunchKernelGGL((capon_inverse_group_kernel<G, true>), grid, block, 0, st, (const float2 *)d_R, loading, out.coef_d, out.w_out,
+                           out.status, n_items, N, out.full);
     else
-        hipLaunchKernelGGL((capon_inverse_group_kernel<G, false>), grid, block, 0, st, (const float2 *)d_R, loading, (double *)d_coef_d,
-                           (float2 *)nullptr, (int *)d_status, n_items, N, (double *)nullptr);
+        hipLaunchKernelGGL((capon_inverse_group_kernel<G, false>), grid, block, 0, st, (const float2 *)d_R, loading, out.coef_d,
+                           (float2 *)nullptr, out.status, n_items, N, (double *)nullptr);
 }
 
 }  // namespace
 
-int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, void *d_coef_d, void *d_cheb, void *d_w_out,
-                         void *d_status, hipStream_t st, void *d_full)
+int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, const CaponOut &out, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
     if (N < 2 || N > DOA_MAX_ANT_ELE) {
@@ -366,16 +363,16 @@ int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, vo
         return DOA_ERR_UNSUPPORTED;
     }
     // the diagonal-sum records are what the ULA scans read; a caller that asks for full records may leave them out
-    const bool need_records = !d_full;
-    if (!d_R || (need_records && (!d_coef_d || (music_uses_cheb(N, 64) && !d_cheb))) || !(loading >= 0.0) || !std::isfinite(loading)) {
+    const bool need_records = !out.full;
+    if (!d_R || (need_records && (!out.coef_d || (music_uses_cheb(N, 64) && !out.cheb_d))) || !(loading >= 0.0) || !std::isfinite(loading)) {
         set_error("Capon: bad arguments of the inverse launch (N=%d, loading=%g)", N, loading);
         return DOA_ERR_INVALID_ARG;
     }
-    if (N > 8) launch_capon_group<16>(N, n_items, d_R, loading, d_coef_d, d_w_out, d_status, st, d_full);
-    else if (N > 4) launch_capon_group<8>(N, n_items, d_R, loading, d_coef_d, d_w_out, d_status, st, d_full);
-    else if (N == 4) launch_capon_lane<4>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st, d_full);
-    else if (N == 3) launch_capon_lane<3>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st, d_full);
-    else launch_capon_lane<2>(n_items, d_R, loading, d_coef_d, d_cheb, d_w_out, d_status, st, d_full);
+    if (N > 8) launch_capon_group<16>(N, n_items, d_R, loading, out, st);
+    else if (N > 4) launch_capon_group<8>(N, n_items, d_R, loading, out, st);
+    else if (N == 4) launch_capon_lane<4>(n_items, d_R, loading, out, st);
+    else if (N == 3) launch_capon_lane<3>(n_items, d_R, loading, out, st);
+    else launch_capon_lane<2>(n_items, d_R, loading, out, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
@@ -390,120 +387,3 @@ int launch_capon_invalid_rows(int P, int M, int n_items, const void *d_status, v
 }
 
 }  // namespace doa
-
-// ---------------------------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------------------------
-#include "block_host.hpp"
-
-struct doa_capon_lin_array : doa::BlockBase {          // bits: the work entries need 64
-    doa::MusicTables tab;
-    double loading = 0.0;
-    doa::DevBuf d_in, d_out, d_coef, d_cheb, d_status, d_w, d_q;
-};
-
-static int capon_work_args(const char *who, doa_capon_lin_array_t *h, int n, std::initializer_list<const void *> required, int min_n = 0)
-{
-    if (int rc = doa::work_args(who, h, n, required, min_n); rc != DOA_OK) return rc;
-    return doa::need_bits64(who, h->bits, "the Capon inverse");
-}
-
-static int capon_reserve_records(doa_capon_lin_array_t *h, int n)
-{
-    const int N = h->tab.N;
-    int rc = h->d_coef.reserve((size_t)n * doa::coef_stride(N) * sizeof(double));
-    if (rc == DOA_OK && doa::music_uses_cheb(N, 64)) rc = h->d_cheb.reserve((size_t)n * doa::kChebRecord * sizeof(double));
-    return rc;
-}
-
-extern "C" {
-
-doa_capon_lin_array_t *doa_capon_lin_array_create(float norm_spacing, int num_ant_ele, int pspectrum_len, float diagonal_loading)
-{
-    doa::clear_error();
-    if (num_ant_ele < 2 || num_ant_ele > DOA_MAX_ANT_ELE) {
-        doa::set_error("capon_lin_array: need 2 <= num_ant_ele <= %d (got %d)", DOA_MAX_ANT_ELE, num_ant_ele);
-        return nullptr;
-    }
-    if (!(norm_spacing > 0.0f) || norm_spacing > 0.5f) {
-        doa::set_error("capon_lin_array: need 0 < norm_spacing <= 0.5 (got %g)", (double)norm_spacing);
-        return nullptr;
-    }
-    if (pspectrum_len <= 0) {
-        doa::set_error("capon_lin_array: pspectrum_len must be > 0 (got %d)", pspectrum_len);
-        return nullptr;
-    }
-    if (!std::isfinite(diagonal_loading) || diagonal_loading < 0.0f) {
-        doa::set_error("capon_lin_array: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
-        return nullptr;
-    }
-    return doa::create_block<doa_capon_lin_array>("capon_lin_array", [&](doa_capon_lin_array &h) {
-        h.loading = (double)diagonal_loading;
-        return h.tab.build(norm_spacing, 1, num_ant_ele, pspectrum_len);      // the scan's tables; their M is unused by the scan
-    });
-}
-
-void doa_capon_lin_array_destroy(doa_capon_lin_array_t *h) { doa::destroy_block(h); }
-
-long long doa_capon_lin_array_items_total(const doa_capon_lin_array_t *h) { return h ? h->items_total : 0; }
-
-int doa_capon_lin_array_work_dev(doa_capon_lin_array_t *h, int noutput_items, const void *d_cov_items, void *d_spectrum_out,
-                                 void *d_status_out, void *hip_stream)
-{
-    doa::clear_error();
-    if (int rc = capon_work_args("capon_lin_array_work_dev", h, noutput_items, {d_cov_items, d_spectrum_out}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int N = h->tab.N, n = noutput_items;
-    int rc = capon_reserve_records(h, n);
-    if (rc == DOA_OK && !d_status_out) rc = h->d_status.reserve((size_t)n * sizeof(int));
-    if (rc != DOA_OK) return rc;
-    void *status = d_status_out ? d_status_out : h->d_status.p;
-    void *cheb = doa::music_uses_cheb(N, 64) ? h->d_cheb.p : nullptr;
-    rc = doa::launch_capon_inverse(N, n, d_cov_items, h->loading, h->d_coef.p, cheb, nullptr, status, st);
-    if (rc == DOA_OK)
-        rc = doa::launch_music_scan(h->tab, 64, n, h->d_coef.p, d_spectrum_out, nullptr, st, nullptr, nullptr, nullptr, nullptr, true, cheb);
-    if (rc == DOA_OK) rc = doa::launch_capon_invalid_rows(h->tab.P, 0, n, status, d_spectrum_out, nullptr, nullptr, st);
-    if (rc != DOA_OK) return rc;
-    h->items_total += n;
-    return n;
-}
-
-int doa_capon_lin_array_work(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out, void *status_out)
-{
-    doa::clear_error();
-    if (int rc = capon_work_args("capon_lin_array_work", h, noutput_items, {cov_items, spectrum_out}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    doa::HostCall io(*h);
-    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
-    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
-    io.out(h->d_status, status_out, (size_t)noutput_items * sizeof(int));
-    int rc = io.status();
-    if (rc == DOA_OK) rc = doa_capon_lin_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->d_status.p, h->stream);
-    return io.finish(rc);
-}
-
-int doa_capon_lin_array_debug(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items, void *inverse_out,
-                              void *null_spectrum_out)
-{
-    doa::clear_error();
-    if (int rc = capon_work_args("capon_lin_array_debug", h, noutput_items, {cov_items}, 1); rc != DOA_OK) return rc;
-    const int N = h->tab.N, P = h->tab.P, n = noutput_items;
-    const size_t in_bytes = (size_t)n * N * N * sizeof(float2);
-    const size_t sp_bytes = (size_t)n * P * sizeof(float);
-    doa::HostCall io(*h);
-    io.in(h->d_in, cov_items, in_bytes);
-    io.out(h->d_out, nullptr, sp_bytes);
-    io.out(h->d_q, null_spectrum_out, sp_bytes);
-    io.out(h->d_w, inverse_out, in_bytes);
-    int rc = io.status();
-    if (rc == DOA_OK) rc = capon_reserve_records(h, n);
-    if (rc == DOA_OK)
-        rc = doa::launch_capon_inverse(N, n, h->d_in.p, h->loading, h->d_coef.p, doa::music_uses_cheb(N, 64) ? h->d_cheb.p : nullptr,
-                                       h->d_w.p, nullptr, h->stream);
-    if (rc == DOA_OK) rc = doa::launch_music_scan(h->tab, 64, n, h->d_coef.p, h->d_out.p, h->d_q.p, h->stream);
-    return io.finish(rc == DOA_OK ? n : rc);
-}
-
-}  // extern "C"

@@ -159,13 +159,16 @@ template <typename T> __device__ __forceinline__ void store_coef_entry(float *co
     }
 }
 // Capon (capon.hip; definition in include/doa_hip.h): the records of W = (H / mu + loading I)^-1 per item, in place of the
-// eigen stage's -- u_l = sum_r W[r+l, r] in the double coefficient record (d_coef_d, required) and, for N <= 4, the
-// Chebyshev record (d_cheb, required there).  d_w_out (optional, diagnostics): W as N x N float2, column-major.  d_status
-// (optional): int32 per item, 0 ok / 1 not positive definite enough or non-finite; such an item's records (and W) are NaN.
-// d_full (optional): W as a full record for launch_array_scan (below), from the same double values as d_w_out; with it
-// d_coef_d and d_cheb may be NULL (the records of the ULA scans are then not written).
-int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, void *d_coef_d, void *d_cheb, void *d_w_out,
-                         void *d_status, hipStream_t st, void *d_full = nullptr);
+// eigen stage's.  Its outputs, in the style of EvdOut (device pointers; set the fields by name).  An item that is not positive
+// definite enough, or not finite, has status 1 and NaN in every record.
+struct CaponOut {
+    double *coef_d = nullptr;   // u_l = sum_r W[r+l, r] as a double coefficient record: required unless `full` is set
+    double *cheb_d = nullptr;   // N <= 4: the Chebyshev record, required wherever coef_d is
+    float2 *w_out = nullptr;    // diagnostics: W as N x N float2, column-major
+    double *full = nullptr;     // W as a full record for launch_array_scan (below), from the same double values as w_out
+    int *status = nullptr;      // int32 per item: 0 ok / 1
+};
+int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, const CaponOut &out, hipStream_t st);
 // after scan and peak pick of a Capon call: for items with status != 0 the spectrum row (P floats; d_spec may be NULL) and the
 // M peak values / locations (d_max / d_argmax may be NULL) become NaN (the scan kernels write 0.0 dB for a NaN record)
 int launch_capon_invalid_rows(int P, int M, int n_items, const void *d_status, void *d_spec, void *d_max, void *d_argmax,
@@ -192,6 +195,8 @@ struct ArrayTable {
 };
 // validation shared by the create entries and doa_music_pipeline_set_steering_table: every entry finite
 bool steering_table_finite(const double *steering, int N, int P);
+// the table checks of every create that takes one (who: for the message): DOA_OK, or DOA_ERR_INVALID_ARG with the error set
+int steering_table_args(const char *who, int num_ant_ele, int pspectrum_len, const double *steering);
 // Q_i = sum_k record[k] T[k][i] in double, q = (float) Q, out = 1 / q, dB against the row maximum with the scan kernels' own
 // normalisation (music_scan_impl.hpp: LeanNorm / db_from_ratio).  d_q (optional): q, P floats per item.
 int launch_array_scan(const ArrayTable &t, int n_items, const void *d_full, void *d_spec, void *d_q, hipStream_t st);

@@ -1,4 +1,4 @@
-// music.hip — MUSIC_lin_array on gfx950: host-side constructor tables, the K4 dispatch and the C ABI.
+// music.hip — MUSIC_lin_array on gfx950: host-side constructor tables and the K4 dispatch (the C ABI: spectrum_blocks.hip).
 //
 // Replaces gr::doa::MUSIC_lin_array (reference lib/MUSIC_lin_array_impl.cc):
 //   ctor  :47-87,98-104  element positions, float-accumulated theta grid, steering vectors
@@ -15,10 +15,7 @@
 #include "music_scan.hpp"
 #include "peak_device.hpp"
 
-#include <climits>
 #include <cmath>
-#include <cstdlib>
-#include <type_traits>
 #include <vector>
 
 namespace doa {
@@ -138,192 +135,3 @@ int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, v
 }
 
 }  // namespace doa
-
-// ---------------------------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------------------------
-#include "block_host.hpp"
-
-struct doa_MUSIC_lin_array : doa::BlockBase {
-    doa::MusicTables tab;
-    doa::DevBuf d_in, d_out, d_coef, d_pn, d_q, d_cheb, d_counts;
-};
-
-static int music_validate(const char *who, float norm_spacing, int num_targets, int num_ant_ele)
-{
-    // grc/doa_MUSIC_lin_array.xml:33-35 (inputs > 0, inputs > num_targets, norm_spacing <= 0.5); the
-    // reference ctor does not validate (num_targets >= N would index cols(0,-1)), so create fails here.
-    if (num_ant_ele <= 0 || num_targets <= 0 || num_targets >= num_ant_ele) {
-        doa::set_error("%s: need 0 < num_targets < num_ant_ele (got %d, %d)", who, num_targets, num_ant_ele);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (!(norm_spacing > 0.0f) || norm_spacing > 0.5f) {
-        doa::set_error("%s: need 0 < norm_spacing <= 0.5 (got %g)", who, (double)norm_spacing);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (num_ant_ele > DOA_MAX_ANT_ELE) {
-        doa::set_error("%s: num_ant_ele=%d exceeds DOA_MAX_ANT_ELE=%d", who, num_ant_ele, DOA_MAX_ANT_ELE);
-        return DOA_ERR_UNSUPPORTED;
-    }
-    return DOA_OK;
-}
-
-// checks of the per-item-count entries
-static int music_counts_args(const char *who, doa_MUSIC_lin_array_t *h, int n, const void *cov, const void *counts, const void *out)
-{
-    if (int rc = doa::work_args(who, h, n, {cov, counts, out}); rc != DOA_OK) return rc;
-    return doa::need_bits64(who, h->bits, "per-item counts");
-}
-
-extern "C" {
-
-doa_MUSIC_lin_array_t *doa_MUSIC_lin_array_create(float norm_spacing, int num_targets, int num_ant_ele,
-                                                  int pspectrum_len)
-{
-    doa::clear_error();
-    if (music_validate("MUSIC_lin_array", norm_spacing, num_targets, num_ant_ele) != DOA_OK) return nullptr;
-    if (pspectrum_len <= 0) {
-        doa::set_error("MUSIC_lin_array: pspectrum_len must be > 0 (got %d)", pspectrum_len);
-        return nullptr;
-    }
-    return doa::create_block<doa_MUSIC_lin_array>("MUSIC_lin_array", [&](doa_MUSIC_lin_array &h) {
-        return h.tab.build(norm_spacing, num_targets, num_ant_ele, pspectrum_len);
-    });
-}
-
-void doa_MUSIC_lin_array_destroy(doa_MUSIC_lin_array_t *h) { doa::destroy_block(h); }
-
-long long doa_MUSIC_lin_array_items_total(const doa_MUSIC_lin_array_t *h) { return h ? h->items_total : 0; }
-
-int doa_MUSIC_lin_array_work_dev(doa_MUSIC_lin_array_t *h, int noutput_items, const void *d_input_items0,
-                                 void *d_output_items0, void *hip_stream)
-{
-    doa::clear_error();
-    if (int rc = doa::work_args("MUSIC_lin_array_work_dev", h, noutput_items, {d_input_items0, d_output_items0}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int N = h->tab.N;
-    int rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(N) * sizeof(double));
-    const bool cheb = doa::music_uses_cheb(N, h->bits);
-    if (rc == DOA_OK && cheb) rc = h->d_cheb.reserve((size_t)noutput_items * doa::kChebRecord * sizeof(double));
-    if (rc != DOA_OK) return rc;
-    doa::EvdOut out;
-    if (h->bits == 64) out.coef_d = h->d_coef.as<double>();
-    else out.coef = h->d_coef.as<float>();
-    if (cheb) out.cheb_d = h->d_cheb.as<double>();
-    rc = doa::launch_music_evd(N, h->tab.M, noutput_items, d_input_items0, out, h->bits, st);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_scan(h->tab, h->bits, noutput_items, h->d_coef.p, d_output_items0, nullptr, st, nullptr, nullptr, nullptr,
-                                nullptr, true, cheb ? h->d_cheb.p : nullptr);
-    if (rc != DOA_OK) return rc;
-    h->items_total += noutput_items;
-    return noutput_items;
-}
-
-int doa_MUSIC_lin_array_work(doa_MUSIC_lin_array_t *h, int noutput_items, const void *input_items0,
-                             void *output_items0)
-{
-    doa::clear_error();
-    if (int rc = doa::work_args("MUSIC_lin_array_work", h, noutput_items, {input_items0, output_items0}); rc != DOA_OK) return rc;
-    if (noutput_items == 0) return 0;
-    doa::HostCall io(*h);
-    io.in(h->d_in, input_items0, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
-    io.out(h->d_out, output_items0, (size_t)noutput_items * h->tab.P * sizeof(float));
-    int rc = io.status();
-    if (rc == DOA_OK) rc = doa_MUSIC_lin_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
-    return io.finish(rc);
-}
-
-int doa_MUSIC_lin_array_work_dev_counts(doa_MUSIC_lin_array_t *h, int noutput_items, const void *d_cov_items,
-                                        const void *d_counts, void *d_spectrum_out, void *hip_stream)
-{
-    doa::clear_error();
-    if (int rc = music_counts_args("MUSIC_lin_array_work_dev_counts", h, noutput_items, d_cov_items, d_counts, d_spectrum_out); rc != DOA_OK)
-        return rc;
-    if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int N = h->tab.N;
-    int rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(N) * sizeof(double));
-    const bool cheb = doa::music_uses_cheb(N, 64);
-    if (rc == DOA_OK && cheb) rc = h->d_cheb.reserve((size_t)noutput_items * doa::kChebRecord * sizeof(double));
-    if (rc != DOA_OK) return rc;
-    doa::EvdOut out;
-    out.coef_d = h->d_coef.as<double>();
-    if (cheb) out.cheb_d = h->d_cheb.as<double>();
-    rc = doa::launch_music_evd_counts(N, noutput_items, d_cov_items, doa::evd_counts_forced((const int *)d_counts), out, st);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_scan(h->tab, 64, noutput_items, h->d_coef.p, d_spectrum_out, nullptr, st, nullptr, nullptr, nullptr,
-                                nullptr, true, cheb ? h->d_cheb.p : nullptr);
-    if (rc == DOA_OK) rc = doa::launch_music_invalid_rows(N, h->tab.P, noutput_items, d_counts, d_spectrum_out, st);
-    if (rc != DOA_OK) return rc;
-    h->items_total += noutput_items;
-    return noutput_items;
-}
-
-int doa_MUSIC_lin_array_work_counts(doa_MUSIC_lin_array_t *h, int noutput_items, const void *cov_items, const void *counts,
-                                    void *spectrum_out)
-{
-    doa::clear_error();
-    if (int rc = music_counts_args("MUSIC_lin_array_work_counts", h, noutput_items, cov_items, counts, spectrum_out); rc != DOA_OK)
-        return rc;
-    if (noutput_items == 0) return 0;
-    doa::HostCall io(*h);
-    io.in(h->d_in, cov_items, (size_t)noutput_items * h->tab.N * h->tab.N * sizeof(float2));
-    io.in(h->d_counts, counts, (size_t)noutput_items * sizeof(int));
-    io.out(h->d_out, spectrum_out, (size_t)noutput_items * h->tab.P * sizeof(float));
-    int rc = io.status();
-    if (rc == DOA_OK) rc = doa_MUSIC_lin_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, h->stream);
-    return io.finish(rc);
-}
-
-int doa_MUSIC_lin_array_debug(doa_MUSIC_lin_array_t *h, int noutput_items, const void *input_items0,
-                              void *projector_out, void *null_spectrum_out)
-{
-    doa::clear_error();
-    if (int rc = doa::work_args("MUSIC_lin_array_debug", h, noutput_items, {input_items0}, 1); rc != DOA_OK) return rc;
-    const int N = h->tab.N, P = h->tab.P;
-    const size_t in_bytes = (size_t)noutput_items * N * N * sizeof(float2);
-    const size_t sp_bytes = (size_t)noutput_items * P * sizeof(float);
-    doa::HostCall io(*h);
-    io.in(h->d_in, input_items0, in_bytes);
-    io.out(h->d_out, nullptr, sp_bytes);
-    io.out(h->d_q, null_spectrum_out, sp_bytes);
-    io.out(h->d_pn, projector_out, in_bytes);
-    io.out(h->d_coef, nullptr, (size_t)noutput_items * doa::coef_stride(N) * sizeof(double));
-    int rc = io.status();
-    doa::EvdOut out;
-    if (h->bits == 64) out.coef_d = h->d_coef.as<double>();
-    else out.coef = h->d_coef.as<float>();
-    out.pn_out = h->d_pn.as<float2>();
-    if (rc == DOA_OK) rc = doa::launch_music_evd(N, h->tab.M, noutput_items, h->d_in.p, out, h->bits, h->stream);
-    if (rc == DOA_OK) rc = doa::launch_music_scan(h->tab, h->bits, noutput_items, h->d_coef.p, h->d_out.p, h->d_q.p, h->stream);
-    return io.finish(rc == DOA_OK ? noutput_items : rc);
-}
-
-long long doa_hip_evd_fallback_count(int reset)
-{
-    doa::clear_error();
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return -1;
-    return doa::evd_fallback_count(reset != 0);
-}
-
-int doa_hip_evd_fallback_counter_device_debug(void)
-{
-    doa::clear_error();
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return -1;
-    return doa::evd_fallback_counter_device(doa::evd_fallback_counter());
-}
-
-int doa_MUSIC_lin_array_set_internal_precision(doa_MUSIC_lin_array_t *h, int bits)
-{
-    doa::clear_error();
-    if (!h || (bits != 32 && bits != 64)) { doa::set_error("MUSIC_lin_array_set_internal_precision: need a handle and bits = 32 or 64"); return DOA_ERR_INVALID_ARG; }
-    h->bits = bits;
-    return DOA_OK;
-}
-
-}  // extern "C"

@@ -1470,3 +1470,23 @@ int launch_music_evd(int N, int M, int n_items, const void *d_R, const EvdOut &o
 }
 
 }  // namespace doa
+
+extern "C" {
+
+long long doa_hip_evd_fallback_count(int reset)
+{
+    doa::clear_error();
+    int dev = 0;
+    if (doa::ensure_device(&dev) != DOA_OK) return -1;
+    return doa::evd_fallback_count(reset != 0);
+}
+
+int doa_hip_evd_fallback_counter_device_debug(void)
+{
+    doa::clear_error();
+    int dev = 0;
+    if (doa::ensure_device(&dev) != DOA_OK) return -1;
+    return doa::evd_fallback_counter_device(doa::evd_fallback_counter());
+}
+
+}  // extern "C"

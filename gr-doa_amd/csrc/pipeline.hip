@@ -7,6 +7,7 @@
 // (covariances, coefficient records, spectra) stay in HBM-resident buffers owned by the handle
 // unless the caller asks for them.
 #include "pipeline_front.hpp"
+#include "spectrum_chain.hpp"
 
 #include <cmath>
 #include <utility>
@@ -29,21 +30,40 @@ struct doa_music_pipeline : doa::PipeFront {
 };
 static_assert(doa_music_pipeline::kFull < doa::PipeLane::kBufs, "a lane has a buffer per slot");
 
-// what one K1 -> EVD -> scan chain needs besides its inputs and outputs
+// what one K1 -> front -> scan chain needs besides its inputs and outputs
 struct PipeWs {
     void *cov;              // covariance items, for a chain whose caller does not ask for them
-    void *coef;             // coefficient records of the chain's items
-    void *cheb;             // N <= 4, double: their pre-transformed twins for the lean scan kernel (else NULL)
+    doa::SpectrumRecords rec;   // the records between the front and the scan (spectrum_chain.hpp)
     void *spec_scratch;     // P floats per item, used when the caller does not want the spectrum
     void *work;             // K1's piece sums (overlapping windows), or NULL
     void *smooth;           // spatial smoothing on: S * S gr_complex per item (else unused)
-    void *status;           // Capon: int32 per item (else unused)
-    void *full;             // steering-table handle: N * N doubles per item (else unused)
-    doa::DevBuf *scratch;   // grown on demand: the serial peak pick of unusual vector lengths
-    size_t scratch_item_off;
+    doa::SpectrumPick pick; // the handle's axes and the scratch of the serial peak pick; a chain adds its two outputs
 };
 
-// K1 -> EVD -> scan (+ peak) for n items on `st` with the workspace `ws`.
+// what sizes a workspace besides the create parameters; a setter passes the configuration it is about to commit, so that a
+// failure leaves the handle as it was.  Every setter that changes one of these reserves `self` for the new configuration, so
+// `self` always holds the records of the configuration the handle is in.
+struct MusicCfg {
+    int S, bits, estimator;
+    bool has_table;
+};
+static MusicCfg cfg_of(const doa_music_pipeline *h) { return {h->S, h->bits, h->estimator, h->has_table}; }
+static doa::SpectrumPlan plan_of(const doa_music_pipeline *h, const MusicCfg &c)
+{
+    return doa::spectrum_plan(c.estimator, c.has_table, c.S ? c.S : h->N, c.bits, false);
+}
+// the chain's description of the handle as it stands (counts: work_dev_auto)
+static doa::SpectrumDesc desc_of(const doa_music_pipeline *h, const doa::EvdCounts *counts = nullptr)
+{
+    doa::SpectrumDesc d;
+    d.estimator = h->estimator; d.N = h->elements(); d.M = h->music.M; d.bits = h->bits; d.loading = h->loading;
+    if (h->has_table) d.table = &h->array;
+    else d.ula = &h->music;
+    d.counts = counts;
+    return d;
+}
+
+// K1 -> front -> scan (+ peak) -> follow-up for n items on `st` with the workspace `ws`.
 // `spec` == nullptr: nobody wants the spectrum (angles-only call): ws.spec_scratch serves as scratch and the lean
 // scan kernel neither converts the row to dB nor writes it.
 static int run_k1(doa_music_pipeline *h, int n, const void *const *d_in, void *cov, const PipeWs &ws, hipStream_t st)
@@ -57,78 +77,25 @@ static int run_evd_scan(doa_music_pipeline *h, int n, void *cov, void *spec, voi
     if (!spec) spec = ws.spec_scratch;
     const unsigned skip = ~h->stages & 7u;
     int rc = DOA_OK;
-    const bool dbl = (h->bits == 64);
-    void *coef = ws.coef;
-    // spatial smoothing: one launch, part of stage bit 1; the eigen stage reads the smoothed items either way
+    // spatial smoothing: one launch, part of stage bit 1; the front reads the smoothed items either way
     if (!(skip & 2)) rc = h->run_smoothing(n, cov, ws.smooth, st);
     else if (h->S) cov = ws.smooth;
     if (rc != DOA_OK) return rc;
-    const bool capon = (h->estimator == DOA_ESTIMATOR_CAPON);
-    if (capon && !dbl) {
+    if (h->estimator == DOA_ESTIMATOR_CAPON && h->bits != 64) {
         doa::set_error("music_pipeline: the Capon estimator needs internal precision 64 (handle is at %d)", h->bits);
         return DOA_ERR_UNSUPPORTED;
     }
-    if (h->has_table) {
-        // an arbitrary array geometry: the stage in front writes full records, launch_array_scan replaces launch_music_scan,
-        // and the peak pick is a launch of its own on the table's axis -- the launches of the blocks MUSIC_array /
-        // capon_array and find_local_max
-        if (!dbl) {
-            doa::set_error("music_pipeline: a steering table needs internal precision 64 (handle is at %d)", h->bits);
-            return DOA_ERR_UNSUPPORTED;
-        }
-        if (!(skip & 2)) {
-            if (capon)
-                rc = doa::launch_capon_inverse(h->N, n, cov, h->loading, nullptr, nullptr, nullptr, ws.status, st, ws.full);
-            else
-                rc = doa::launch_music_evd_full(h->N, h->music.M, n, cov, ws.full, nullptr, st);
-        }
-        if (rc != DOA_OK) return rc;
-        if (skip & 4) return n;
-        if (h->has_grid) {
-            // grid mode: the scan and find_local_max_2d's pick on the row in LDS are ONE launch, which stores a row only for a
-            // caller that asked for it (a grid too large for LDS is two launches and borrows the scratch rows); argmax holds
-            // M azimuths, then M elevations per item
-            const int M = h->grid.M;
-            void *rows = store_spec ? spec : (h->array.P > doa::kArrayGridFusedMax ? ws.spec_scratch : nullptr);
-            float *am_az = static_cast<float *>(am);
-            rc = doa::launch_array_scan_peaks2d(h->array, h->grid, n, ws.full, rows, mx, am_az, am_az + M, 2 * M, st);
-            // Capon: a status-1 item's NaN record gave a 0.0 dB row and its one peak; the chain of blocks ends with a NaN row
-            // and 3 M NaN for it (the second launch covers the 2 M wide argmax)
-            if (rc == DOA_OK && capon && !(skip & 2))
-                rc = doa::launch_capon_invalid_rows(h->array.P, M, n, ws.status, store_spec ? spec : nullptr, mx, nullptr, st);
-            if (rc == DOA_OK && capon && !(skip & 2))
-                rc = doa::launch_capon_invalid_rows(0, 2 * M, n, ws.status, nullptr, nullptr, am, st);
-            return rc == DOA_OK ? n : rc;
-        }
-        rc = doa::launch_array_scan(h->array, n, ws.full, spec, nullptr, st);
-        if (rc != DOA_OK) return rc;
-        rc = doa::launch_peak_pick(h->peaks, n, spec, nullptr, mx, am, *ws.scratch, (size_t)h->max_batch, ws.scratch_item_off, st);
-        if (rc == DOA_OK && capon && !(skip & 2))
-            rc = doa::launch_capon_invalid_rows(h->peaks.L, h->peaks.M, n, ws.status, store_spec ? spec : nullptr, mx, am, st);
-        return rc == DOA_OK ? n : rc;
+    if (h->has_table && h->bits != 64) {
+        doa::set_error("music_pipeline: a steering table needs internal precision 64 (handle is at %d)", h->bits);
+        return DOA_ERR_UNSUPPORTED;
     }
-    if (!(skip & 2)) {
-        if (capon) {
-            rc = doa::launch_capon_inverse(h->elements(), n, cov, h->loading, coef, ws.cheb, nullptr, ws.status, st);
-        } else {
-            doa::EvdOut out;
-            if (dbl) out.coef_d = (double *)coef;
-            else out.coef = (float *)coef;
-            out.cheb_d = (double *)ws.cheb;
-            rc = doa::launch_music_evd(h->elements(), h->music.M, n, cov, out, h->bits, st);
-        }
-    }
-    if (rc != DOA_OK) return rc;
-    bool peaks_done = false;
-    if (skip & 4) return n;
-    rc = doa::launch_music_scan(h->music, h->bits, n, coef, spec, nullptr, st, &h->peaks, mx, am, &peaks_done, store_spec, ws.cheb);
-    if (rc != DOA_OK) return rc;
-    if (!peaks_done)
-        rc = doa::launch_peak_pick(h->peaks, n, spec, nullptr, mx, am, *ws.scratch, (size_t)h->max_batch, ws.scratch_item_off, st);
-    // Capon: the scan wrote 0.0 dB rows (and the peak pick their peaks) for the NaN records of status-1 items (with the
-    // inverse launch dropped by set_stages there is no status of this call to act on)
-    if (rc == DOA_OK && capon && !(skip & 2))
-        rc = doa::launch_capon_invalid_rows(h->peaks.L, h->peaks.M, n, ws.status, store_spec ? spec : nullptr, mx, am, st);
+    const doa::SpectrumDesc d = desc_of(h);
+    doa::SpectrumPick pick = ws.pick;
+    pick.d_max = mx; pick.d_argmax = am;
+    if (!(skip & 2)) rc = doa::spectrum_front(d, n, cov, ws.rec, nullptr, st);
+    if (rc == DOA_OK && !(skip & 4)) rc = doa::spectrum_scan(d, n, ws.rec, spec, nullptr, store_spec, &pick, st);
+    // (with the front dropped by set_stages there is no status of this call to act on)
+    if (rc == DOA_OK && !(skip & 4) && !(skip & 2)) rc = doa::spectrum_follow_up(d, n, ws.rec, store_spec ? spec : nullptr, &pick, st);
     return rc == DOA_OK ? n : rc;
 }
 static int run_ws(doa_music_pipeline *h, int n, const void *const *d_in, void *cov, void *spec, void *mx, void *am,
@@ -143,40 +110,33 @@ static int run_ws(doa_music_pipeline *h, int n, const void *const *d_in, void *c
 static PipeWs view(doa_music_pipeline *h, doa::PipeLane &ln, size_t item_off)
 {
     using H = doa_music_pipeline;
+    const doa::SpectrumPlan p = plan_of(h, cfg_of(h));
+    auto record = [&](int slot, size_t bytes) { return bytes ? ln.at(slot, item_off, bytes) : nullptr; };
     PipeWs ws;
     ws.cov = ln.at(H::kCov, item_off, (size_t)h->N * h->N * sizeof(float2));
-    ws.coef = ln.at(H::kCoef, item_off, doa::coef_stride(h->N) * (h->bits == 64 ? sizeof(double) : sizeof(float)));
-    ws.cheb = ln.at(H::kCheb, item_off, doa::kChebRecord * sizeof(double));
+    ws.rec = {record(H::kCoef, p.coef), record(H::kCheb, p.cheb), record(H::kFull, p.full), record(H::kStatus, p.status)};
     ws.spec_scratch = ln.at(H::kSpec, item_off, h->peaks.L * sizeof(float));
     ws.work = ln.buf[H::kWork].p;
     ws.smooth = ln.at(H::kSmooth, item_off, (size_t)h->S * h->S * sizeof(float2));
-    ws.status = ln.at(H::kStatus, item_off, sizeof(int));
-    ws.full = ln.at(H::kFull, item_off, doa::full_record_len(h->N) * sizeof(double));
-    ws.scratch = &ln.buf[H::kScratch];
-    ws.scratch_item_off = item_off;
+    ws.pick.peaks = &h->peaks; ws.pick.grid = h->has_grid ? &h->grid : nullptr;
+    ws.pick.scratch = &ln.buf[H::kScratch]; ws.pick.reserve_items = (size_t)h->max_batch; ws.pick.item_off = item_off;
     return ws;
 }
 
-// what sizes a workspace besides the create parameters; a setter passes the configuration it is about to commit, so that a
-// failure leaves the handle as it was
-struct MusicCfg {
-    int S, bits, estimator;
-    bool has_table;
-};
-static MusicCfg cfg_of(const doa_music_pipeline *h) { return {h->S, h->bits, h->estimator, h->has_table}; }
 // Sizes `ln` for configuration `c`: records and covariances of up to G batches (64-128 B per item), spectrum rows of up to
 // G_angles angles-only batches; need_cov / need_spec: some batch brings no covariance / spectrum buffer of its own.  The
-// coefficient records are sized as doubles: the group launches write none, and set_internal_precision must not have to grow them.
+// record slots come from the plan (spectrum_chain.hpp: doubles for the coefficients, G batches of Chebyshev records).
 static int reserve(doa_music_pipeline *h, doa::PipeLane &ln, int G, int G_angles, bool need_cov, bool need_spec, const MusicCfg &c)
 {
     using H = doa_music_pipeline;
     const size_t items = (size_t)h->max_batch;
+    const doa::SpectrumPlan p = plan_of(h, c);
     int rc = h->reserve_front(ln, need_cov ? G : 0, c.S);
-    if (rc == DOA_OK) rc = ln.buf[H::kCoef].reserve(items * doa::coef_stride(h->N) * sizeof(double));
-    if (rc == DOA_OK && doa::music_uses_cheb(c.S ? c.S : h->N, c.bits)) rc = ln.buf[H::kCheb].reserve(G * items * doa::kChebRecord * sizeof(double));
+    if (rc == DOA_OK) rc = ln.buf[H::kCoef].reserve(items * p.coef_slot);
+    if (rc == DOA_OK) rc = ln.buf[H::kCheb].reserve(G * items * p.cheb);
     if (rc == DOA_OK && need_spec) rc = ln.buf[H::kSpec].reserve(G_angles * items * h->peaks.L * sizeof(float));
-    if (rc == DOA_OK && c.estimator == DOA_ESTIMATOR_CAPON) rc = ln.buf[H::kStatus].reserve(items * sizeof(int));
-    if (rc == DOA_OK && c.has_table) rc = ln.buf[H::kFull].reserve(items * doa::full_record_len(h->N) * sizeof(double));
+    if (rc == DOA_OK) rc = ln.buf[H::kStatus].reserve(items * p.status);
+    if (rc == DOA_OK) rc = ln.buf[H::kFull].reserve(items * p.full);
     return rc;
 }
 // the handle's own workspace: one batch, every buffer
@@ -260,15 +220,14 @@ int doa_music_pipeline_set_estimator(doa_music_pipeline_t *h, int estimator, flo
         doa::set_error("music_pipeline_set_estimator: unknown estimator %d (DOA_ESTIMATOR_MUSIC or DOA_ESTIMATOR_CAPON)", estimator);
         return DOA_ERR_INVALID_ARG;
     }
-    if (estimator == DOA_ESTIMATOR_CAPON) {
-        if (!std::isfinite(diagonal_loading) || diagonal_loading < 0.0f) {
-            doa::set_error("music_pipeline_set_estimator: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
-            return DOA_ERR_INVALID_ARG;
-        }
-        if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-        if (int rc = reserve_self(h, {h->S, h->bits, estimator, h->has_table}); rc != DOA_OK) return rc;
-        h->loading = (double)diagonal_loading;
+    const bool capon = (estimator == DOA_ESTIMATOR_CAPON);
+    if (capon && (!std::isfinite(diagonal_loading) || diagonal_loading < 0.0f)) {
+        doa::set_error("music_pipeline_set_estimator: diagonal_loading must be finite and >= 0 (got %g)", (double)diagonal_loading);
+        return DOA_ERR_INVALID_ARG;
     }
+    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    if (int rc = reserve_self(h, {h->S, h->bits, estimator, h->has_table}); rc != DOA_OK) return rc;
+    if (capon) h->loading = (double)diagonal_loading;
     h->estimator = estimator;
     return DOA_OK;
 }
@@ -278,26 +237,18 @@ int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double 
     doa::clear_error();
     if (!h) { doa::set_error("music_pipeline_set_steering_table: bad arguments"); return DOA_ERR_INVALID_ARG; }
     const int N = h->N, P = h->music.P, M = h->peaks.M;
-    if (!steering) {                                     // back to the uniform linear array and its 0 .. 180 axis
-        if (!h->has_table) return DOA_OK;
-        if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-        doa::PeakTables axis;
-        if (int rc = axis.build(M, P, 0.0f, 180.0f); rc != DOA_OK) { axis.release(); return rc; }
-        h->peaks.release();
-        h->peaks = std::move(axis);
-        h->has_table = false;
-        h->has_grid = false; h->grid = doa::Peaks2dTables{};
-        return DOA_OK;
-    }
+    const bool clear = !steering;                        // back to the uniform linear array and its 0 .. 180 axis
+    if (clear && !h->has_table) return DOA_OK;
+    if (clear) { x_min = 0.0f; x_max = 180.0f; }
     if (!std::isfinite(x_min) || !std::isfinite(x_max) || !(x_max > x_min)) {
         doa::set_error("music_pipeline_set_steering_table: need finite x_min < x_max (got %g, %g)", (double)x_min, (double)x_max);
         return DOA_ERR_INVALID_ARG;
     }
-    if (!doa::steering_table_finite(steering, N, P)) {
+    if (!clear && !doa::steering_table_finite(steering, N, P)) {
         doa::set_error("music_pipeline_set_steering_table: the table (%d rows of %d complex doubles) holds a value that is not finite", P, N);
         return DOA_ERR_INVALID_ARG;
     }
-    if (h->S) {
+    if (!clear && h->S) {
         doa::set_error("music_pipeline_set_steering_table: spatial smoothing is on, and it assumes a translation-invariant "
                        "(uniform linear) array");
         return DOA_ERR_UNSUPPORTED;
@@ -306,14 +257,13 @@ int doa_music_pipeline_set_steering_table(doa_music_pipeline_t *h, const double 
     // everything is built aside and swapped in at the end: a failure leaves the handle as it was
     doa::ArrayTable table;
     doa::PeakTables axis;
-    int rc = table.build(N, P, steering);
+    int rc = clear ? DOA_OK : table.build(N, P, steering);
     if (rc == DOA_OK) rc = axis.build(M, P, x_min, x_max);
-    if (rc == DOA_OK) rc = reserve_self(h, {h->S, h->bits, h->estimator, true});
-    if (rc != DOA_OK) { table.release(); axis.release(); return rc; }
-    h->array.release(); h->peaks.release();
+    if (rc == DOA_OK) rc = reserve_self(h, {h->S, h->bits, h->estimator, !clear});
+    if (rc != DOA_OK) return rc;
     h->array = std::move(table); h->peaks = std::move(axis);
-    h->has_table = true;
-    h->has_grid = false; h->grid = doa::Peaks2dTables{};     // a plain table replaces a grid
+    h->has_table = !clear;
+    h->has_grid = false; h->grid = doa::Peaks2dTables{};     // a plain table, or none, replaces a grid
     return DOA_OK;
 }
 
@@ -409,8 +359,6 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const int n = noutput_items;
-    const int elements = h->elements();
-    const bool cheb = doa::music_uses_cheb(elements, 64);
     int rc = reserve_self(h, cfg_of(h));
     if (rc != DOA_OK) return rc;
     const PipeWs ws = view(h, h->self, 0);
@@ -418,19 +366,15 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
     void *spec = d_spectrum_out ? d_spectrum_out : ws.spec_scratch;
     rc = run_k1(h, n, d_input_items, cov, ws, st);
     if (rc == DOA_OK) rc = h->run_smoothing(n, cov, ws.smooth, st);
-    doa::EvdOut out;
-    out.coef_d = (double *)ws.coef;
-    if (cheb) out.cheb_d = (double *)ws.cheb;
     const doa::EvdCounts cnt = doa::evd_counts_estimate((int *)d_count_out, (float *)d_eig_out, h->K, method, h->music.M);
-    if (rc == DOA_OK) rc = doa::launch_music_evd_counts(elements, n, cov, cnt, out, st);
-    if (rc == DOA_OK)
-        rc = doa::launch_music_scan(h->music, 64, n, ws.coef, spec, nullptr, st, nullptr, nullptr, nullptr, nullptr, true,
-                                    cheb ? ws.cheb : nullptr);
+    const doa::SpectrumDesc d = desc_of(h, &cnt);
+    if (rc == DOA_OK) rc = doa::spectrum_front(d, n, cov, ws.rec, nullptr, st);
+    if (rc == DOA_OK) rc = doa::spectrum_scan(d, n, ws.rec, spec, nullptr, true, nullptr, st);
     // a spectrum the caller sees: the row of a count -1 item is NaN, as MUSIC_lin_array_work_dev_counts leaves it (a fifth,
     // one-load-per-item launch; the peak pick below does not read the rows of such items)
-    if (rc == DOA_OK && d_spectrum_out) rc = doa::launch_music_invalid_rows(elements, h->peaks.L, n, d_count_out, spec, st);
+    if (rc == DOA_OK) rc = doa::spectrum_follow_up(d, n, ws.rec, d_spectrum_out, nullptr, st);
     if (rc == DOA_OK)
-        rc = doa::launch_peak_pick(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, *ws.scratch, (size_t)h->max_batch, 0, st);
+        rc = doa::launch_peak_pick(h->peaks, n, spec, d_count_out, d_max_out, d_argmax_out, *ws.pick.scratch, (size_t)h->max_batch, 0, st);
     return rc == DOA_OK ? n : rc;
 }
 
@@ -536,8 +480,8 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         const unsigned skip = ~h->stages & 7u;                   // doa_music_pipeline_set_stages
         int rc = DOA_OK;
         if (!(skip & 1)) rc = doa::launch_autocorrelate_group(N, h->K, h->avg, grp, ln.st, h->has_gain ? h->d_gain.p : nullptr, h->format, h->scale);
-        if (rc == DOA_OK && !(skip & 2)) rc = doa::launch_music_evd_group(N, h->music.M, grp, nullptr, ws.cheb, ln.st);
-        if (rc == DOA_OK && !(skip & 4)) rc = doa::launch_music_scan_group(h->music, h->peaks, grp, ws.cheb, g.store, ln.st);
+        if (rc == DOA_OK && !(skip & 2)) rc = doa::launch_music_evd_group(N, h->music.M, grp, nullptr, ws.rec.cheb, ln.st);
+        if (rc == DOA_OK && !(skip & 4)) rc = doa::launch_music_scan_group(h->music, h->peaks, grp, ws.rec.cheb, g.store, ln.st);
         return rc;
     };
     const int rc = h->run_planned("music_pipeline_work_dev_batches", n_batches, L, hip_stream, traits, prepare, launch);

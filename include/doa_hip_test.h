@@ -131,6 +131,15 @@ DOA_HIP_API int doa_hip_batch_plan_debug(int n_batches, const void *const *outpu
                                          int n_lanes, int rotation_in, int *group_out, int *lane_out, int *sync_first_out,
                                          int *rotation_out);
 
+/* The records a spectrum estimator keeps between its stage in front (eigen stage or Capon inverse) and its scan
+ * (gr-doa_amd/csrc/spectrum_chain.hpp: spectrum_plan), as the four spectrum blocks and music_pipeline size them: no handle, no
+ * device.  estimator: DOA_ESTIMATOR_MUSIC / _CAPON; steering_table: 0 = uniform linear array, 1 = a steering table; bits: the
+ * internal precision; counted: 1 = a source count per item.  bytes_out[0..4], bytes per item, 0 = the record does not exist:
+ * coefficient record, Chebyshev record, full record, status word, and the coefficient SLOT (sized as doubles whatever bits
+ * is).  Returns DOA_OK, DOA_ERR_UNSUPPORTED for a combination no entry runs (bytes_out all 0), or DOA_ERR_INVALID_ARG. */
+DOA_HIP_API int doa_hip_spectrum_plan_debug(int estimator, int steering_table, int num_ant_ele, int bits, int counted,
+                                            long long *bytes_out);
+
 #ifdef __cplusplus
 }
 #endif
