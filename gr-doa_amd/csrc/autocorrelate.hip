@@ -15,10 +15,12 @@
 // Every streaming kernel is templated on a sample loader (Fc32Samples / Sc16Samples): the sc16 form reads complex
 // int16 and widens in registers, with the same lanes, accumulators and summation order as the fc32 form.
 #include "kernels.hpp"
+#include "launch_routes.hpp"
 #include "sample_loaders.hpp"
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace doa {
 
@@ -448,189 +450,167 @@ __global__ void cov_fb_kernel(float2 *out, int nn, long long n_items, float fb_h
     if (e2 != e) p[e2] = nv;
 }
 
-// Waves per CU one launch may occupy (0 = one wave per snapshot, no cap); larger launches grid-stride.  At N = 4,
-// 16 (= one wave per snapshot at the benchmark batch: 4096 snapshots on 256 CUs) measured against 8 with the round-1
-// kernels: -0.6 us on the kernel alone (23.2 vs 23.8 us) and -1.2 us per 4-stream pipeline step (25.6 vs 27.1).
-static int cov_waves_per_cu(int n_ch)
+// The launches of a route (launch_routes.hpp: cov_route).  A = CovArgs (one batch) or CovGroupArgs (a group of batches).
+// Measurements behind the route's numbers:
+//  * waves per CU: at N = 4, 16 (= one wave per snapshot at the benchmark batch: 4096 snapshots on 256 CUs) measured against 8
+//    with the round-1 kernels: -0.6 us on the kernel alone (23.2 vs 23.8 us) and -1.2 us per 4-stream pipeline step (25.6 vs
+//    27.1); wider arrays hold 2-4x the registers per wave and measured better with 8 (N = 6: 54.4 vs 57.3 us, 4-stream step
+//    56.8 vs 63.0 us);
+//  * UN*TN 16-byte loads in flight per wave (UN = 1, 2, 8 measured within 3 % of UN = 4 at N = 4; N = 6: 44 us with UN = 4
+//    against 55 with 2; N = 7: 68 us with 2 against 74 with 1); sc16: UN 8-byte loads, see Sc16Samples;
+//  * the pair loads are a read-once stream: non-temporal loads (+19 % on MI355X against the default cache policy);
+//  * a group is ONE WAVE PER SNAPSHOT, no cap: the single-batch cap (16 waves per CU, which at the benchmark batch is one wave
+//    per snapshot anyway) would turn a group into 4096 waves that stay for the whole launch, and the EVD / scan workgroups of
+//    the neighbouring lane would find no free wave slots until it ends; with one wave per snapshot workgroups retire all the
+//    time.  (Lab builds: DOA_COV_GROUP_WAVES_PER_CU > 0 restores a cap; profiles/grouped_batches.txt.)
+template <class L, int TN, class A> static void launch_cov_tn(const CovRoute &rt, const A &g, hipStream_t st)
 {
-    // N <= 4: one wave per snapshot at the benchmark batch; wider arrays hold 2-4x the registers per wave and measured
-    // better with 8 (N = 6: 54.4 vs 57.3 us, 4-stream step 56.8 vs 63.0 us)
-    const int v = DOA_LAB_ENV_INT("DOA_COV_WAVES_PER_CU", -1);
-    return v >= 0 ? v : (n_ch <= 4 ? 16 : 8);
+    const dim3 grid(rt.main.grid), block(rt.main.block);
+    constexpr int UN = cov_unroll(TN);
+    if constexpr (std::is_same<A, CovArgs>::value) {
+        if (rt.kernel == CovKernel::Pieces) {               // the read-once two-kernel path (see cov_piece_kernel)
+            hipLaunchKernelGGL((cov_piece_kernel<L, TN, UN, true>), grid, block, 0, st, g);
+            hipLaunchKernelGGL(cov_combine_kernel, dim3(rt.second.grid), dim3(rt.second.block), 0, st, g);
+            return;
+        }
+    }
+    if (!rt.vec2) hipLaunchKernelGGL((cov_wave_kernel<L, TN, false, 1, false, A>), grid, block, 0, st, g);
+    else          hipLaunchKernelGGL((cov_wave_kernel<L, TN, true, UN, true, A>), grid, block, 0, st, g);
 }
 
-// the read-once two-kernel path (see cov_piece_kernel)
-template <class L, int TN> static void launch_pieces(const CovArgs &g, hipStream_t st)
+template <class L> static void launch_cov(const CovRoute &rt, const CovArgs &g, hipStream_t st)
 {
-    const int waves_per_block = 4;
-    int blocks = (g.n_steps + waves_per_block - 1) / waves_per_block;
-    if (cov_waves_per_cu(TN) > 0) {
-        const int cap = cu_count() * cov_waves_per_cu(TN) / waves_per_block;
-        if (blocks > cap) blocks = cap;
+    switch (rt.kernel == CovKernel::Mfma ? 0 : rt.TN) {
+    case 1: launch_cov_tn<L, 1>(rt, g, st); break;
+    case 2: launch_cov_tn<L, 2>(rt, g, st); break;
+    case 3: launch_cov_tn<L, 3>(rt, g, st); break;
+    case 4: launch_cov_tn<L, 4>(rt, g, st); break;
+    case 5: launch_cov_tn<L, 5>(rt, g, st); break;
+    case 6: launch_cov_tn<L, 6>(rt, g, st); break;
+    case 7: launch_cov_tn<L, 7>(rt, g, st); break;
+    case 8: launch_cov_tn<L, 8>(rt, g, st); break;
+    default: {
+        const dim3 grid(rt.main.grid), block(rt.main.block);
+        if (rt.vec2) hipLaunchKernelGGL((cov_mfma_kernel<L, true, 4>), grid, block, 0, st, g);
+        else         hipLaunchKernelGGL((cov_mfma_kernel<L, false, 4>), grid, block, 0, st, g);
+        if (rt.second.grid)
+            hipLaunchKernelGGL(cov_fb_kernel, dim3(rt.second.grid), dim3(rt.second.block), 0, st, g.out, g.n_ch * g.n_ch,
+                               (long long)g.n_out, g.fb_hk);
     }
-    constexpr int UN = (TN <= 6) ? 4 : 2;
-    hipLaunchKernelGGL((cov_piece_kernel<L, TN, UN, true>), dim3(blocks), dim3(waves_per_block * kWave), 0, st, g);
-    const long long total = (long long)g.n_out * g.n_ch * g.n_ch;
-    hipLaunchKernelGGL(cov_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g);
+    }
+}
+template <class L> static void launch_cov(const CovRoute &rt, const CovGroupArgs &g, hipStream_t st)
+{
+    switch (rt.TN) {
+    case 2: launch_cov_tn<L, 2>(rt, g, st); break;
+    case 3: launch_cov_tn<L, 3>(rt, g, st); break;
+    default: launch_cov_tn<L, 4>(rt, g, st); break;
+    }
 }
 
-template <class L, int TN> static void launch_wave(const CovArgs &g, bool vec2, hipStream_t st)
+static CovKnobs cov_knobs()
 {
-    if (g.pieces) { launch_pieces<L, TN>(g, st); return; }
-    const int waves_per_block = 4;
-    int blocks = (g.n_out + waves_per_block - 1) / waves_per_block;
-    if (cov_waves_per_cu(TN) > 0) {
-        const int cap = cu_count() * cov_waves_per_cu(TN) / waves_per_block;
-        if (blocks > cap) blocks = cap;
+    return {DOA_LAB_ENV_INT("DOA_COV_WAVES_PER_CU", -1), DOA_LAB_ENV_INT("DOA_COV_MFMA_WAVES_PER_CU", 16),
+            DOA_LAB_ENV_INT("DOA_COV_GROUP_WAVES_PER_CU", 0)};
+}
+
+// every stream of a batch aligned to two samples
+static bool streams_pair_aligned(const void *const *d_in, int N, int format)
+{
+    for (int k = 0; k < N; k++)
+        if (reinterpret_cast<uintptr_t>(d_in[k]) % (2 * sample_bytes(format))) return false;
+    return true;
+}
+// One batch's N streams: every one non-NULL and aligned to one sample, else the error set (batch >= 0: named in it)
+static int check_streams(const void *const *d_in, int N, int format, int batch, bool *pair_aligned)
+{
+    const int sb = (int)sample_bytes(format);
+    for (int k = 0; k < N; k++) {
+        if (!d_in[k]) {
+            if (batch >= 0) set_error("autocorrelate: input stream %d of batch %d is NULL", k, batch);
+            else set_error("autocorrelate: input stream %d is NULL", k);
+            return DOA_ERR_INVALID_ARG;
+        }
+        if (reinterpret_cast<uintptr_t>(d_in[k]) % sb) { set_error("autocorrelate: input stream %d is not %d-byte aligned", k, sb); return DOA_ERR_INVALID_ARG; }
     }
-    dim3 grid(blocks), block(waves_per_block * kWave);
-    // UN*TN 16-byte loads in flight per wave (UN = 1, 2, 8 measured within 3 % of UN = 4 at N = 4; N = 6: 44 us with
-    // UN = 4 against 55 with 2; N = 7: 68 us with 2 against 74 with 1); sc16: UN 8-byte loads, see Sc16Samples
-    constexpr int UN = (TN <= 6) ? 4 : 2;
-    if (!vec2) {
-        hipLaunchKernelGGL((cov_wave_kernel<L, TN, false, 1, false>), grid, block, 0, st, g);
-        return;
-    }
-    // read-once stream: non-temporal loads (+19 % on MI355X against the default cache policy)
-    hipLaunchKernelGGL((cov_wave_kernel<L, TN, true, UN, true>), grid, block, 0, st, g);
+    *pair_aligned = streams_pair_aligned(d_in, N, format);
+    return DOA_OK;
+}
+
+static void fill_cov_args(CovArgs &g, int N, int K, int S, int avg, int n_out, const void *d_gain_outer, int format, float scale)
+{
+    g.n_ch = N; g.K = K; g.S = S; g.n_out = n_out; g.avg = avg;
+    g.inv_k = (float)(1.0 / K);
+    g.fb_hk = (float)(0.5 / K);
+    g.gain = static_cast<const float2 *>(d_gain_outer);
+    g.scale = (format == DOA_SAMPLE_SC16) ? scale : 1.0f;
 }
 
 // Launches K1 on `st`.  d_in: N device pointers.  Returns DOA_OK / error.
-// bytes of piece-sum workspace launch_autocorrelate wants for n_out windows (0: the shape does not
-// take the read-once path)
-size_t autocorrelate_workspace_bytes(int N, int K, int ovl, int n_out)
-{
-    const int S = K - ovl;
-    if (ovl <= 0 || N > 8 || n_out <= 0 || (S & 1) || ((K % S) & 1)) return 0;
-    return (size_t)(n_out + K / S) * 2 * N * N * sizeof(float2);
-}
-
-template <class L> static void launch_routes(const CovArgs &g, bool vec2, hipStream_t st)
-{
-    switch (g.n_ch) {
-    case 1: launch_wave<L, 1>(g, vec2, st); break;
-    case 2: launch_wave<L, 2>(g, vec2, st); break;
-    case 3: launch_wave<L, 3>(g, vec2, st); break;
-    case 4: launch_wave<L, 4>(g, vec2, st); break;
-    case 5: launch_wave<L, 5>(g, vec2, st); break;
-    case 6: launch_wave<L, 6>(g, vec2, st); break;
-    case 7: launch_wave<L, 7>(g, vec2, st); break;
-    case 8: launch_wave<L, 8>(g, vec2, st); break;
-    default: {
-        int blocks = (g.n_out + 3) / 4;
-        const int mfma_wpc = DOA_LAB_ENV_INT("DOA_COV_MFMA_WAVES_PER_CU", 16);
-        if (blocks > cu_count() * mfma_wpc / 4) blocks = cu_count() * mfma_wpc / 4;        // <= 16 waves per CU, grid-stride beyond
-        constexpr int UN = 4;                          // 4 wave-iterations (64 samples) of loads in flight
-        if (vec2) hipLaunchKernelGGL((cov_mfma_kernel<L, true, UN>), dim3(blocks), dim3(256), 0, st, g);
-        else      hipLaunchKernelGGL((cov_mfma_kernel<L, false, UN>), dim3(blocks), dim3(256), 0, st, g);
-        if (g.avg == 1) {
-            const int nn = g.n_ch * g.n_ch, half = (nn + 1) / 2;
-            const long long total = (long long)g.n_out * half;
-            hipLaunchKernelGGL(cov_fb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g.out, nn,
-                               (long long)g.n_out, g.fb_hk);
-        }
-    }
-    }
-}
-
+// The route rule is the same in both formats: every stream aligned to one sample is required, every stream aligned to two
+// samples with S even takes the pair loads (and, with overlap and a workspace, the read-once path)
 int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *const *d_in, void *d_out,
                          hipStream_t st, const void *d_gain_outer, void *d_workspace, int format, float scale)
 {
     if (n_out <= 0) return DOA_OK;
     CovArgs g;
     memset(&g, 0, sizeof g);
-    const bool sc16 = (format == DOA_SAMPLE_SC16);
-    const int sb = sc16 ? 4 : 8;                   // bytes per sample
-    // the route rule is the same in both formats: every stream aligned to one sample is required, every stream aligned to
-    // two samples with S even takes the pair loads (and, with overlap, the read-once path)
-    bool vec2 = ((K - ovl) % 2 == 0);
-    for (int k = 0; k < N; k++) {
-        g.in[k] = d_in[k];
-        if (!d_in[k]) { set_error("autocorrelate: input stream %d is NULL", k); return DOA_ERR_INVALID_ARG; }
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % sb) { set_error("autocorrelate: input stream %d is not %d-byte aligned", k, sb); return DOA_ERR_INVALID_ARG; }
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % (2 * sb)) vec2 = false;
-    }
-    for (int k = N; k < DOA_MAX_ANT_ELE; k++) g.in[k] = g.in[0];
+    CovShape shape;
+    shape.N = N; shape.K = K; shape.ovl = ovl; shape.avg = avg; shape.n_out = n_out; shape.format = format;
+    shape.workspace = (d_workspace != nullptr);
+    if (int rc = check_streams(d_in, N, format, -1, &shape.pair_aligned); rc != DOA_OK) return rc;
+    const CovRoute rt = cov_route(shape, cu_count(), cov_knobs());
+    for (int k = 0; k < DOA_MAX_ANT_ELE; k++) g.in[k] = d_in[k < N ? k : 0];
     g.out = static_cast<float2 *>(d_out);
-    g.n_ch = N; g.K = K; g.S = K - ovl; g.n_out = n_out; g.avg = avg;
-    g.inv_k = (float)(1.0 / K);
-    g.fb_hk = (float)(0.5 / K);
-    g.gain = static_cast<const float2 *>(d_gain_outer);
-    g.scale = sc16 ? scale : 1.0f;
-    if (d_workspace && vec2 && autocorrelate_workspace_bytes(N, K, ovl, n_out) > 0) {
+    fill_cov_args(g, N, K, K - ovl, avg, n_out, d_gain_outer, format, scale);
+    if (rt.kernel == CovKernel::Pieces) {
         g.pieces = static_cast<float2 *>(d_workspace);
-        g.q = K / g.S; g.r = K % g.S; g.n_steps = n_out + g.q;
+        g.q = rt.q; g.r = rt.r; g.n_steps = rt.n_steps;
     }
-    if (sc16) launch_routes<Sc16Samples>(g, vec2, st);
-    else      launch_routes<Fc32Samples>(g, vec2, st);
+    if (format == DOA_SAMPLE_SC16) launch_cov<Sc16Samples>(rt, g, st);
+    else                           launch_cov<Fc32Samples>(rt, g, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
 
 bool autocorrelate_pair_loads(int N, int K, int ovl, const void *const *d_in, int format)
 {
-    const int sb = (format == DOA_SAMPLE_SC16) ? 4 : 8;
-    if ((K - ovl) % 2) return false;
-    for (int k = 0; k < N; k++)
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % (2 * sb)) return false;
-    return true;
-}
-
-// Grid of a multi-batch K1: ONE WAVE PER SNAPSHOT, no cap.  The single-batch cap (cov_waves_per_cu: 16 waves per CU, which at
-// the benchmark batch is one wave per snapshot anyway) would turn a group into 4096 waves that stay for the whole launch, and
-// the EVD / scan workgroups of the neighbouring lane would find no free wave slots until it ends; with one wave per snapshot
-// workgroups retire all the time.  (Lab builds: DOA_COV_GROUP_WAVES_PER_CU > 0 restores a cap; profiles/grouped_batches.txt.)
-template <class L, int TN> static void launch_wave_group(const CovGroupArgs &g, bool vec2, hipStream_t st)
-{
-    const int waves_per_block = 4;
-    int blocks = (g.n_out + waves_per_block - 1) / waves_per_block;
-    if (const int wpc = DOA_LAB_ENV_INT("DOA_COV_GROUP_WAVES_PER_CU", 0); wpc > 0) {
-        const int cap = cu_count() * wpc / waves_per_block;
-        if (blocks > cap) blocks = cap;
-    }
-    dim3 grid(blocks), block(waves_per_block * kWave);
-    constexpr int UN = 4;                       // as launch_wave for N <= 6
-    if (!vec2) hipLaunchKernelGGL((cov_wave_kernel<L, TN, false, 1, false, CovGroupArgs>), grid, block, 0, st, g);
-    else       hipLaunchKernelGGL((cov_wave_kernel<L, TN, true, UN, true, CovGroupArgs>), grid, block, 0, st, g);
-}
-template <class L> static void launch_group_routes(const CovGroupArgs &g, bool vec2, hipStream_t st)
-{
-    switch (g.n_ch) {
-    case 2: launch_wave_group<L, 2>(g, vec2, st); break;
-    case 3: launch_wave_group<L, 3>(g, vec2, st); break;
-    default: launch_wave_group<L, 4>(g, vec2, st); break;
-    }
+    return cov_pair_loads(K, ovl, streams_pair_aligned(d_in, N, format));
 }
 
 int launch_autocorrelate_group(int N, int K, int avg, const BatchGroup &grp, hipStream_t st, const void *d_gain_outer,
                                int format, float scale)
 {
     if (grp.n_batches <= 0 || grp.n <= 0) return DOA_OK;
-    if (N < 2 || N > 4 || grp.n_batches > kMaxGroup) { set_error("autocorrelate: not a group shape (N=%d, %d batches)", N, grp.n_batches); return DOA_ERR_INVALID_ARG; }
+    CovShape shape;
+    shape.N = N; shape.K = K; shape.avg = avg; shape.n_out = grp.n_batches * grp.n; shape.format = format; shape.group = true;
+    // (whether the route takes a group does not depend on the streams: refuse before reading them)
+    if (grp.n_batches > kMaxGroup || cov_route(shape, cu_count(), cov_knobs()).status != DOA_OK) {
+        set_error("autocorrelate: not a group shape (N=%d, %d batches)", N, grp.n_batches);
+        return DOA_ERR_INVALID_ARG;
+    }
+    // a group must be uniform in the load route, because the two routes sum in different orders
+    for (int b = 0; b < grp.n_batches; b++) {
+        bool pair_aligned;
+        if (int rc = check_streams(grp.in[b], N, format, b, &pair_aligned); rc != DOA_OK) return rc;
+        if (b == 0) shape.pair_aligned = pair_aligned;
+        else if (cov_pair_loads(K, 0, pair_aligned) != cov_pair_loads(K, 0, shape.pair_aligned)) {
+            set_error("autocorrelate: a group mixes the two load routes");
+            return DOA_ERR_INVALID_ARG;
+        }
+    }
+    const CovRoute rt = cov_route(shape, cu_count(), cov_knobs());
     CovGroupArgs g;
     memset(static_cast<void *>(&g), 0, sizeof g);
-    const bool sc16 = (format == DOA_SAMPLE_SC16);
-    const int sb = sc16 ? 4 : 8;
-    const bool vec2 = autocorrelate_pair_loads(N, K, 0, grp.in[0], format);
     for (int b = 0; b < kMaxGroup; b++) {
         const int src = b < grp.n_batches ? b : 0;          // unused entries repeat batch 0: never a wild pointer
-        for (int k = 0; k < 4; k++) {
-            const void *p = grp.in[src][k < N ? k : 0];
-            if (!p) { set_error("autocorrelate: input stream %d of batch %d is NULL", k, src); return DOA_ERR_INVALID_ARG; }
-            if (reinterpret_cast<uintptr_t>(p) % sb) { set_error("autocorrelate: input stream %d is not %d-byte aligned", k, sb); return DOA_ERR_INVALID_ARG; }
-            g.gin[b][k] = p;
-        }
-        if (autocorrelate_pair_loads(N, K, 0, grp.in[src], format) != vec2) { set_error("autocorrelate: a group mixes the two load routes"); return DOA_ERR_INVALID_ARG; }
+        for (int k = 0; k < 4; k++) g.gin[b][k] = grp.in[src][k < N ? k : 0];
         g.gout[b] = static_cast<float2 *>(grp.cov[src]);
     }
     g.split = GroupSplit::make(grp.n);
-    g.n_ch = N; g.K = K; g.S = K; g.n_out = grp.n_batches * grp.n; g.avg = avg;
-    g.inv_k = (float)(1.0 / K);
-    g.fb_hk = (float)(0.5 / K);
-    g.gain = static_cast<const float2 *>(d_gain_outer);
-    g.scale = sc16 ? scale : 1.0f;
-    if (sc16) launch_group_routes<Sc16Samples>(g, vec2, st);
-    else      launch_group_routes<Fc32Samples>(g, vec2, st);
+    fill_cov_args(g, N, K, K, avg, shape.n_out, d_gain_outer, format, scale);
+    if (format == DOA_SAMPLE_SC16) launch_cov<Sc16Samples>(rt, g, st);
+    else                           launch_cov<Fc32Samples>(rt, g, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
@@ -760,7 +740,7 @@ int doa_autocorrelate_work_dev(doa_autocorrelate_t *h, int noutput_items, const 
     }
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     // piece-sum workspace of the read-once path (grow-only; growing frees the old buffer, which waits for the device)
-    const size_t ws = doa::autocorrelate_workspace_bytes(h->inputs, h->snapshot, h->overlap, noutput_items);
+    const size_t ws = doa::cov_workspace_bytes(h->inputs, h->snapshot, h->overlap, noutput_items);
     int rc = ws ? h->d_work.reserve(ws) : DOA_OK;
     if (rc != DOA_OK) return rc;
     rc = doa::launch_autocorrelate(h->inputs, h->snapshot, h->overlap, h->avg, noutput_items, d_input_items,
@@ -796,7 +776,7 @@ int doa_autocorrelate_work(doa_autocorrelate_t *h, int noutput_items, const void
         DOA_HIP_TRY(hipMemcpyAsync(dst, input_items[k], span * sb, hipMemcpyHostToDevice, h->stream));
         d_ptrs[k] = dst;
     }
-    const size_t ws = doa::autocorrelate_workspace_bytes(N, h->snapshot, h->overlap, noutput_items);
+    const size_t ws = doa::cov_workspace_bytes(N, h->snapshot, h->overlap, noutput_items);
     if (ws) rc = h->d_work.reserve(ws);
     if (rc != DOA_OK) return rc;
     rc = doa::launch_autocorrelate(N, h->snapshot, h->overlap, h->avg, noutput_items, d_ptrs, h->d_out.p, h->stream,

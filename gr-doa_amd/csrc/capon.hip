@@ -364,7 +364,7 @@ int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, co
     }
     // the diagonal-sum records are what the ULA scans read; a caller that asks for full records may leave them out
     const bool need_records = !out.full;
-    if (!d_R || (need_records && (!out.coef_d || (music_uses_cheb(N, 64) && !out.cheb_d))) || !(loading >= 0.0) || !std::isfinite(loading)) {
+    if (!d_R || (need_records && (!out.coef_d || (scan_reads_cheb(N, 64) && !out.cheb_d))) || !(loading >= 0.0) || !std::isfinite(loading)) {
         set_error("Capon: bad arguments of the inverse launch (N=%d, loading=%g)", N, loading);
         return DOA_ERR_INVALID_ARG;
     }

@@ -1,12 +1,13 @@
 // kernels.hpp — launch entry points shared between the per-block C-ABI files and the pipeline.
 #pragma once
 #include "common.hpp"
+#include "launch_routes.hpp"
 
 namespace doa {
 
 // K1  (autocorrelate.hip)
 // d_gain_outer: optional N*N float2 table w[a + b*N] = g_a conj(g_b) (fused antenna correction), or NULL
-size_t autocorrelate_workspace_bytes(int N, int K, int ovl, int n_out);
+// d_workspace: optional piece sums of the read-once path, cov_workspace_bytes(N, K, ovl, n_out) bytes (launch_routes.hpp)
 // format / scale: DOA_SAMPLE_FC32 (scale unused) or DOA_SAMPLE_SC16 (widened in registers as __fmul_rn((float)q, scale))
 int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *const *d_in, void *d_out,
                          hipStream_t st, const void *d_gain_outer = nullptr, void *d_workspace = nullptr,
@@ -15,7 +16,7 @@ int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *
 int check_input_format(const char *what, int format, float scale);
 inline size_t sample_bytes(int format) { return format == DOA_SAMPLE_SC16 ? 4 : 8; }
 
-// ---- multi-batch ("grouped") launches of the lean route: N <= 4, no overlap, double, P = 256 / 512 / 1024 ----------------
+// ---- multi-batch ("grouped") launches of the lean route: the shapes evd_route and scan_route accept in their group modes -----
 // One K1, one EVD and one scan launch each cover a GROUP of up to kMaxGroup batches of `n` items each: item
 // g = batch * n + local, 0 <= g < n_batches * n.  The kernels get the group's pointers BY VALUE in their arguments (no
 // device-side table); the records between them (coefficients, Chebyshev form) are packed densely by g in one workspace.
@@ -51,11 +52,7 @@ struct GroupSplit {
 bool autocorrelate_pair_loads(int N, int K, int ovl, const void *const *d_in, int format);
 int launch_autocorrelate_group(int N, int K, int avg, const BatchGroup &grp, hipStream_t st, const void *d_gain_outer,
                                int format, float scale);
-// the shapes launch_music_evd_group / launch_music_scan_group take (the one-lane EVD route; the lean scan kernel)
-inline bool music_group_shape_ok(int N, int M, int P, int bits)
-{
-    return N >= 2 && N <= 4 && bits == 64 && !(N == 4 && M == 2) && (P == 256 || P == 512 || P == 1024);
-}
+// the one-lane EVD kernel over a group (evd_route's group mode says which shapes)
 int launch_music_evd_group(int N, int M, const BatchGroup &grp, void *d_coef_d, void *d_cheb, hipStream_t st);
 
 // Host-built tables of MUSIC_lin_array (music.hip): z_i = exp(j*psi_i), psi_i = k_i * d with
@@ -135,7 +132,6 @@ int launch_music_invalid_rows(int N, int P, int n_items, const void *d_counts, v
 // read) -> S x S items, full Hermitian.  fb: 0 forward, 1 forward-backward.  d_Rs must not overlap d_R (not checked).
 // 16-byte loads and stores when both pointers are 16-byte aligned, 8-byte ones otherwise: the same bits either way.
 int launch_spatial_smooth(int N, int S, int fb, int n_items, const void *d_R, void *d_Rs, hipStream_t st);
-inline bool music_uses_cheb(int N, int bits) { return N <= 4 && bits == 64; }
 constexpr int kChebRecord = 8;      // doubles per item
 // Q(psi) = u0 + 2 sum_l (x_l cos(l psi) - y_l sin(l psi)), u_l = x_l + j y_l, in powers of c = cos psi and s = sin psi
 // (cos 2x = 2c^2 - 1, cos 3x = 4c^3 - 3c, sin 2x = 2sc, sin 3x = s(4c^2 - 1)):  Q = A(c) + s B(c),
@@ -217,7 +213,7 @@ int launch_music_scan(const MusicTables &t, int bits, int n_items, const void *d
                       hipStream_t st, const PeakTables *peaks = nullptr, void *d_max = nullptr,
                       void *d_argmax = nullptr, bool *peaks_done = nullptr, bool store_spectrum = true,
                       const void *d_cheb = nullptr);
-// the lean scan + peak pick over a group (music_group_shape_ok shapes, peaks->L == t.P, every grp.spec 16-byte aligned);
+// the lean scan + peak pick over a group (scan_route's group mode says which shapes; peaks->L == t.P, every grp.spec 16-byte aligned);
 // d_cheb: the group's records, dense by g.  store_spectrum = false: grp.spec are scratch rows (angles only)
 int launch_music_scan_group(const MusicTables &t, const PeakTables &peaks, const BatchGroup &grp, const void *d_cheb,
                             bool store_spectrum, hipStream_t st);

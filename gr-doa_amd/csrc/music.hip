@@ -61,6 +61,12 @@ int MusicTables::build(float norm_spacing_, int num_targets, int num_ant_ele, in
 DOA_SCAN_SIZES(DOA_SCAN_EXTERN)
 DOA_SCAN_GROUP_EXTERN(2) DOA_SCAN_GROUP_EXTERN(3) DOA_SCAN_GROUP_EXTERN(4)
 
+static ScanKnobs scan_knobs()
+{
+    return {DOA_LAB_ENV_INT("DOA_SCAN_WPB", kRouteWavesPerBlock), DOA_LAB_ENV_INT("DOA_SCAN_LEAN_WAVES_PER_CU", 0),
+            DOA_LAB_ENV_INT("DOA_SCAN_NOTRIM", 0), DOA_LAB_ENV_INT("DOA_SCAN_WAVES_PER_CU", 8)};
+}
+
 int launch_music_scan(const MusicTables &t, int bits, int n_items, const void *d_coef, void *d_spec, void *d_q,
                       hipStream_t st, const PeakTables *peaks, void *d_max, void *d_argmax, bool *peaks_done,
                       bool store_spectrum, const void *d_cheb)
@@ -73,22 +79,18 @@ int launch_music_scan(const MusicTables &t, int bits, int n_items, const void *d
         pk.xaxis = peaks->d_x.as<float>(); pk.val = (float *)d_max; pk.loc = (float *)d_argmax; pk.M = peaks->M;
         pk.store = store_spectrum;
     }
-    bool done = false;
-    // compiled polynomial sizes: 2, 3, 4, 6, 8, 12, 16 (an array of n elements uses the next size up
-    // with zero high-order coefficients)
-    const int n = t.N;
-    if (n < 2 || n > DOA_MAX_ANT_ELE) {
-        set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", n, DOA_MAX_ANT_ELE);
-        return DOA_ERR_UNSUPPORTED;
+    ScanShape s;
+    s.n_ant = t.N; s.bits = bits == 32 ? 32 : 64; s.P = t.P; s.n_items = n_items;
+    s.spec_aligned = reinterpret_cast<uintptr_t>(d_spec) % 16 == 0; s.q = (d_q != nullptr);
+    s.pick = (pk.val != nullptr); s.M = pk.M; s.store = pk.store; s.cheb = (pk.cheb != nullptr);
+    const ScanRoute rt = scan_route(s, cu_count(), scan_knobs());
+    if (rt.status != DOA_OK) { set_error("%s", rt.why); return rt.status; }
+    switch (rt.N) {
+#define DOA_SCAN_CASE(n) case n: launch_scan_n<n>(rt, t, bits, n_items, d_coef, d_spec, d_q, pk, st); break;
+    DOA_SCAN_SIZES(DOA_SCAN_CASE)
+#undef DOA_SCAN_CASE
     }
-    if (n == 2) done = launch_scan_n<2>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
-    else if (n == 3) done = launch_scan_n<3>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
-    else if (n == 4) done = launch_scan_n<4>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
-    else if (n <= 6) done = launch_scan_n<6>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
-    else if (n <= 8) done = launch_scan_n<8>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
-    else if (n <= 12) done = launch_scan_n<12>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
-    else done = launch_scan_n<16>(t, bits, n_items, d_coef, d_spec, d_q, pk, st);
-    if (peaks_done) *peaks_done = done;
+    if (peaks_done) *peaks_done = rt.picked;
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }
@@ -97,15 +99,24 @@ int launch_music_scan_group(const MusicTables &t, const PeakTables &peaks, const
                             bool store_spectrum, hipStream_t st)
 {
     if (grp.n_batches <= 0 || grp.n <= 0) return DOA_OK;
-    bool ok = music_group_shape_ok(t.N, peaks.M, t.P, 64) && peaks.L == t.P && d_cheb && grp.n_batches <= kMaxGroup;
-    for (int b = 0; b < grp.n_batches && ok; b++)
-        ok = grp.spec[b] && reinterpret_cast<uintptr_t>(grp.spec[b]) % 16 == 0 && grp.mx[b] && grp.am[b];
-    if (!ok) { set_error("MUSIC: not a group the lean scan kernel takes (N=%d, P=%d, %d batches)", t.N, t.P, grp.n_batches); return DOA_ERR_INVALID_ARG; }
+    bool ok = peaks.L == t.P && grp.n_batches <= kMaxGroup;
+    ScanShape s;
+    s.n_ant = t.N; s.P = t.P; s.n_items = grp.n_batches * grp.n; s.M = peaks.M; s.store = store_spectrum;
+    s.cheb = (d_cheb != nullptr); s.group = true; s.spec_aligned = true;
+    for (int b = 0; b < grp.n_batches && ok; b++) {
+        ok = grp.spec[b] && grp.mx[b] && grp.am[b];
+        if (reinterpret_cast<uintptr_t>(grp.spec[b]) % 16) s.spec_aligned = false;
+    }
+    const ScanRoute rt = scan_route(s, cu_count(), scan_knobs());
+    if (!ok || rt.status != DOA_OK) {
+        set_error("MUSIC: not a group the lean scan kernel takes (N=%d, P=%d, %d batches)", t.N, t.P, grp.n_batches);
+        return DOA_ERR_INVALID_ARG;
+    }
     ScanPeakArgs pk;
     pk.cheb = d_cheb; pk.xaxis = peaks.d_x.as<float>(); pk.M = peaks.M; pk.store = store_spectrum;
-    if (t.N == 2) launch_scan_group_n<2>(t, grp, pk, st);
-    else if (t.N == 3) launch_scan_group_n<3>(t, grp, pk, st);
-    else launch_scan_group_n<4>(t, grp, pk, st);
+    if (rt.N == 2) launch_scan_group_n<2>(rt, t, grp, pk, st);
+    else if (rt.N == 3) launch_scan_group_n<3>(rt, t, grp, pk, st);
+    else launch_scan_group_n<4>(rt, t, grp, pk, st);
     DOA_HIP_TRY(hipGetLastError());
     return DOA_OK;
 }

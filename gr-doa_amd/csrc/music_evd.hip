@@ -11,6 +11,7 @@
 // Output: one 2N-value coefficient record per item ([u0, Re u1, Im u1, ...]); P_N itself on request.
 #include "jacobi.hpp"
 #include "evd_subspace.hpp"
+#include "launch_routes.hpp"
 #include <mutex>
 #include <type_traits>
 
@@ -1139,13 +1140,6 @@ __global__ __launch_bounds__(64) void music_evd_subspace_kernel(const float2 *__
     evd_block16_item<double, !PN>(Ri, item, N, MC, out, sVr, sVi, sLam);      // (LEAN unless P_N is wanted)
 }
 
-template <int G, int MC>
-static void launch_evd_subspace_gm(int N, int n_items, const float2 *R, const EvdOut &out, hipStream_t st,
-                                   unsigned long long *d_fallback_count)
-{
-    hipLaunchKernelGGL((out.pn_out ? music_evd_subspace_kernel<G, MC, true> : music_evd_subspace_kernel<G, MC, false>), dim3(n_items),
-                       dim3(64), 0, st, R, out.coef, out.coef_d, out.pn_out, n_items, N, d_fallback_count);
-}
 // Diagnostics: items of subspace-kernel launches that took the Jacobi fall-back.  ONE COUNTER PER DEVICE, allocated on first use
 // with that device current (the launchers run with the handle's device bound: bind_device): a kernel only ever adds into
 // memory of the device it runs on.  (Until round 3 there was one counter per process on whichever device came first; a handle
@@ -1203,154 +1197,6 @@ long long evd_fallback_count(bool reset)
     return total;
 }
 
-// 4 < N <= 16, 1 <= M <= 4, 2 M <= N (the iteration pays when the signal subspace is the small one)
-static bool launch_evd_subspace(int N, int M, int n_items, const float2 *R, const EvdOut &out, hipStream_t st,
-                                unsigned long long *d_fallback_count)
-{
-    if (N <= 4 || N > 16 || M < 1 || M > 4 || 2 * M > N) return false;
-#define DOA_SUB(G_, M_) launch_evd_subspace_gm<G_, M_>(N, n_items, R, out, st, d_fallback_count)
-    if (N <= 8) { if (M == 1) DOA_SUB(8, 1); else if (M == 2) DOA_SUB(8, 2); else if (M == 3) DOA_SUB(8, 3); else DOA_SUB(8, 4); }
-    else { if (M == 1) DOA_SUB(16, 1); else if (M == 2) DOA_SUB(16, 2); else if (M == 3) DOA_SUB(16, 3); else DOA_SUB(16, 4); }
-#undef DOA_SUB
-    return true;
-}
-
-static int evd_check_size(int N)
-{
-    if (N >= 2 && N <= DOA_MAX_ANT_ELE) return DOA_OK;
-    set_error("MUSIC: num_ant_ele=%d outside the built range 2..%d", N, DOA_MAX_ANT_ELE);
-    return DOA_ERR_UNSUPPORTED;
-}
-
-// The Jacobi form of an array size, and its grid: one wave per item above 8 elements (G = 16), else 8 lanes per item above 4,
-// else 4 lanes per item.  launch(G as an integral_constant, grid) launches that form's kernel.
-template <class Launch> static void evd_jacobi_form(int N, int n_items, Launch &&launch)
-{
-    if (N > 8) launch(std::integral_constant<int, 16>{}, dim3(n_items));
-    else if (N > 4) launch(std::integral_constant<int, 8>{}, dim3((n_items + 7) / 8));
-    else launch(std::integral_constant<int, 4>{}, dim3((n_items + 15) / 16));
-}
-
-// music_evd_block16_kernel / music_evd_group_kernel; out: coef, coef_d, pn_out, or pilot and cal_out (calibrate mode)
-template <typename T> static void launch_evd_jacobi(int N, int M, int n_items, const float2 *R, const EvdOut &out, hipStream_t st)
-{
-    evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
-        constexpr int G = decltype(g)::value;
-        if constexpr (G < 16)
-            hipLaunchKernelGGL((music_evd_group_kernel<G, T>), grid, dim3(64), 0, st, R, out.coef, out.coef_d, out.pn_out, n_items, N,
-                               M, out.pilot, out.cal_out);
-        else {
-            const bool lean = !out.pn_out && !out.cal_out;
-            hipLaunchKernelGGL((lean ? music_evd_block16_kernel<T, true> : music_evd_block16_kernel<T, false>), grid, dim3(64), 0, st,
-                               R, out.coef, out.coef_d, out.pn_out, n_items, N, M, out.pilot, out.cal_out);
-        }
-    });
-}
-
-// calibrate_lin_array: top eigenvector of each covariance item, de-rotated by the pilot steering vector
-int launch_calibrate(int N, int n_items, const void *d_R, const void *d_pilot, void *d_out, int bits, hipStream_t st)
-{
-    if (n_items <= 0) return DOA_OK;
-    EvdOut out;
-    out.pilot = (const float2 *)d_pilot;
-    out.cal_out = (float2 *)d_out;
-    if (bits == 32) launch_evd_jacobi<float>(N, 1, n_items, (const float2 *)d_R, out, st);
-    else launch_evd_jacobi<double>(N, 1, n_items, (const float2 *)d_R, out, st);
-    DOA_HIP_TRY(hipGetLastError());
-    return DOA_OK;
-}
-
-// N <= 4, two or three sources, double: four lanes per item (music_evd_quad_kernel)
-static bool launch_evd_quad(int N, int M, int n_items, const float2 *R, const EvdOut &out, hipStream_t st)
-{
-    // two sources only: with three (N = 4: ONE noise eigenvalue) 1.6 % of random-direction items fall back and take their
-    // waves with them -- 26 against the Jacobi's 11 us per 4096 items (profiles/r04_lab_evd_quad.txt)
-    // and four antennas only: at N = 3 the one-lane Jacobi is the faster one by far (5.4 against 14.7 us per 4096 random-direction
-    // items: a 3 x 3 sweep is three rotations, and the quad spends a lane on padding; profiles/r04_lab_evd_noise_vector.txt)
-    if (N != 4 || M != 2) return false;
-    hipLaunchKernelGGL((out.pn_out ? music_evd_quad_kernel<2, true> : music_evd_quad_kernel<2, false>), dim3((n_items + 15) / 16),
-                       dim3(64), 0, st, R, out.coef, out.coef_d, out.pn_out, n_items, N, out.cheb_d, evd_fallback_counter());
-    return true;
-}
-
-template <int N> static void launch_evd_n(int M, int n_items, const float2 *R, const EvdOut &out, int bits, hipStream_t st)
-{
-    dim3 block(64), grid((n_items + 63) / 64);
-    const bool f32 = (bits == 32);                       // float: no Chebyshev record, and no subspace iteration to count
-    hipLaunchKernelGGL((f32 ? music_evd_kernel<N, float> : music_evd_kernel<N, double>), grid, block, 0, st, EvdOne{R}, out.coef,
-                       out.coef_d, out.pn_out, n_items, M, f32 ? nullptr : out.cheb_d, f32 ? nullptr : evd_fallback_counter());
-}
-
-// the one-lane kernel over a group of batches (music_group_shape_ok shapes: double, and not the quad kernel's N = 4, M = 2)
-template <int N> static void launch_evd_group_n(int M, int n_items, const EvdGroup &src, void *d_coef_d, void *d_cheb, hipStream_t st)
-{
-    dim3 block(64), grid((n_items + 63) / 64);
-    hipLaunchKernelGGL((music_evd_kernel<N, double, EvdGroup>), grid, block, 0, st, src, (float *)nullptr, (double *)d_coef_d,
-                       (float2 *)nullptr, n_items, M, (double *)d_cheb, evd_fallback_counter());
-}
-
-int launch_music_evd_group(int N, int M, const BatchGroup &grp, void *d_coef_d, void *d_cheb, hipStream_t st)
-{
-    if (grp.n_batches <= 0 || grp.n <= 0) return DOA_OK;
-    if (N < 2 || N > 4 || (N == 4 && M == 2) || grp.n_batches > kMaxGroup) {
-        set_error("MUSIC: not a group shape (N=%d, M=%d, %d batches)", N, M, grp.n_batches);
-        return DOA_ERR_INVALID_ARG;
-    }
-    EvdGroup src;
-    for (int b = 0; b < kMaxGroup; b++) src.cov[b] = static_cast<const float2 *>(grp.cov[b < grp.n_batches ? b : 0]);
-    src.split = GroupSplit::make(grp.n);
-    const int n_items = grp.n_batches * grp.n;
-    switch (N) {
-    case 2: launch_evd_group_n<2>(M, n_items, src, d_coef_d, d_cheb, st); break;
-    case 3: launch_evd_group_n<3>(M, n_items, src, d_coef_d, d_cheb, st); break;
-    default: launch_evd_group_n<4>(M, n_items, src, d_coef_d, d_cheb, st); break;
-    }
-    DOA_HIP_TRY(hipGetLastError());
-    return DOA_OK;
-}
-
-template <int N> static void launch_evd_counts_n(int n_items, const float2 *R, const EvdCounts &cnt, const EvdOut &out, hipStream_t st)
-{
-    dim3 block(64), grid((n_items + 63) / 64);
-    hipLaunchKernelGGL((music_evd_kernel<N, double, EvdOneCounts>), grid, block, 0, st, EvdOneCounts{R, cnt}, (float *)nullptr,
-                       out.coef_d, (float2 *)nullptr, n_items, 0, out.cheb_d, (unsigned long long *)nullptr);
-}
-
-int launch_music_evd_counts(int N, int n_items, const void *d_R, const EvdCounts &cnt, const EvdOut &out, hipStream_t st)
-{
-    if (n_items <= 0) return DOA_OK;
-    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
-    if (!cnt.counts_in && (!cnt.count_out || cnt.K < 2 || cnt.kmax < 0 || cnt.kmax > N - 1 ||
-                           (cnt.method != DOA_SOURCE_COUNT_MDL && cnt.method != DOA_SOURCE_COUNT_AIC))) {
-        set_error("source count: bad arguments (K=%d, method=%d, kmax=%d, N=%d)", cnt.K, cnt.method, cnt.kmax, N);
-        return DOA_ERR_INVALID_ARG;
-    }
-    const float2 *R = (const float2 *)d_R;
-    // always the Jacobi forms (the subspace iterations never form the noise eigenvalues)
-    if (N <= 4 && !out.es_rec) {
-        switch (N) {
-        case 2: launch_evd_counts_n<2>(n_items, R, cnt, out, st); break;
-        case 3: launch_evd_counts_n<3>(n_items, R, cnt, out, st); break;
-        default: launch_evd_counts_n<4>(n_items, R, cnt, out, st); break;
-        }
-    } else {
-        // N <= 4: the record needs the eigenvectors by rows: four lanes per item (no Chebyshev record from this form's count mode)
-        if (N <= 4 && out.cheb_d) {
-            set_error("MUSIC: the signal-subspace record and the Chebyshev record do not come from one launch");
-            return DOA_ERR_INVALID_ARG;
-        }
-        evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
-            constexpr int G = decltype(g)::value;
-            if constexpr (G < 16)
-                hipLaunchKernelGGL((music_evd_group_counts_kernel<G>), grid, dim3(64), 0, st, R, out.coef_d, n_items, N, cnt, out.es_rec);
-            else
-                hipLaunchKernelGGL(music_evd_block16_counts_kernel, grid, dim3(64), 0, st, R, out.coef_d, n_items, N, cnt, out.es_rec);
-        });
-    }
-    DOA_HIP_TRY(hipGetLastError());
-    return DOA_OK;
-}
-
 // The Jacobi forms writing P_N itself as a full record (kernels.hpp) for the steering-table scan: the row-per-lane epilogue
 // holds P_N in double where it writes the float2 diagnostics, and the record is stored from those values.  No diagonal sums.
 template <int G>
@@ -1396,77 +1242,176 @@ __global__ __launch_bounds__(64) void music_evd_block16_record_kernel(const floa
     evd_block16_item<double, true>(R + (size_t)item * (N * N), item, N, 1, out, sVr, sVi, sLam);
 }
 
+// ---- the launches of a route (launch_routes.hpp: evd_route) ---------------------------------------------------------------
+// Measurements behind the route: N <= 4: one lane per item, everything in registers (10.5 us vs 11.0 us for the 4-lane group
+// kernel at batch 4096: at this size the cross-lane traffic eats the shorter dependency chain); N > 4: 8 lanes per item
+// (N <= 8) or one wave per item (block Jacobi), 15x / 17x faster than one lane per item with the matrices in scratch.  The quad
+// kernel takes two sources only: with three (N = 4: ONE noise eigenvalue) 1.6 % of random-direction items fall back and take
+// their waves with them -- 26 against the Jacobi's 11 us per 4096 items (profiles/r04_lab_evd_quad.txt); and four antennas
+// only: at N = 3 the one-lane Jacobi is the faster one by far (5.4 against 14.7 us per 4096 random-direction items: a 3 x 3
+// sweep is three rotations, and the quad spends a lane on padding; profiles/r04_lab_evd_noise_vector.txt).
+// (the order of the branches below is the order in which the kernels stand in the code object)
+template <typename T>
+static void launch_evd_jacobi(const EvdRoute &rt, dim3 grid, dim3 block, hipStream_t st, const float2 *R, const EvdOut &out, int n, int N, int M)
+{
+    if (rt.G == 16)
+        hipLaunchKernelGGL((rt.LEAN ? music_evd_block16_kernel<T, true> : music_evd_block16_kernel<T, false>), grid, block, 0, st, R,
+                           out.coef, out.coef_d, out.pn_out, n, N, M, out.pilot, out.cal_out);
+#define DOA_GROUP(G_) hipLaunchKernelGGL((music_evd_group_kernel<G_, T>), grid, block, 0, st, R, out.coef, out.coef_d, out.pn_out, n, N, M, out.pilot, out.cal_out)
+    else if (rt.G == 8) DOA_GROUP(8);
+    else DOA_GROUP(4);
+#undef DOA_GROUP
+}
+// the one-lane kernel of a group of batches or with a count per item (double)
+template <class Src>
+static void launch_evd_one_lane(int N, dim3 grid, dim3 block, hipStream_t st, const Src &src, const EvdOut &out, int n, int M,
+                                unsigned long long *fallback_count)
+{
+#define DOA_ONE(N_) hipLaunchKernelGGL((music_evd_kernel<N_, double, Src>), grid, block, 0, st, src, (float *)nullptr, out.coef_d, (float2 *)nullptr, n, M, out.cheb_d, fallback_count)
+    switch (N) {
+    case 2: DOA_ONE(2); break;
+    case 3: DOA_ONE(3); break;
+    default: DOA_ONE(4); break;
+    }
+#undef DOA_ONE
+}
+
+// `out` holds the outputs of the mode and no others; cnt: the Counts mode; grp: the Group mode (R unused)
+static int launch_evd(const EvdShape &s, const float2 *R, const EvdOut &out, hipStream_t st, const EvdCounts *cnt = nullptr,
+                      const EvdGroup *grp = nullptr)
+{
+    const EvdRoute rt = evd_route(s);
+    if (rt.status != DOA_OK) { set_error("%s", rt.why); return rt.status; }
+    const dim3 grid(rt.dim.grid), block(rt.dim.block);
+    const int n = s.n_items, N = s.N, M = s.M;
+    const bool f32 = (s.bits == 32), jacobi = (rt.kernel == EvdKernel::Jacobi || rt.kernel == EvdKernel::Block16);
+    unsigned long long *fallback_count = rt.counts_fallbacks ? evd_fallback_counter() : nullptr;
+    if (rt.kernel == EvdKernel::Subspace) {
+#define DOA_SUB(G_, M_) hipLaunchKernelGGL((rt.PN ? music_evd_subspace_kernel<G_, M_, true> : music_evd_subspace_kernel<G_, M_, false>), \
+                                           grid, block, 0, st, R, out.coef, out.coef_d, out.pn_out, n, N, fallback_count)
+        if (rt.G == 8) { if (M == 1) DOA_SUB(8, 1); else if (M == 2) DOA_SUB(8, 2); else if (M == 3) DOA_SUB(8, 3); else DOA_SUB(8, 4); }
+        else { if (M == 1) DOA_SUB(16, 1); else if (M == 2) DOA_SUB(16, 2); else if (M == 3) DOA_SUB(16, 3); else DOA_SUB(16, 4); }
+#undef DOA_SUB
+    } else if (jacobi && (s.mode == EvdMode::Fixed || s.mode == EvdMode::Calibrate)) {
+        if (f32) launch_evd_jacobi<float>(rt, grid, block, st, R, out, n, N, M);
+        else launch_evd_jacobi<double>(rt, grid, block, st, R, out, n, N, M);
+    } else if (rt.kernel == EvdKernel::Quad) {
+        hipLaunchKernelGGL((rt.PN ? music_evd_quad_kernel<2, true> : music_evd_quad_kernel<2, false>), grid, block, 0, st, R, out.coef,
+                           out.coef_d, out.pn_out, n, N, out.cheb_d, fallback_count);
+    } else if (s.mode == EvdMode::Group) {
+        launch_evd_one_lane(N, grid, block, st, *grp, out, n, M, fallback_count);
+    } else if (rt.kernel == EvdKernel::OneLane && s.mode == EvdMode::Counts) {
+        launch_evd_one_lane(N, grid, block, st, EvdOneCounts{R, *cnt}, out, n, 0, fallback_count);
+    } else if (jacobi) {
+        // the Jacobi forms of the other modes (double): a count per item, the signal-subspace record only, the full record
+#define DOA_JACOBI(name, ...)                                                                                      \
+    do {                                                                                                           \
+        if (rt.G == 16) hipLaunchKernelGGL(music_evd_block16_##name##_kernel, grid, block, 0, st, __VA_ARGS__);    \
+        else if (rt.G == 8) hipLaunchKernelGGL((music_evd_group_##name##_kernel<8>), grid, block, 0, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL((music_evd_group_##name##_kernel<4>), grid, block, 0, st, __VA_ARGS__);            \
+    } while (0)
+        if (s.mode == EvdMode::Counts) DOA_JACOBI(counts, R, out.coef_d, n, N, *cnt, out.es_rec);
+        else if (s.mode == EvdMode::Record) DOA_JACOBI(record, R, out.es_rec, n, N);
+        else DOA_JACOBI(full, R, out.pn_d, out.pn_out, n, N, M);
+#undef DOA_JACOBI
+    } else {
+#define DOA_ONE(N_) hipLaunchKernelGGL((f32 ? music_evd_kernel<N_, float> : music_evd_kernel<N_, double>), grid, block, 0, st, EvdOne{R}, out.coef, out.coef_d, out.pn_out, n, M, out.cheb_d, fallback_count)
+        switch (N) {
+        case 2: DOA_ONE(2); break;
+        case 3: DOA_ONE(3); break;
+        default: DOA_ONE(4); break;
+        }
+#undef DOA_ONE
+    }
+    DOA_HIP_TRY(hipGetLastError());
+    return DOA_OK;
+}
+
+// the argument checks of the entries below come after the size check, which is the route's
+static bool evd_size_ok(int N) { return N >= 2 && N <= DOA_MAX_ANT_ELE; }
+
+static EvdShape evd_shape(EvdMode mode, int N, int M, int bits, int n_items)
+{
+    EvdShape s;
+    s.mode = mode; s.N = N; s.M = M; s.bits = bits; s.n_items = n_items;
+    return s;
+}
+
+// calibrate_lin_array: top eigenvector of each covariance item, de-rotated by the pilot steering vector
+int launch_calibrate(int N, int n_items, const void *d_R, const void *d_pilot, void *d_out, int bits, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    EvdOut out;
+    out.pilot = (const float2 *)d_pilot;
+    out.cal_out = (float2 *)d_out;
+    return launch_evd(evd_shape(EvdMode::Calibrate, N, 1, bits == 32 ? 32 : 64, n_items), (const float2 *)d_R, out, st);
+}
+
+int launch_music_evd_group(int N, int M, const BatchGroup &grp, void *d_coef_d, void *d_cheb, hipStream_t st)
+{
+    if (grp.n_batches <= 0 || grp.n <= 0) return DOA_OK;
+    const EvdShape s = evd_shape(EvdMode::Group, N, M, 64, grp.n_batches * grp.n);
+    if (grp.n_batches > kMaxGroup || evd_route(s).status != DOA_OK) {
+        set_error("MUSIC: not a group shape (N=%d, M=%d, %d batches)", N, M, grp.n_batches);
+        return DOA_ERR_INVALID_ARG;
+    }
+    EvdGroup src;
+    for (int b = 0; b < kMaxGroup; b++) src.cov[b] = static_cast<const float2 *>(grp.cov[b < grp.n_batches ? b : 0]);
+    src.split = GroupSplit::make(grp.n);
+    EvdOut out;
+    out.coef_d = (double *)d_coef_d; out.cheb_d = (double *)d_cheb;
+    return launch_evd(s, nullptr, out, st, nullptr, &src);
+}
+
+int launch_music_evd_counts(int N, int n_items, const void *d_R, const EvdCounts &cnt, const EvdOut &out, hipStream_t st)
+{
+    if (n_items <= 0) return DOA_OK;
+    if (evd_size_ok(N) && !cnt.counts_in && (!cnt.count_out || cnt.K < 2 || cnt.kmax < 0 || cnt.kmax > N - 1 ||
+                                              (cnt.method != DOA_SOURCE_COUNT_MDL && cnt.method != DOA_SOURCE_COUNT_AIC))) {
+        set_error("source count: bad arguments (K=%d, method=%d, kmax=%d, N=%d)", cnt.K, cnt.method, cnt.kmax, N);
+        return DOA_ERR_INVALID_ARG;
+    }
+    EvdShape s = evd_shape(EvdMode::Counts, N, 0, 64, n_items);
+    s.cheb = (out.cheb_d != nullptr); s.es_rec = (out.es_rec != nullptr);
+    EvdOut o;
+    o.coef_d = out.coef_d; o.cheb_d = out.cheb_d; o.es_rec = out.es_rec;
+    return launch_evd(s, (const float2 *)d_R, o, st, &cnt);
+}
+
 int launch_music_evd_record(int N, int n_items, const void *d_R, void *d_rec, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
-    if (!d_R || !d_rec) {
+    if (evd_size_ok(N) && (!d_R || !d_rec)) {
         set_error("MUSIC: bad arguments of the record eigen launch (N=%d)", N);
         return DOA_ERR_INVALID_ARG;
     }
-    evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
-        constexpr int G = decltype(g)::value;
-        if constexpr (G < 16)
-            hipLaunchKernelGGL((music_evd_group_record_kernel<G>), grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_rec, n_items, N);
-        else
-            hipLaunchKernelGGL(music_evd_block16_record_kernel, grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_rec, n_items, N);
-    });
-    DOA_HIP_TRY(hipGetLastError());
-    return DOA_OK;
+    EvdOut out;
+    out.es_rec = (double *)d_rec;
+    return launch_evd(evd_shape(EvdMode::Record, N, 1, 64, n_items), (const float2 *)d_R, out, st);
 }
 
 int launch_music_evd_full(int N, int M, int n_items, const void *d_R, void *d_full, void *d_pn, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
-    if (!d_R || !d_full || M < 1 || M >= N) {
+    if (evd_size_ok(N) && (!d_R || !d_full || M < 1 || M >= N)) {
         set_error("MUSIC: bad arguments of the full-record eigen launch (N=%d, M=%d)", N, M);
         return DOA_ERR_INVALID_ARG;
     }
-    evd_jacobi_form(N, n_items, [&](auto g, dim3 grid) {
-        constexpr int G = decltype(g)::value;
-        if constexpr (G < 16)
-            hipLaunchKernelGGL((music_evd_group_full_kernel<G>), grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_full,
-                               (float2 *)d_pn, n_items, N, M);
-        else
-            hipLaunchKernelGGL(music_evd_block16_full_kernel, grid, dim3(64), 0, st, (const float2 *)d_R, (double *)d_full,
-                               (float2 *)d_pn, n_items, N, M);
-    });
-    DOA_HIP_TRY(hipGetLastError());
-    return DOA_OK;
+    EvdOut out;
+    out.pn_d = (double *)d_full; out.pn_out = (float2 *)d_pn;
+    return launch_evd(evd_shape(EvdMode::Full, N, M, 64, n_items), (const float2 *)d_R, out, st);
 }
 
 int launch_music_evd(int N, int M, int n_items, const void *d_R, const EvdOut &out, int evd_bits, hipStream_t st)
 {
     if (n_items <= 0) return DOA_OK;
-    if (int rc = evd_check_size(N); rc != DOA_OK) return rc;
-    const float2 *R = (const float2 *)d_R;
-    // N <= 4: one lane per item, everything in registers (measured 10.5 us vs 11.0 us for the
-    // 4-lane group kernel at batch 4096: at this size the cross-lane traffic eats the shorter
-    // dependency chain).  N > 4: 8 lanes per item (N <= 8) or one wave per item (block Jacobi), 15x / 17x faster than
-    // one lane per item with the matrices in scratch.
-    const bool f32 = (evd_bits == 32);
-    // wide arrays, few sources, double: signal-subspace iteration with the block Jacobi as its per-item fall-back
-    if (!f32 && launch_evd_subspace(N, M, n_items, R, out, st, evd_fallback_counter())) {
-        DOA_HIP_TRY(hipGetLastError());
-        return DOA_OK;
-    }
-    if (N > 4) {
-        EvdOut jac;                                     // (no pilot, no cal_out: not the calibrate mode)
-        jac.coef = out.coef; jac.coef_d = out.coef_d; jac.pn_out = out.pn_out;
-        if (f32) launch_evd_jacobi<float>(N, M, n_items, R, jac, st);
-        else launch_evd_jacobi<double>(N, M, n_items, R, jac, st);
-    } else if (!f32 && DOA_LAB_ENV_INT("DOA_EVD_QUAD", 1) && launch_evd_quad(N, M, n_items, R, out, st)) {
-        // (N <= 4 with M >= 2 in double; M = 1 keeps the one-lane iteration below)
-    } else {
-        switch (N) {
-        case 2: launch_evd_n<2>(M, n_items, R, out, evd_bits, st); break;
-        case 3: launch_evd_n<3>(M, n_items, R, out, evd_bits, st); break;
-        default: launch_evd_n<4>(M, n_items, R, out, evd_bits, st); break;
-        }
-    }
-    DOA_HIP_TRY(hipGetLastError());
-    return DOA_OK;
+    EvdShape s = evd_shape(EvdMode::Fixed, N, M, evd_bits == 32 ? 32 : 64, n_items);
+    s.pn_out = (out.pn_out != nullptr);
+    s.quad = DOA_LAB_ENV_INT("DOA_EVD_QUAD", 1) != 0;
+    EvdOut o;                                           // (no pilot, no cal_out: not the calibrate mode; float: no Chebyshev record)
+    o.coef = out.coef; o.coef_d = out.coef_d; o.pn_out = out.pn_out;
+    if (s.bits == 64) o.cheb_d = out.cheb_d;
+    return launch_evd(s, (const float2 *)d_R, o, st);
 }
 
 }  // namespace doa

@@ -839,16 +839,16 @@ __global__ __launch_bounds__(256) void music_scan_generic_kernel(const T *__rest
 }
 
 
+// ---- the launches of a route (launch_routes.hpp: scan_route) whose compiled polynomial size is N --------------------------
+// the fast kernel's three variants: diagnostics (Q out), fused with the peak pick, plain
 template <int N, int CH, typename T, bool ZREG = true>
-static void launch_scan_fast(dim3 grid, dim3 block, hipStream_t st, const T *co, const T *z, float *sp, float *q, int P,
-                             int n_items, const ScanPeakArgs &pk, int n_ant)
+static void launch_scan_fast(const ScanRoute &rt, dim3 grid, dim3 block, hipStream_t st, const T *co, const T *z, float *sp, float *q,
+                             int P, int n_items, const ScanPeakArgs &pk, int n_ant)
 {
-    // three variants: diagnostics (Q out), plain, fused with the peak pick; spectra are write-once ->
-    // non-temporal stores in the two production variants
-    if (q)
+    if (rt.HAS_Q)
         hipLaunchKernelGGL((music_scan_kernel<N, CH, T, true, false, false, ZREG>), grid, block, 0, st, co, z, sp, q, P,
                            n_items, nullptr, nullptr, nullptr, 0, n_ant);
-    else if (pk.val)
+    else if (rt.PEAKS)
         hipLaunchKernelGGL((music_scan_kernel<N, CH, T, false, true, true, ZREG>), grid, block, 0, st, co, z, sp, q, P,
                            n_items, pk.xaxis, pk.val, pk.loc, pk.M, n_ant);
     else
@@ -857,48 +857,31 @@ static void launch_scan_fast(dim3 grid, dim3 block, hipStream_t st, const T *co,
 }
 
 // The lean benchmark-shape kernel (music_scan_peak1_kernel) for n_items items whose outputs `out` describes: one batch
-// (ScanOne) or a group of batches (ScanGroup, n_items = the group's total) -- the same grid rule for both.
+// (ScanOne) or a group of batches (ScanGroup, n_items = the group's total) -- the same grid rule for both.  Measurements behind
+// the grid: 12 waves per CU up to a few items per wave (the benchmark batch: 2048 waves with two items each; one item per wave
+// makes every wave pay the 16 KiB table load for 4 KiB of output), 16 -- all the 104-VGPR kernel can hold -- beyond: at large
+// batches the kernel sits between its two ablations (rows stored without arithmetic, arithmetic without stores: DESIGN.md
+// section 3) and a fourth wave per SIMD is worth 225-229 against 232-240 us per 262144 items.
 template <int N, typename T, class Out>
-static void launch_scan_lean(const T *rec, const T *z, int P, int n_items, const Out &out, bool peaks, const ScanPeakArgs &pk,
+static void launch_scan_lean(const ScanRoute &rt, const T *rec, const T *z, int n_items, const Out &out, const ScanPeakArgs &pk,
                              hipStream_t st)
 {
-    const int waves_per_block = 4;
-    // lab: workgroup size in waves, 1..4 (the kernels are bounded to 256 threads and their per-wave LDS rows to four)
-    const int lwpb_env = DOA_LAB_ENV_INT("DOA_SCAN_WPB", waves_per_block);
-    const int lwpb = lwpb_env < 1 ? 1 : (lwpb_env > 4 ? 4 : lwpb_env);
-    const dim3 lblock(lwpb * kWave);
-    int lb = (n_items + lwpb - 1) / lwpb;
-    // Waves per CU: 12 up to a few items per wave (the benchmark batch: 2048 waves with two items each; one item per wave
-    // makes every wave pay the 16 KiB table load for 4 KiB of output), 16 -- all the 104-VGPR kernel can hold -- beyond:
-    // at large batches the kernel sits between its two ablations (rows stored without arithmetic, arithmetic without
-    // stores: DESIGN.md section 3) and a fourth wave per SIMD is worth 225-229 against 232-240 us per 262144 items.
-    const int per_wave16 = n_items / (cu_count() * 16);
-    const int lwpc_env = DOA_LAB_ENV_INT("DOA_SCAN_LEAN_WAVES_PER_CU", 0);
-    const int lwpc = lwpc_env > 0 ? lwpc_env : (per_wave16 >= 4 ? 16 : 12);
-    const int cap = cu_count() * lwpc / lwpb;
-    if (lb > cap && !DOA_LAB_ENV_INT("DOA_SCAN_NOTRIM", 0)) {
-        // every wave takes the same number of items (4096 items on a cap of 3072 waves would be one round of 3072 and a
-        // second of 1024 with two thirds of the chip idle: 2048 waves with two items each instead)
-        const int cap_waves = cap * lwpb;
-        const int per_wave = (n_items + cap_waves - 1) / cap_waves;
-        const int waves = (n_items + per_wave - 1) / per_wave;
-        lb = (waves + lwpb - 1) / lwpb;
-    } else if (lb > cap) lb = cap;
-    dim3 lgrid(lb);
+    static_assert(LeanRecord<N, T>::kPre == scan_reads_cheb(N, 8 * (int)sizeof(T)), "the route and the kernel agree on the record's form");
+    const dim3 lgrid(rt.dim.grid), lblock(rt.dim.block);
 #define DOA_LEAN_LAUNCH(CH_, MULTI_, PEAKS_, STORE_)                                                               \
     hipLaunchKernelGGL((music_scan_peak1_kernel<N, CH_, T, MULTI_, PEAKS_, STORE_, 0, Out>), lgrid, lblock, 0, st, rec, z,  \
                        out, n_items, pk.xaxis, pk.M)
 #define DOA_LEAN_CH(MULTI_, PEAKS_, STORE_)                                                                        \
     do {                                                                                                           \
-        if (P == 256) DOA_LEAN_LAUNCH(1, MULTI_, PEAKS_, STORE_);                                                  \
-        else if (P == 512) DOA_LEAN_LAUNCH(2, MULTI_, PEAKS_, STORE_);                                             \
+        if (rt.CH == 1) DOA_LEAN_LAUNCH(1, MULTI_, PEAKS_, STORE_);                                                \
+        else if (rt.CH == 2) DOA_LEAN_LAUNCH(2, MULTI_, PEAKS_, STORE_);                                           \
         else DOA_LEAN_LAUNCH(4, MULTI_, PEAKS_, STORE_);                                                           \
     } while (0)
 #ifdef DOA_LAB
     if constexpr (N == 4 && sizeof(T) == 8 && std::is_same<Out, ScanOne>::value) {
         // ablations of the graded kernel (results invalid): DOA_SCAN_ABLATE=1 no row stores, =2 row stores only
         const int ablate = DOA_LAB_ENV_INT("DOA_SCAN_ABLATE", 0);
-        if (ablate && P == 1024 && pk.val && pk.store && pk.M == 1) {
+        if (ablate && rt.CH == 4 && pk.val && pk.store && pk.M == 1) {
             if (ablate == 1)
                 hipLaunchKernelGGL((music_scan_peak1_kernel<4, 4, T, false, true, true, 1>), lgrid, lblock, 0, st, rec, z, out, n_items,
                                    pk.xaxis, pk.M);
@@ -909,96 +892,75 @@ static void launch_scan_lean(const T *rec, const T *z, int P, int n_items, const
         }
     }
 #endif
-    if (!peaks) {
+    if (!rt.PEAKS) {
         if constexpr (std::is_same<Out, ScanOne>::value) DOA_LEAN_CH(false, false, true);   // (groups always pick peaks)
-    } else if (!pk.store) {                                   // angles only (sp is scratch for irregular rows)
-        if (pk.M == 1) DOA_LEAN_CH(false, true, false);
+    } else if (!rt.STORE) {                                   // angles only (sp is scratch for irregular rows)
+        if (!rt.MULTI) DOA_LEAN_CH(false, true, false);
         else DOA_LEAN_CH(true, true, false);
     }
-    else if (pk.M == 1) DOA_LEAN_CH(false, true, true);
+    else if (!rt.MULTI) DOA_LEAN_CH(false, true, true);
     else DOA_LEAN_CH(true, true, true);
 #undef DOA_LEAN_CH
 #undef DOA_LEAN_LAUNCH
 }
 
-// returns true when the fused peak pick ran (fast path only)
 template <int N, typename T>
-static bool launch_scan_nt(const T *co, const T *z, int P, int n_items, void *d_spec, void *d_q, const ScanPeakArgs &pk,
-                           int n_ant, hipStream_t st)
+static void launch_scan_nt(const ScanRoute &rt, const T *co, const T *z, int P, int n_items, void *d_spec, void *d_q,
+                           const ScanPeakArgs &pk, int n_ant, hipStream_t st)
 {
     float *sp = (float *)d_spec, *q = (float *)d_q;
-    const int waves_per_block = 4;
-    const bool aligned = (P % 4 == 0) && (reinterpret_cast<uintptr_t>(d_spec) % 16 == 0);
-    // two items per wave at the benchmark batch: the z table is loaded once per wave and the next
-    // item's coefficient record is prefetched behind the current item's arithmetic
-    int blocks = (n_items + waves_per_block - 1) / waves_per_block;
-    const int wpc = DOA_LAB_ENV_INT("DOA_SCAN_WAVES_PER_CU", 8);
-    const int max_blocks = cu_count() * wpc / waves_per_block;
-    if (blocks > max_blocks) blocks = max_blocks;
-    dim3 grid(blocks), block(waves_per_block * kWave);
-    // the lean benchmark-shape kernel (see music_scan_peak1_kernel); also without a peak pick -- the stand-alone
-    // MUSIC_lin_array block -- so that block and pipeline produce the same spectrum bit for bit: same kernel, same
-    // arithmetic.  For N <= 4 in double it reads the pre-transformed records (pk.cheb), which the caller must supply.
-    constexpr bool kPre = LeanRecord<N, T>::kPre;
-    if (aligned && !q && n_ant == N && (P == 256 || P == 512 || P == 1024) && (!kPre || pk.cheb)) {
-        const T *rec = kPre ? static_cast<const T *>(pk.cheb) : co;
-        launch_scan_lean<N, T>(rec, z, P, n_items, ScanOne{sp, pk.val, pk.loc}, pk.val != nullptr, pk, st);
-        return pk.val != nullptr;
-    }
-    // long spectra without diagnostics: P > 2048 in double.  peak_pick<16> on a register-resident row makes the fused fast
-    // kernel a 511-VGPR, one-wave-per-SIMD kernel (135 us per 4096 items at N = 16); instead:
-    if (aligned && P > 2048 && sizeof(T) == 8 && !q) {
-        // with the peak pick wanted (the pipeline) and P a multiple of 64 up to 4096: scan + K5 in one launch, the row staged in
-        // LDS and written once (the two-launch form it replaced moved the row through HBM four times)
-        // (also without the peak pick -- the stand-alone MUSIC_lin_array block: same kernel, same bits, 56 against the 62 us
-        // per 4096 items of the two-pass kernel below that parks Q in the output row)
-        if ((!pk.val || pk.M >= 1) && P % 64 == 0 && P <= 4096) {
-            const int M_pick = pk.val ? pk.M : 0;
-            int fb = (n_items + waves_per_block - 1) / waves_per_block;
-            if (fb > cu_count() * 2) fb = cu_count() * 2;                 // 64 KiB of LDS per workgroup: two per CU
+    const dim3 grid(rt.dim.grid), block(rt.dim.block);
+    switch (rt.kernel) {
+    case ScanKernel::Lean:
+        launch_scan_lean<N, T>(rt, rt.reads_cheb ? static_cast<const T *>(pk.cheb) : co, z, n_items, ScanOne{sp, pk.val, pk.loc}, pk, st);
+        break;
+    case ScanKernel::Long:
+        // peak_pick<16> on a register-resident row makes the fused fast kernel a 511-VGPR, one-wave-per-SIMD kernel (135 us per
+        // 4096 items at N = 16); this one stages the row in LDS and writes it once (the two-launch form it replaced moved the row
+        // through HBM four times).  Also without the peak pick -- the stand-alone MUSIC_lin_array block: same kernel, same bits,
+        // 56 against the 62 us per 4096 items of the two-pass kernel below that parks Q in the output row.
+        // (the route takes it and the stream kernel in double only; both are compiled for float as well)
+        {
 #ifdef DOA_LAB
             if constexpr (N == 16) {
                 const int abl = DOA_LAB_ENV_INT("DOA_SCAN_LONG_ABLATE", 0);
-#define DOA_LONG_ABL(A_) if (abl == A_) { hipLaunchKernelGGL((music_scan_peak_long_kernel<N, T, A_>), dim3(fb), block, 0, st, co, z, sp, P, n_items, n_ant, pk.xaxis, pk.val, pk.loc, M_pick); return pk.val != nullptr; }
+#define DOA_LONG_ABL(A_) if (abl == A_) { hipLaunchKernelGGL((music_scan_peak_long_kernel<N, T, A_>), grid, block, 0, st, co, z, sp, P, n_items, n_ant, pk.xaxis, pk.val, pk.loc, rt.M_pick); return; }
                 DOA_LONG_ABL(1) DOA_LONG_ABL(2) DOA_LONG_ABL(4) DOA_LONG_ABL(6) DOA_LONG_ABL(7) DOA_LONG_ABL(3) DOA_LONG_ABL(5)
 #undef DOA_LONG_ABL
             }
 #endif
-            hipLaunchKernelGGL((music_scan_peak_long_kernel<N, T>), dim3(fb), block, 0, st, co, z, sp, P, n_items, n_ant,
-                               pk.xaxis, pk.val, pk.loc, M_pick);
-            return pk.val != nullptr;
+            hipLaunchKernelGGL((music_scan_peak_long_kernel<N, T>), grid, block, 0, st, co, z, sp, P, n_items, n_ant, pk.xaxis, pk.val,
+                               pk.loc, rt.M_pick);
         }
-        // lengths the fused kernel does not take: the rolled two-pass kernel; the peak pick, if any, is left to the caller
-        // (returns false)
-        int sb = (n_items + waves_per_block - 1) / waves_per_block;
-        if (sb > cu_count() * 16 / waves_per_block) sb = cu_count() * 16 / waves_per_block;
-        hipLaunchKernelGGL((music_scan_stream_kernel<N, T>), dim3(sb), block, 0, st, co, z, sp, P, n_items, n_ant);
-        return false;
-    }
-    if (aligned && P <= 4096) {
+        break;
+    case ScanKernel::Stream:
+        hipLaunchKernelGGL((music_scan_stream_kernel<N, T>), grid, block, 0, st, co, z, sp, P, n_items, n_ant);
+        break;
+    case ScanKernel::Fast: {
         constexpr bool ZBIG = (sizeof(T) == 4);          // float tables fit the register file up to P = 4096
-        if (P <= 256) launch_scan_fast<N, 1, T>(grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
-        else if (P <= 512) launch_scan_fast<N, 2, T>(grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
-        else if (P <= 1024) launch_scan_fast<N, 4, T>(grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
-        else if (P <= 2048) launch_scan_fast<N, 8, T, ZBIG>(grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
-        else launch_scan_fast<N, 16, T, ZBIG>(grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
-        return pk.val != nullptr && q == nullptr;
+        if (rt.CH == 1) launch_scan_fast<N, 1, T>(rt, grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
+        else if (rt.CH == 2) launch_scan_fast<N, 2, T>(rt, grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
+        else if (rt.CH == 4) launch_scan_fast<N, 4, T>(rt, grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
+        else if (rt.CH == 8) launch_scan_fast<N, 8, T, ZBIG>(rt, grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
+        else launch_scan_fast<N, 16, T, ZBIG>(rt, grid, block, st, co, z, sp, q, P, n_items, pk, n_ant);
+        break;
     }
-    hipLaunchKernelGGL((music_scan_generic_kernel<N, T>), grid, block, 0, st, co, z, sp, q, P, n_items, n_ant);
-    return false;
+    case ScanKernel::Generic:
+        hipLaunchKernelGGL((music_scan_generic_kernel<N, T>), grid, block, 0, st, co, z, sp, q, P, n_items, n_ant);
+        break;
+    }
 }
 
-template <int N> bool launch_scan_n(const MusicTables &t, int bits, int n_items, const void *d_coef, void *d_spec,
-                                           void *d_q, const ScanPeakArgs &pk, hipStream_t st)
+template <int N> void launch_scan_n(const ScanRoute &rt, const MusicTables &t, int bits, int n_items, const void *d_coef,
+                                    void *d_spec, void *d_q, const ScanPeakArgs &pk, hipStream_t st)
 {
-    if (bits == 32)
-        return launch_scan_nt<N, float>((const float *)d_coef, t.d_z.as<float>(), t.P, n_items, d_spec, d_q, pk, t.N, st);
-    return launch_scan_nt<N, double>((const double *)d_coef, t.d_zd.as<double>(), t.P, n_items, d_spec, d_q, pk, t.N, st);
+    if (bits == 32) launch_scan_nt<N, float>(rt, (const float *)d_coef, t.d_z.as<float>(), t.P, n_items, d_spec, d_q, pk, t.N, st);
+    else launch_scan_nt<N, double>(rt, (const double *)d_coef, t.d_zd.as<double>(), t.P, n_items, d_spec, d_q, pk, t.N, st);
 }
 
-template <int N> void launch_scan_group_n(const MusicTables &t, const BatchGroup &grp, const ScanPeakArgs &pk, hipStream_t st)
+template <int N> void launch_scan_group_n(const ScanRoute &rt, const MusicTables &t, const BatchGroup &grp, const ScanPeakArgs &pk,
+                                          hipStream_t st)
 {
-    static_assert(LeanRecord<N, double>::kPre, "groups read the Chebyshev-form records");
     ScanGroup out;
     for (int b = 0; b < kMaxGroup; b++) {
         const int src = b < grp.n_batches ? b : 0;          // unused entries repeat batch 0: never a wild pointer
@@ -1007,7 +969,7 @@ template <int N> void launch_scan_group_n(const MusicTables &t, const BatchGroup
         out.loc[b] = static_cast<float *>(grp.am[src]);
     }
     out.split = GroupSplit::make(grp.n);
-    launch_scan_lean<N, double>(static_cast<const double *>(pk.cheb), t.d_zd.as<double>(), t.P, grp.n_batches * grp.n, out, true, pk, st);
+    launch_scan_lean<N, double>(rt, static_cast<const double *>(pk.cheb), t.d_zd.as<double>(), grp.n_batches * grp.n, out, pk, st);
 }
 
 }  // namespace doa

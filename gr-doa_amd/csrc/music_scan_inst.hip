@@ -7,9 +7,10 @@
 #endif
 
 namespace doa {
-template bool launch_scan_n<DOA_SCAN_N>(const MusicTables &, int, int, const void *, void *, void *, const ScanPeakArgs &,
-                                        hipStream_t);
+template void launch_scan_n<DOA_SCAN_N>(const ScanRoute &, const MusicTables &, int, int, const void *, void *, void *,
+                                        const ScanPeakArgs &, hipStream_t);
 #if DOA_SCAN_N <= 4
-template void launch_scan_group_n<DOA_SCAN_N>(const MusicTables &, const BatchGroup &, const ScanPeakArgs &, hipStream_t);
+template void launch_scan_group_n<DOA_SCAN_N>(const ScanRoute &, const MusicTables &, const BatchGroup &, const ScanPeakArgs &,
+                                              hipStream_t);
 #endif
 }  // namespace doa

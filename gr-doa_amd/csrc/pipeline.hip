@@ -436,7 +436,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
     const int N = h->N, n = noutput_items, P = h->peaks.L;
 
     // ---- the plan (batch_plan.hpp): what makes a batch lean, and its group cap ----
-    const bool lean_shape = h->estimator == DOA_ESTIMATOR_MUSIC && !h->has_table && h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::music_group_shape_ok(N, h->music.M, P, h->bits) &&
+    const bool lean_shape = h->estimator == DOA_ESTIMATOR_MUSIC && !h->has_table && h->S == 0 && h->ovl == 0 && h->peaks.L == h->music.P && doa::group_routes_accept(N, h->music.M, P, h->bits) &&
                             (long long)doa::kMaxGroup * n <= (1 << 28);
     const int L_all = h->lanes.n_lanes;
     const int L = (lean_shape && group_lanes() < L_all) ? group_lanes() : L_all;

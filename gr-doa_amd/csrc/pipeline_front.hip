@@ -26,7 +26,7 @@ int PipeFront::open(int dev, int inputs, int snapshot_size, int overlap_size, in
 int PipeFront::reserve_front(PipeLane &ln, int cov_batches, int S_)
 {
     int rc = ln.buf[kCov].reserve((size_t)cov_batches * max_batch * N * N * sizeof(float2));
-    if (const size_t ws = autocorrelate_workspace_bytes(N, K, ovl, max_batch); ws && rc == DOA_OK) rc = ln.buf[kWork].reserve(ws);
+    if (const size_t ws = cov_workspace_bytes(N, K, ovl, max_batch); ws && rc == DOA_OK) rc = ln.buf[kWork].reserve(ws);
     if (rc == DOA_OK && S_) rc = ln.buf[kSmooth].reserve((size_t)max_batch * S_ * S_ * sizeof(float2));
     return rc;
 }
@@ -188,7 +188,7 @@ int PipeFront::host_run(const char *who, int n_items, const void *const *input_i
     int rc = d_res.reserve(res_bytes);
     for (auto &b : d_in)
         if (rc == DOA_OK) rc = b.reserve(stride * N);
-    if (const size_t ws = autocorrelate_workspace_bytes(N, K, ovl, (int)chunk); ws && rc == DOA_OK)
+    if (const size_t ws = cov_workspace_bytes(N, K, ovl, (int)chunk); ws && rc == DOA_OK)
         rc = d_work1.reserve(ws);                      // lane 0 uses the workspace create() sized for max_batch
     if (rc != DOA_OK) return rc;
     int lane = 0, chunk_index = 0;

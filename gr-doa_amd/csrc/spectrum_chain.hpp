@@ -42,7 +42,7 @@ inline SpectrumPlan spectrum_plan(int estimator, bool table, int N, int bits, bo
     else {
         p.coef = coef_stride(N) * (bits == 64 ? sizeof(double) : sizeof(float));
         p.coef_slot = coef_stride(N) * sizeof(double);
-        if (music_uses_cheb(N, bits)) p.cheb = kChebRecord * sizeof(double);
+        if (scan_reads_cheb(N, bits)) p.cheb = kChebRecord * sizeof(double);
     }
     if (capon) p.status = sizeof(int);
     return p;

@@ -140,6 +140,23 @@ DOA_HIP_API int doa_hip_batch_plan_debug(int n_batches, const void *const *outpu
 DOA_HIP_API int doa_hip_spectrum_plan_debug(int estimator, int steering_table, int num_ant_ele, int bits, int counted,
                                             long long *bytes_out);
 
+/* Which kernels a shape launches, and with which grids (gr-doa_amd/csrc/launch_routes.hpp: cov_route, evd_route, scan_route): no
+ * handle, no device; cu_count is the device's compute-unit count as the launchers would pass it.  stage 0 = K1 (covariance), 1 =
+ * K2+K3 (eigen stage), 2 = K4 (scan of a uniform linear array).  shape, n_shape values, 0 / 1 where a flag:
+ *   stage 0 (9):  inputs, snapshot_size, overlap_size, avg_method, noutput_items, sample format, every stream aligned to two
+ *                 samples, a piece-sum workspace was supplied, a group of batches (noutput_items = the group's total)
+ *   stage 1 (8):  num_ant_ele, num_targets, internal precision, items, mode (0 fixed source count, 1 a count per item, 2 the
+ *                 signal-subspace record only, 3 the full record, 4 calibrate, 5 a group of batches), projector wanted (mode
+ *                 0), Chebyshev record wanted (mode 1), signal-subspace record wanted (mode 1)
+ *   stage 2 (11): num_ant_ele, internal precision, pspectrum_len, items, spectrum pointer 16-byte aligned, null spectrum wanted,
+ *                 fused peak pick wanted, its num_max_vals, spectrum stored, Chebyshev record supplied, a group of batches
+ * text_out (text_cap bytes): one line per launch in launch order, "kernel<template,arguments> grid block lanes work strides":
+ * the kernel's name without namespace or blanks, workgroups, threads per workgroup, lanes per work item, work items of the
+ * launch, 1 if the kernel strides over them by its grid; then one "key value" line per further fact of the route
+ * (workspace_bytes; counts_fallbacks; reads_cheb, picked).  Returns the number of launches; a shape the route refuses returns
+ * the launcher's status with its error text set; DOA_ERR_INVALID_ARG for bad arguments of this entry. */
+DOA_HIP_API int doa_hip_launch_route_debug(int stage, const int *shape, int n_shape, int cu_count, char *text_out, int text_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,18 @@ def test_shapes_on_and_off_the_lean_route(shape):
         _check(shape, 70, K_MAX_GROUP + 3, lanes, form, max_batch=80)
 
 
+@pytest.mark.parametrize("lanes,form", [(1, "attached"), (4, "detached")])
+def test_odd_snapshot_size_groups_batches_of_either_alignment(lanes, form):
+    """K = 63, n = 17: batches cut one after the other from one buffer lie 1071 samples apart, so every second one is aligned to
+    one sample only.  With an odd step K1 takes the single loads whatever the alignment: nothing mixes, the batches share
+    their groups' launches, and every batch equals its own work_dev call bit for bit."""
+    shape, n, nb = dict(LEAN, K=63), 17, 5
+    whole = _inputs(shape, nb * n, seed=7)
+    ins = [[t[b * n * 63:(b + 1) * n * 63] for t in whole] for b in range(nb)]
+    assert {x[0].data_ptr() % 16 for x in ins} == {0, 8}
+    _check(shape, n, nb, lanes, form, ins=ins)
+
+
 def test_unaligned_spectrum_pointer_inside_a_call():
     """a batch whose spectrum pointer is not 16-byte aligned leaves the lean route on its own; its neighbours stay grouped"""
     nb = 10
