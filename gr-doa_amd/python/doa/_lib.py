@@ -203,6 +203,16 @@ SIGNATURES = {
     "doa_esprit_linear_array_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "doa_root_pipeline_set_estimator": (C.c_int, [_vp, C.c_int]),
     "doa_pipeline_set_steering_grid": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "doa_channel_covariance_create": (_vp, [C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "doa_channel_covariance_destroy": (None, [_vp]),
+    "doa_channel_covariance_history": (C.c_int, [_vp]),
+    "doa_channel_covariance_forecast": (C.c_int, [_vp, C.c_int]),
+    "doa_channel_covariance_input_span": (C.c_longlong, [_vp, C.c_int]),
+    "doa_channel_covariance_set_input_format": (C.c_int, [_vp, C.c_int, C.c_float]),
+    "doa_channel_covariance_set_bins": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "doa_channel_covariance_num_bins": (C.c_int, [_vp]),
+    "doa_channel_covariance_work": (C.c_int, [_vp, C.c_int, _vpp, _vp, _vp]),
+    "doa_channel_covariance_work_dev": (C.c_int, [_vp, C.c_int, _vpp, _vp, _vp, _vp]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

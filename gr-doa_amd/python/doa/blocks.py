@@ -227,6 +227,88 @@ class autocorrelate_sc16(autocorrelate):
         self.in_sig = [(_I16, 2)] * self.inputs
 
 
+def _periodic_window(name, fft_len) -> np.ndarray:
+    """The named windows of channel_covariance: periodic forms, computed in double and rounded to float32."""
+    t = 2.0 * np.pi * np.arange(fft_len, dtype=np.float64) / fft_len
+    forms = {"rect": lambda: np.ones(fft_len), "hann": lambda: 0.5 - 0.5 * np.cos(t),
+             "hamming": lambda: 0.54 - 0.46 * np.cos(t),
+             "blackman": lambda: 0.42 - 0.5 * np.cos(t) + 0.08 * np.cos(2.0 * t)}
+    if name not in forms:
+        raise ValueError(f"unknown window {name!r} (rect, hann, hamming, blackman or an array of fft_len values)")
+    return forms[name]().astype(_F32)
+
+
+class channel_covariance(_StreamInput, _Block):
+    """doa.channel_covariance(inputs, snapshot_size, overlap_size, fft_len, window="hann") — one covariance per snapshot and
+    frequency bin (the Welch / Bartlett cross-spectral matrix; include/doa_hip.h has the definition): each snapshot is cut
+    into snapshot_size / fft_len blocks, every block windowed and Fourier-transformed, and the products averaged over the
+    blocks.  Item i * num_bins() + j is the column-major inputs x inputs matrix of bin (first_bin + j) mod fft_len of
+    snapshot i, an ordinary covariance item for every block behind it.  Not a block of the reference.
+    window: "rect", "hann", "hamming", "blackman" (periodic forms) or an array of fft_len values."""
+
+    _destroy = staticmethod(lib.doa_channel_covariance_destroy)
+    _set_format = staticmethod(lib.doa_channel_covariance_set_input_format)
+
+    def __init__(self, inputs, snapshot_size, overlap_size, fft_len, window="hann"):
+        super().__init__()
+        self.inputs, self.snapshot_size = int(inputs), int(snapshot_size)
+        self.overlap_size, self.fft_len = int(overlap_size), int(fft_len)
+        if isinstance(window, str):                   # (a bad fft_len is the library's to refuse: it does not read the window then)
+            w = _periodic_window(window, max(self.fft_len, 1))
+        else:
+            w = np.ascontiguousarray(window, dtype=_F32).reshape(-1)
+            if w.size != self.fft_len:
+                raise ValueError(f"window has {w.size} values, fft_len is {self.fft_len}")
+        self.window = w
+        self._h = check_handle(lib.doa_channel_covariance_create(self.inputs, self.snapshot_size, self.overlap_size,
+                                                                 self.fft_len, _vp(w)), "channel_covariance")
+        self.first_bin = 0
+        self.in_sig = [(_C64, 1)] * self.inputs
+        self.out_sig = [(_C64, self.inputs * self.inputs), (_F32, self.fft_len)]
+
+    def history(self) -> int:
+        return check(lib.doa_channel_covariance_history(self._h))
+
+    def forecast(self, noutput_items: int) -> int:
+        return check(lib.doa_channel_covariance_forecast(self._h, int(noutput_items)))
+
+    def input_span(self, noutput_items: int) -> int:
+        return int(lib.doa_channel_covariance_input_span(self._h, int(noutput_items)))
+
+    def set_bins(self, first_bin, num_bins) -> None:
+        """Write only the bins (first_bin + j) mod fft_len, j < num_bins; the power output keeps all fft_len bins."""
+        check(lib.doa_channel_covariance_set_bins(self._h, int(first_bin), int(num_bins)))
+        self.first_bin = int(first_bin)
+
+    def num_bins(self) -> int:
+        return check(lib.doa_channel_covariance_num_bins(self._h))
+
+    def bin_frequencies(self, sample_rate=1.0) -> np.ndarray:
+        """Centre frequency of every selected bin, in item order: fftfreq(fft_len) * sample_rate."""
+        sel = (self.first_bin + np.arange(self.num_bins())) % self.fft_len
+        return np.fft.fftfreq(self.fft_len)[sel] * float(sample_rate)
+
+    def general_work(self, noutput_items, input_items, output_items):
+        """input_items[k]: stream k from its first history sample (at least input_span(noutput_items) long);
+        output_items[0]: [>= n * num_bins(), N*N] complex64; output_items[1] (optional): [>= n, fft_len] float32.
+        noutput_items counts snapshots.  Returns (snapshots produced, samples consumed per input)."""
+        n = int(noutput_items)
+        arrs = self._host_streams(input_items, self.input_span(n))
+        cov = output_items[0]
+        assert cov.dtype == _C64 and cov.flags.c_contiguous and cov.size >= n * self.num_bins() * self.inputs ** 2
+        power = C.c_void_p(0)
+        if len(output_items) > 1 and output_items[1] is not None:
+            pw = output_items[1]
+            assert pw.dtype == _F32 and pw.flags.c_contiguous and pw.size >= n * self.fft_len
+            power = _vp(pw)
+        produced = check(lib.doa_channel_covariance_work(self._h, n, ptr_array([a.ctypes.data for a in arrs]), _vp(cov), power))
+        return produced, self.forecast(produced)
+
+    def work_dev(self, noutput_items, d_input_ptrs, d_cov_ptr, d_power_ptr=None, stream=None) -> int:
+        return check(lib.doa_channel_covariance_work_dev(self._h, int(noutput_items), ptr_array(d_input_ptrs),
+                                                         _dev_ptr(d_cov_ptr), _opt_ptr(d_power_ptr), _stream_ptr(stream)))
+
+
 def _fuse(fn, handle, correction, n):
     if correction is None:
         check(fn(handle, C.c_void_p(0)))

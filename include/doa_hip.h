@@ -947,6 +947,57 @@ DOA_HIP_API int doa_write_phase_config(const char *filename, const float *values
 DOA_HIP_API int doa_write_antenna_calib(const char *filename, const float *gains, const float *phases, int n);
 
 /* ---------------------------------------------------------------------------------------------
+ * channel_covariance — one covariance per snapshot AND frequency bin (the Welch / Bartlett cross-spectral matrix): the
+ *   front end for several narrowband emitters at different frequencies inside one captured band, which the whole-band
+ *   covariance of autocorrelate mixes (an N-element array separates at most N - 1 of them).  Every (snapshot, bin) matrix
+ *   is an ordinary covariance item: MUSIC_lin_array, capon_*, rootMUSIC_linear_array, esprit_linear_array, source_count,
+ *   spatial_smooth and the array blocks take the noutput_items * num_bins items as they are.  Not a block of the reference.
+ * The definition, one for every entry (tests/channel_covariance_ref.py restates it in numpy).  inputs N, snapshot_size K,
+ *   fft_len F, window w (F floats, NULL = all ones), B = K / F blocks per snapshot; snapshot i starts at sample
+ *   s_i = i (K - overlap_size) exactly as in autocorrelate, block b covers samples [bF, bF + F) of it:
+ *       X[a,b,f]   = sum_t w[t] x_a[s_i + bF + t] exp(-2 pi i f t / F)
+ *       R_i,f[p,q] = 1 / (B W2) sum_b X[p,b,f] conj(X[q,b,f]),      W2 = sum_t w[t]^2  (double, from the float32 w)
+ *   so white noise of variance s^2 gives a diagonal of s^2 in every bin for any window, and with the rectangular window
+ *   the mean of R_i,f over the F bins is the autocorrelate covariance (avg_method 0).  A bin's matrix has rank <= B.
+ *   Arithmetic is float: widened sample x window, float radix-2 FFT with twiddles rounded from double, float accumulation
+ *   over the blocks in block order, ONE final multiply by (float)(1 / (B W2)).  The result is exactly Hermitian (the lower
+ *   triangle is the bitwise conjugate of the upper one, diagonal imaginary parts are +0), has no atomics in it and does
+ *   not depend on noutput_items or on the item's position in the call.
+ * Layouts: input_items as autocorrelate (and its set_input_format contract, sc16 bit-identical to fc32 on the widened
+ *   samples).  out_cov = noutput_items * num_bins column-major N x N gr_complex matrices, item i * num_bins + j = bin
+ *   (first_bin + j) mod F of snapshot i; bins in natural FFT order (bin f = f / F cycles per sample, bins >= F / 2 are
+ *   negative frequencies).  out_power (optional, may be NULL) = noutput_items x F floats, ALWAYS all F bins in natural
+ *   order whatever the selection: power[i,f] = the float sum over p = 0..N-1, in that order, of the real diagonal of R_i,f
+ *   -- 4 F bytes per snapshot to find the occupied bins with.
+ * create validates before the device is looked for: 1 <= inputs <= 8 (9..16: not built into this library), fft_len one of
+ *   16, 32, 64, 128, 256, snapshot_size a positive multiple of fft_len, 0 <= overlap_size < snapshot_size, a finite window
+ *   with W2 > 0.  set_bins: 0 <= first_bin < F, 1 <= num_bins <= F (wrapping past F - 1), the default is all F bins; a
+ *   refused call returns DOA_ERR_INVALID_ARG and leaves the handle as it was.  Downstream cost scales with num_bins.
+ * work_dev queues on the caller's stream and does nothing else.  Device streams aligned to two samples with an even
+ *   snapshot_size - overlap_size take 16-byte (sc16: 8-byte) loads, any other stream aligned to one sample the scalar-load
+ *   route; both do the same arithmetic in the same order.  The host work returns with its stream synchronised whether it
+ *   worked or not.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct doa_channel_covariance doa_channel_covariance_t;
+
+DOA_HIP_API doa_channel_covariance_t *doa_channel_covariance_create(int inputs, int snapshot_size, int overlap_size,
+                                                                    int fft_len, const float *window);
+DOA_HIP_API void doa_channel_covariance_destroy(doa_channel_covariance_t *h);
+/* history, forecast and input_span: the formulas of autocorrelate */
+DOA_HIP_API int doa_channel_covariance_history(const doa_channel_covariance_t *h);
+DOA_HIP_API int doa_channel_covariance_forecast(const doa_channel_covariance_t *h, int noutput_items);
+DOA_HIP_API long long doa_channel_covariance_input_span(const doa_channel_covariance_t *h, int noutput_items);
+DOA_HIP_API int doa_channel_covariance_set_input_format(doa_channel_covariance_t *h, int format, float scale);
+DOA_HIP_API int doa_channel_covariance_set_bins(doa_channel_covariance_t *h, int first_bin, int num_bins);
+DOA_HIP_API int doa_channel_covariance_num_bins(const doa_channel_covariance_t *h);
+/* noutput_items counts snapshots */
+DOA_HIP_API int doa_channel_covariance_work(doa_channel_covariance_t *h, int noutput_items,
+                                            const void *const *input_items, void *out_cov, float *out_power);
+DOA_HIP_API int doa_channel_covariance_work_dev(doa_channel_covariance_t *h, int noutput_items,
+                                                const void *const *d_input_items, void *d_out_cov, void *d_out_power,
+                                                void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
  * sim_source — the signal front end of the simulation flowgraphs as one generator
  *   (reference apps/run_MUSIC_lin_array_simulation.py:66-74 array manifold, :204-210 sig_source_c +
  *   noise_source_c per source -> add -> multiply_matrix_cc):
