@@ -25,6 +25,48 @@ def five_emitters(n=6):
     return sim.make_streams(4, n * 1024, THETAS, 0.5, snr_db=20.0, seed=3, freqs=FREQS)
 
 
+FFT_LENS = (16, 32, 64, 128, 256)
+
+
+def round_structures(F):
+    """Block counts B = K / F that reach every guard of the kernel's round loop for this F.  A wave takes CB = max(1, 64 / F)
+    blocks side by side and a round RB = 4 CB blocks (csrc/channel_covariance.hip); the counts follow from those two:
+        1                a single block
+        CB - 1, CB + 1   a wave with some of its side-by-side blocks empty; a second wave with one block (CB > 1 only)
+        RB - 1, RB       one round less one block; exactly one round
+        RB + 1           a second round of one block
+        2 RB + CB + 1    a third round that ends inside the second wave
+        3 RB             several full rounds
+    F = 16: 1 3 5 15 16 17 37 48;  F = 32: 1 3 7 8 9 19 24;  F >= 64: 1 3 4 5 10 12."""
+    CB = max(1, 64 // F)
+    RB = 4 * CB
+    counts = {1, RB - 1, RB, RB + 1, 2 * RB + CB + 1, 3 * RB}
+    if CB > 1:
+        counts |= {CB - 1, CB + 1}
+    return sorted(counts)
+
+
+def partial_third_round(F):
+    """The count of round_structures(F) with two full rounds and a third that ends inside the second wave."""
+    CB = max(1, 64 // F)
+    return 2 * (4 * CB) + CB + 1
+
+
+def sweep_samples(N, F, B, n=3):
+    """The sweep's input: int16 [N, n B F, 2] over the whole int16 range, seeded by the shape.  doa.sim.from_sc16 widens
+    it to the complex64 samples the fc32 runs take, so every format and route sees the same values."""
+    return np.random.default_rng([N, F, B]).integers(-32768, 32768, size=(N, n * B * F, 2), dtype=np.int16)
+
+
+def sweep_window(case, F):
+    """Window number `case` of the sweep: the four named ones, then a random positive one (float32 [F])."""
+    names = WINDOWS + ("custom",)
+    name = names[case % len(names)]
+    if name == "custom":
+        return name, (0.25 + np.random.default_rng(F).random(F)).astype(np.float32)
+    return name, name
+
+
 def window(name, fft_len):
     """Periodic window of fft_len points, computed in double and rounded to float32."""
     t = 2.0 * np.pi * np.arange(fft_len, dtype=np.float64) / fft_len
@@ -71,6 +113,36 @@ def channel_covariance(x, K, overlap, F, w, n, first_bin=0, num_bins=None):
     N = R.shape[-1]
     items = R.transpose(0, 1, 3, 2).reshape(n, F, N * N)                         # column-major: p + q N
     return items[:, selected_bins(F, first_bin, num_bins)], power
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def assert_items_match(cov, pw, R64, p64, N, F, label=None):
+    """What every full-band output of the block is held to.  cov [n, F, N*N] complex64 and pw [n, F] float32 from the device,
+    R64 and p64 from channel_covariance().  Parity: |R_hip - R_f64| <= 2e-6 max|R|, the maximum over all bins of the
+    snapshot.  The item contract, bit for bit: the lower triangle is the conjugate of the upper one, diagonal imaginary
+    parts are +0, power is the in-order float sum of the stored diagonals (and within 2e-6 N max|R| of float64).
+    Prints the worst parity error as a fraction of max|R| under `label` before asserting, and returns it."""
+    n = cov.shape[0]
+    assert cov.shape == (n, F, N * N) and pw.shape == (n, F) and cov.dtype == np.complex64 and pw.dtype == np.float32
+    scale = np.abs(R64).reshape(n, -1).max(axis=1)
+    err = np.abs(cov - R64).reshape(n, -1).max(axis=1) / scale
+    if label:
+        print(f"{label}: {err.max():.2e} of max|R|")
+    assert err.max() <= 2e-6
+    # exactly Hermitian: the lower triangle is the bitwise conjugate of the upper one, diagonal imaginary parts are +0
+    M = cov.reshape(n, F, N, N)                                    # [i, f, q, p] = R[p, q]
+    assert np.array_equal(bits(M.real), bits(M.real.transpose(0, 1, 3, 2)))
+    assert np.array_equal(bits(M.imag), bits(-M.imag.transpose(0, 1, 3, 2)) * (1 - np.eye(N, dtype=np.uint32)))
+    # power: the in-order float sum of the returned diagonals, bit for bit
+    want = np.zeros((n, F), np.float32)
+    for p in range(N):
+        want = want + M[:, :, p, p].real
+    assert np.array_equal(bits(pw), bits(want))
+    assert np.abs(pw - p64).max() <= 2e-6 * N * scale.max()
+    return float(err.max())
 
 
 def _fft_f32(v):

@@ -76,6 +76,42 @@ def test_float32_restatement_is_within_the_parity_bound(F, K, N):
     assert np.abs(p32 - p64).max() <= 2e-6 * N * np.abs(R64).max()
 
 
+def test_round_structures_follow_from_the_round_geometry():
+    assert ref.round_structures(16) == [1, 3, 5, 15, 16, 17, 37, 48]
+    assert ref.round_structures(32) == [1, 3, 7, 8, 9, 19, 24]
+    for F in (64, 128, 256):
+        assert ref.round_structures(F) == [1, 3, 4, 5, 10, 12]
+    for F in ref.FFT_LENS:
+        assert ref.partial_third_round(F) in ref.round_structures(F)
+        assert max(ref.round_structures(F)) * F <= 3072
+
+
+@pytest.mark.parametrize("kind", ["gaussian", "int16"])
+@pytest.mark.parametrize("F", ref.FFT_LENS)
+def test_float32_restatement_is_within_the_parity_bound_on_the_sweep_grid(F, kind):
+    """The yardstick over the grid of test_gpu_channel_covariance_shapes.py: every round structure of F, N = 1, 3 and 8,
+    the four named windows, on Gaussian samples and on the sweep's widened int16 samples.  Measured worst figures (of
+    max|R| over 396 cases each; the bound is 2e-6): Gaussian 3.7e-7 (F = 256, B = 1, N = 3, blackman), int16 3.5e-7
+    (F = 256, B = 1, N = 1, blackman) -- both under half the bound, so the int16 samples are a fair input for it."""
+    n = 3
+    worst = (0.0, None)
+    for N in (1, 3, 8):
+        for B in ref.round_structures(F):
+            K = B * F
+            if kind == "gaussian":
+                x = _rand_streams(N, n * K, seed=F + 1000 * N + B)
+            else:
+                x = doa.sim.from_sc16(ref.sweep_samples(N, F, B, n))
+            for w in ref.WINDOWS:
+                R64, p64 = ref.channel_covariance(x, K, 0, F, w, n)
+                R32, p32 = ref.channel_covariance_f32(x, K, 0, F, w, n)
+                err = (np.abs(R32 - R64).reshape(n, -1).max(axis=1) / np.abs(R64).reshape(n, -1).max(axis=1)).max()
+                worst = max(worst, (float(err), (N, B, w)))
+                assert err <= 2e-6, (N, B, w)
+                assert np.abs(p32 - p64).max() <= 2e-6 * N * np.abs(R64).max(), (N, B, w)
+    print(f"float32 restatement F={F} {kind}: worst {worst[0]:.2e} of max|R| at (N, B, window) = {worst[1]}")
+
+
 def _create(inputs, K, ovl, F, window="default"):
     w = np.ones(max(F, 1), np.float32) if isinstance(window, str) else np.asarray(window, np.float32)
     return _lib.lib.doa_channel_covariance_create(inputs, K, ovl, F, None if window is None else w.ctypes.data)

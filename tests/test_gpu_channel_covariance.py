@@ -33,8 +33,7 @@ def _window(name, F):
     return name
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+_bits = ref.bits
 
 
 def _run(blk, x, n, power=True):
@@ -69,20 +68,9 @@ CASES = [(2, 64, 0, 16, "rect"), (3, 48, 16, 16, "hann"), (4, 1024, 0, 64, "hann
 @pytest.mark.parametrize("N,K,ovl,F,wname", CASES)
 def test_matches_the_float64_definition(N, K, ovl, F, wname):
     x, cov, pw, R64, p64 = _case(N, K, ovl, F, wname)
-    scale = np.abs(R64).reshape(N_SNAP, -1).max(axis=1)
-    err = np.abs(cov - R64).reshape(N_SNAP, -1).max(axis=1) / scale
-    print(f"N={N} K={K} overlap={ovl} F={F} {wname}: {err.max():.2e} of max|R|")
-    assert err.max() <= 2e-6
-    # exactly Hermitian: the lower triangle is the bitwise conjugate of the upper one, diagonal imaginary parts are +0
-    M = cov.reshape(N_SNAP, F, N, N)                               # [i, f, q, p] = R[p, q]
-    assert np.array_equal(_bits(M.real), _bits(M.real.transpose(0, 1, 3, 2)))
-    assert np.array_equal(_bits(M.imag), _bits(-M.imag.transpose(0, 1, 3, 2)) * (1 - np.eye(N, dtype=np.uint32)))
-    # power: the in-order float sum of the returned diagonals, bit for bit
-    want = np.zeros((N_SNAP, F), np.float32)
-    for p in range(N):
-        want = want + M[:, :, p, p].real
-    assert np.array_equal(_bits(pw), _bits(want))
-    assert np.abs(pw - p64).max() <= 2e-6 * N * scale.max()
+    # parity, exactly Hermitian items, power the in-order float sum of the stored diagonals: one helper, shared with the
+    # shape sweep (test_gpu_channel_covariance_shapes.py)
+    ref.assert_items_match(cov, pw, R64, p64, N, F, label=f"N={N} K={K} overlap={ovl} F={F} {wname}")
 
 
 def test_bin_selection_wraps_and_keeps_the_power_port():
