@@ -13,6 +13,7 @@
 // (R[a,b] *= g_a conj(g_b), before the forward-backward step) and the corrected streams are never
 // written to or re-read from HBM — that removes 16 B/sample/stream of traffic, twice what K1 itself
 // moves.  The two forms agree to fp32 rounding (~1e-7 relative).
+#include "block_host.hpp"
 #include "kernels.hpp"
 
 #include <cmath>
@@ -86,23 +87,34 @@ int launch_antenna_correction(int N, const float *gains_re_im, long long n, cons
 
 }  // namespace doa
 
-struct doa_antenna_correction {
+struct doa_antenna_correction : doa::BlockBase {
     int N = 0;
-    int device = 0;
     float gains[2 * DOA_MAX_ANT_ELE] = {0};
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out;
 };
+
+// what both creates check first, and their common tail: g = num_ant_ele (re, im) pairs
+static bool antenna_count_ok(int num_ant_ele)
+{
+    if (num_ant_ele > 0 && num_ant_ele <= DOA_MAX_ANT_ELE) return true;
+    doa::set_error("antenna_correction: num_ant_ele=%d outside 1..%d", num_ant_ele, DOA_MAX_ANT_ELE);
+    return false;
+}
+static doa_antenna_correction_t *antenna_create(int num_ant_ele, const float *g)
+{
+    return doa::create_block<doa_antenna_correction>("antenna_correction", [&](doa_antenna_correction &h) {
+        h.N = num_ant_ele;
+        memcpy(h.gains, g, sizeof(float) * 2 * num_ant_ele);
+        return (int)DOA_OK;
+    });
+}
 
 extern "C" {
 
 doa_antenna_correction_t *doa_antenna_correction_create(int num_ant_ele, const char *config_filename)
 {
     doa::clear_error();
-    if (num_ant_ele <= 0 || num_ant_ele > DOA_MAX_ANT_ELE) {
-        doa::set_error("antenna_correction: num_ant_ele=%d outside 1..%d", num_ant_ele, DOA_MAX_ANT_ELE);
-        return nullptr;
-    }
+    if (!antenna_count_ok(num_ant_ele)) return nullptr;
     if (!config_filename) { doa::set_error("antenna_correction: config_filename is NULL"); return nullptr; }
     // lib/antenna_correction_impl.cc:56-73 — same parsing (operator>> on floats), same messages
     std::ifstream infile(config_filename);
@@ -114,49 +126,18 @@ doa_antenna_correction_t *doa_antenna_correction_create(int num_ant_ele, const c
         g.push_back(std::complex<float>((float)(1.0 / GainEst), 0) * std::exp(std::complex<float>(0, -PhaseEst)));
     }
     if ((int)g.size() != num_ant_ele) { doa::set_error("Configuration file does not have enough inputs."); return nullptr; }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_antenna_correction();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->N = num_ant_ele; h->device = dev;
-    for (int k = 0; k < num_ant_ele; k++) { h->gains[2 * k] = g[k].real(); h->gains[2 * k + 1] = g[k].imag(); }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("antenna_correction: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+    return antenna_create(num_ant_ele, reinterpret_cast<const float *>(g.data()));   // (std::complex<float>: re, im)
 }
 
 doa_antenna_correction_t *doa_antenna_correction_create_gains(int num_ant_ele, const float *gains_re_im)
 {
     doa::clear_error();
-    if (num_ant_ele <= 0 || num_ant_ele > DOA_MAX_ANT_ELE) {
-        doa::set_error("antenna_correction: num_ant_ele=%d outside 1..%d", num_ant_ele, DOA_MAX_ANT_ELE);
-        return nullptr;
-    }
+    if (!antenna_count_ok(num_ant_ele)) return nullptr;
     if (!gains_re_im) { doa::set_error("antenna_correction: gains_re_im is NULL"); return nullptr; }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_antenna_correction();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->N = num_ant_ele; h->device = dev;
-    memcpy(h->gains, gains_re_im, sizeof(float) * 2 * num_ant_ele);
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("antenna_correction: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+    return antenna_create(num_ant_ele, gains_re_im);
 }
 
-void doa_antenna_correction_destroy(doa_antenna_correction_t *h)
-{
-    if (!h) return;
-    h->d_in.release(); h->d_out.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_antenna_correction_destroy(doa_antenna_correction_t *h) { doa::destroy_block(h); }
 
 int doa_antenna_correction_gains(const doa_antenna_correction_t *h, float *gains_re_im)
 {
@@ -169,10 +150,8 @@ int doa_antenna_correction_work_dev(doa_antenna_correction_t *h, int noutput_ite
                                     void *const *d_output_items, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || !d_input_items || !d_output_items) {
-        doa::set_error("antenna_correction_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("antenna_correction_work_dev", h, noutput_items, {d_input_items, d_output_items}); rc != DOA_OK) return rc;
+    if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     int rc = doa::launch_antenna_correction(h->N, h->gains, noutput_items, d_input_items, d_output_items,
                                             static_cast<hipStream_t>(hip_stream));
@@ -183,30 +162,17 @@ int doa_antenna_correction_work(doa_antenna_correction_t *h, int noutput_items, 
                                 void *const *output_items)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || !input_items || !output_items) {
-        doa::set_error("antenna_correction_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("antenna_correction_work", h, noutput_items, {input_items, output_items}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t n = (size_t)noutput_items, n_al = (n + 1) & ~(size_t)1;
-    int rc = h->d_in.reserve(n_al * h->N * sizeof(float2));
-    if (rc == DOA_OK) rc = h->d_out.reserve(n_al * h->N * sizeof(float2));
-    if (rc != DOA_OK) return rc;
+    const size_t bytes = (size_t)noutput_items * sizeof(float2);
+    doa::HostCall io(*h);
     const void *di[DOA_MAX_ANT_ELE];
     void *dout[DOA_MAX_ANT_ELE];
-    for (int k = 0; k < h->N; k++) {
-        if (!input_items[k] || !output_items[k]) { doa::set_error("antenna_correction_work: port %d is NULL", k); return DOA_ERR_INVALID_ARG; }
-        di[k] = h->d_in.as<float2>() + k * n_al;
-        dout[k] = h->d_out.as<float2>() + k * n_al;
-        DOA_HIP_TRY(hipMemcpyAsync(const_cast<void *>(di[k]), input_items[k], n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-    }
-    rc = doa::launch_antenna_correction(h->N, h->gains, noutput_items, di, dout, h->stream);
-    if (rc != DOA_OK) return rc;
-    for (int k = 0; k < h->N; k++)
-        DOA_HIP_TRY(hipMemcpyAsync(output_items[k], dout[k], n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    io.in_streams("antenna_correction_work", h->d_in, input_items, h->N, bytes, di);
+    // (n rounded up to even: every output stream stays 16-byte aligned, which the kernel's pair stores want)
+    int rc = io.out_streams("antenna_correction_work", h->d_out, output_items, h->N, bytes, (bytes + 15) & ~(size_t)15, dout);
+    if (rc == DOA_OK) rc = doa_antenna_correction_work_dev(h, noutput_items, di, dout, h->stream);
+    return io.finish(rc);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 // path (cov_piece_kernel + cov_combine_kernel); 8 < N <= 16 runs on the matrix cores (cov_mfma_kernel).
 // Every streaming kernel is templated on a sample loader (Fc32Samples / Sc16Samples): the sc16 form reads complex
 // int16 and widens in registers, with the same lanes, accumulators and summation order as the fc32 form.
+#include "block_host.hpp"
 #include "kernels.hpp"
 #include "launch_routes.hpp"
 #include "sample_loaders.hpp"
@@ -514,29 +515,6 @@ static CovKnobs cov_knobs()
             DOA_LAB_ENV_INT("DOA_COV_GROUP_WAVES_PER_CU", 0)};
 }
 
-// every stream of a batch aligned to two samples
-static bool streams_pair_aligned(const void *const *d_in, int N, int format)
-{
-    for (int k = 0; k < N; k++)
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % (2 * sample_bytes(format))) return false;
-    return true;
-}
-// One batch's N streams: every one non-NULL and aligned to one sample, else the error set (batch >= 0: named in it)
-static int check_streams(const void *const *d_in, int N, int format, int batch, bool *pair_aligned)
-{
-    const int sb = (int)sample_bytes(format);
-    for (int k = 0; k < N; k++) {
-        if (!d_in[k]) {
-            if (batch >= 0) set_error("autocorrelate: input stream %d of batch %d is NULL", k, batch);
-            else set_error("autocorrelate: input stream %d is NULL", k);
-            return DOA_ERR_INVALID_ARG;
-        }
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % sb) { set_error("autocorrelate: input stream %d is not %d-byte aligned", k, sb); return DOA_ERR_INVALID_ARG; }
-    }
-    *pair_aligned = streams_pair_aligned(d_in, N, format);
-    return DOA_OK;
-}
-
 static void fill_cov_args(CovArgs &g, int N, int K, int S, int avg, int n_out, const void *d_gain_outer, int format, float scale)
 {
     g.n_ch = N; g.K = K; g.S = S; g.n_out = n_out; g.avg = avg;
@@ -558,7 +536,7 @@ int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *
     CovShape shape;
     shape.N = N; shape.K = K; shape.ovl = ovl; shape.avg = avg; shape.n_out = n_out; shape.format = format;
     shape.workspace = (d_workspace != nullptr);
-    if (int rc = check_streams(d_in, N, format, -1, &shape.pair_aligned); rc != DOA_OK) return rc;
+    if (int rc = check_streams("autocorrelate", d_in, N, sample_bytes(format), &shape.pair_aligned); rc != DOA_OK) return rc;
     const CovRoute rt = cov_route(shape, cu_count(), cov_knobs());
     for (int k = 0; k < DOA_MAX_ANT_ELE; k++) g.in[k] = d_in[k < N ? k : 0];
     g.out = static_cast<float2 *>(d_out);
@@ -575,7 +553,9 @@ int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *
 
 bool autocorrelate_pair_loads(int N, int K, int ovl, const void *const *d_in, int format)
 {
-    return cov_pair_loads(K, ovl, streams_pair_aligned(d_in, N, format));
+    bool pair_aligned = true;           // (not check_streams: this only asks, a bad stream is the launch's to refuse)
+    for (int k = 0; k < N; k++) pair_aligned = pair_aligned && reinterpret_cast<uintptr_t>(d_in[k]) % (2 * sample_bytes(format)) == 0;
+    return cov_pair_loads(K, ovl, pair_aligned);
 }
 
 int launch_autocorrelate_group(int N, int K, int avg, const BatchGroup &grp, hipStream_t st, const void *d_gain_outer,
@@ -592,7 +572,7 @@ int launch_autocorrelate_group(int N, int K, int avg, const BatchGroup &grp, hip
     // a group must be uniform in the load route, because the two routes sum in different orders
     for (int b = 0; b < grp.n_batches; b++) {
         bool pair_aligned;
-        if (int rc = check_streams(grp.in[b], N, format, b, &pair_aligned); rc != DOA_OK) return rc;
+        if (int rc = check_streams("autocorrelate", grp.in[b], N, sample_bytes(format), &pair_aligned, b); rc != DOA_OK) return rc;
         if (b == 0) shape.pair_aligned = pair_aligned;
         else if (cov_pair_loads(K, 0, pair_aligned) != cov_pair_loads(K, 0, shape.pair_aligned)) {
             set_error("autocorrelate: a group mixes the two load routes");
@@ -615,36 +595,27 @@ int launch_autocorrelate_group(int N, int K, int avg, const BatchGroup &grp, hip
     return DOA_OK;
 }
 
-int check_input_format(const char *what, int format, float scale)
-{
-    if (format != DOA_SAMPLE_FC32 && format != DOA_SAMPLE_SC16) {
-        set_error("%s_set_input_format: unknown format %d (DOA_SAMPLE_FC32 = 0, DOA_SAMPLE_SC16 = 1)", what, format);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (!std::isfinite(scale) || !(scale > 0.0f)) {
-        set_error("%s_set_input_format: scale must be finite and > 0 (got %g)", what, (double)scale);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (format == DOA_SAMPLE_FC32 && scale != 1.0f) {
-        set_error("%s_set_input_format: fc32 samples are not rescaled (scale must be 1.0, got %g)", what, (double)scale);
-        return DOA_ERR_INVALID_ARG;
-    }
-    return DOA_OK;
-}
-
 }  // namespace doa
 
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_autocorrelate {
-    int inputs, snapshot, overlap, avg;
-    int device;
-    hipStream_t stream = nullptr;
+struct doa_autocorrelate : doa::BlockBase {
+    int inputs = 0, avg = 0;
+    doa::StreamWindow win;
+    doa::InputFormat fmt;               // doa_autocorrelate_set_input_format
     doa::DevBuf d_in, d_out, d_gain, d_work;
     bool has_gain = false;
-    int format = DOA_SAMPLE_FC32;       // doa_autocorrelate_set_input_format
-    float scale = 1.0f;
+    // K1 for n items on `st`, with the piece-sum workspace of the read-once path (grow-only; growing frees the old buffer,
+    // which waits for the device)
+    int launch(int n, const void *const *d_in_ptrs, void *d_out_items, hipStream_t st)
+    {
+        const size_t ws = doa::cov_workspace_bytes(inputs, win.K, win.overlap, n);
+        if (int rc = ws ? d_work.reserve(ws) : (int)DOA_OK; rc != DOA_OK) return rc;
+        const int rc = doa::launch_autocorrelate(inputs, win.K, win.overlap, avg, n, d_in_ptrs, d_out_items, st,
+                                                 has_gain ? d_gain.p : nullptr, ws ? d_work.p : nullptr, fmt.format, fmt.scale);
+        return rc == DOA_OK ? n : rc;
+    }
 };
 
 extern "C" {
@@ -663,30 +634,13 @@ doa_autocorrelate_t *doa_autocorrelate_create(int inputs, int snapshot_size, int
         doa::set_error("autocorrelate: inputs=%d exceeds DOA_MAX_ANT_ELE=%d", inputs, DOA_MAX_ANT_ELE);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_autocorrelate();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->inputs = inputs; h->snapshot = snapshot_size; h->overlap = overlap_size; h->avg = avg_method;
-    h->device = dev;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("autocorrelate: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_autocorrelate>("autocorrelate", [&](doa_autocorrelate &h) {
+        h.inputs = inputs; h.avg = avg_method; h.win.K = snapshot_size; h.win.overlap = overlap_size;
+        return (int)DOA_OK;
+    });
 }
 
-void doa_autocorrelate_destroy(doa_autocorrelate_t *h)
-{
-    if (!h) return;
-    h->d_in.release();
-    h->d_out.release();
-    h->d_gain.release();
-    h->d_work.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_autocorrelate_destroy(doa_autocorrelate_t *h) { doa::destroy_block(h); }
 
 int doa_autocorrelate_fuse_antenna_correction(doa_autocorrelate_t *h, const float *gains_re_im)
 {
@@ -710,81 +664,42 @@ int doa_autocorrelate_fuse_antenna_correction(doa_autocorrelate_t *h, const floa
 int doa_autocorrelate_set_input_format(doa_autocorrelate_t *h, int format, float scale)
 {
     doa::clear_error();
-    if (!h) { doa::set_error("autocorrelate_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (const int rc = doa::check_input_format("autocorrelate", format, scale); rc != DOA_OK) return rc;
-    h->format = format; h->scale = scale;
-    return DOA_OK;
+    return doa::set_input_format("autocorrelate", h ? &h->fmt : nullptr, format, scale);
 }
 
-int doa_autocorrelate_history(const doa_autocorrelate_t *h) { return h ? h->overlap + 1 : DOA_ERR_INVALID_ARG; }
+int doa_autocorrelate_history(const doa_autocorrelate_t *h) { return h ? h->win.history() : DOA_ERR_INVALID_ARG; }
 
 int doa_autocorrelate_forecast(const doa_autocorrelate_t *h, int noutput_items)
 {
-    if (!h || noutput_items < 0) return DOA_ERR_INVALID_ARG;
-    return (h->snapshot - h->overlap) * noutput_items;
+    return h && noutput_items >= 0 ? h->win.forecast(noutput_items) : DOA_ERR_INVALID_ARG;
 }
 
-long long doa_autocorrelate_input_span(const doa_autocorrelate_t *h, int noutput_items)
-{
-    if (!h || noutput_items <= 0) return 0;
-    return (long long)(noutput_items - 1) * (h->snapshot - h->overlap) + h->snapshot;
-}
+long long doa_autocorrelate_input_span(const doa_autocorrelate_t *h, int noutput_items) { return h ? h->win.input_span(noutput_items) : 0; }
 
 int doa_autocorrelate_work_dev(doa_autocorrelate_t *h, int noutput_items, const void *const *d_input_items,
                                void *d_output_items0, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || !d_input_items || (!d_output_items0 && noutput_items > 0)) {
-        doa::set_error("autocorrelate_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("autocorrelate_work_dev", h, noutput_items, {d_input_items, d_output_items0}); rc != DOA_OK) return rc;
+    if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    // piece-sum workspace of the read-once path (grow-only; growing frees the old buffer, which waits for the device)
-    const size_t ws = doa::cov_workspace_bytes(h->inputs, h->snapshot, h->overlap, noutput_items);
-    int rc = ws ? h->d_work.reserve(ws) : DOA_OK;
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_autocorrelate(h->inputs, h->snapshot, h->overlap, h->avg, noutput_items, d_input_items,
-                                   d_output_items0, static_cast<hipStream_t>(hip_stream),
-                                   h->has_gain ? h->d_gain.p : nullptr, ws ? h->d_work.p : nullptr, h->format, h->scale);
-    return rc == DOA_OK ? noutput_items : rc;
+    return h->launch(noutput_items, d_input_items, d_output_items0, static_cast<hipStream_t>(hip_stream));
 }
 
 int doa_autocorrelate_work(doa_autocorrelate_t *h, int noutput_items, const void *const *input_items,
                            void *output_items0)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || !input_items || (!output_items0 && noutput_items > 0)) {
-        doa::set_error("autocorrelate_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("autocorrelate_work", h, noutput_items, {input_items, output_items0}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const int N = h->inputs;
-    const size_t span = (size_t)doa_autocorrelate_input_span(h, noutput_items);
-    const size_t sb = doa::sample_bytes(h->format);
-    // distance between the device copies of the streams: 16-B aligned, staggered against the 8 KiB aliasing period
-    const size_t stride = doa::stream_stride_bytes(span * sb);
-    int rc = h->d_in.reserve(stride * N);
-    if (rc != DOA_OK) return rc;
-    const size_t out_bytes = (size_t)noutput_items * N * N * sizeof(float2);
-    rc = h->d_out.reserve(out_bytes);
-    if (rc != DOA_OK) return rc;
+    doa::HostCall io(*h);
     const void *d_ptrs[DOA_MAX_ANT_ELE];
-    for (int k = 0; k < N; k++) {
-        if (!input_items[k]) { doa::set_error("autocorrelate_work: input_items[%d] is NULL", k); return DOA_ERR_INVALID_ARG; }
-        char *dst = h->d_in.as<char>() + k * stride;
-        DOA_HIP_TRY(hipMemcpyAsync(dst, input_items[k], span * sb, hipMemcpyHostToDevice, h->stream));
-        d_ptrs[k] = dst;
-    }
-    const size_t ws = doa::cov_workspace_bytes(N, h->snapshot, h->overlap, noutput_items);
-    if (ws) rc = h->d_work.reserve(ws);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_autocorrelate(N, h->snapshot, h->overlap, h->avg, noutput_items, d_ptrs, h->d_out.p, h->stream,
-                                   h->has_gain ? h->d_gain.p : nullptr, ws ? h->d_work.p : nullptr, h->format, h->scale);
-    if (rc != DOA_OK) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(output_items0, h->d_out.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return noutput_items;
+    // (the device copies start on their stride boundaries, 16-byte aligned, whatever the caller's alignment)
+    io.in_streams("autocorrelate_work", h->d_in, input_items, N, (size_t)h->win.input_span(noutput_items) * h->fmt.sample_bytes(), d_ptrs);
+    int rc = io.out(h->d_out, output_items0, (size_t)noutput_items * N * N * sizeof(float2));
+    if (rc == DOA_OK) rc = h->launch(noutput_items, d_ptrs, h->d_out.p, h->stream);
+    return io.finish(rc);
 }
 
 }  // extern "C"

@@ -308,11 +308,11 @@ template <class L> static void launch_chan(int N, bool vec2, const ChanCovArgs &
 // C ABI
 // ---------------------------------------------------------------------------------------------
 struct doa_channel_covariance : doa::BlockBase {
-    int N = 0, K = 0, overlap = 0, F = 0, lg_f = 0;
+    int N = 0, F = 0, lg_f = 0;
+    doa::StreamWindow win;
     int first_bin = 0, num_bins = 0;
     float inv = 0.f;                       // (float)(1 / (B W2))
-    int format = DOA_SAMPLE_FC32;
-    float scale = 1.0f;
+    doa::InputFormat fmt;
     doa::DevBuf d_table;                   // [F/2] float2 twiddles, then [F] float window
     doa::DevBuf d_in, d_out, d_power;      // the host entry's buffers
 };
@@ -354,7 +354,7 @@ doa_channel_covariance_t *doa_channel_covariance_create(int inputs, int snapshot
         return nullptr;
     }
     return doa::create_block<doa_channel_covariance>("channel_covariance", [&](doa_channel_covariance &h) -> int {
-        h.N = inputs; h.K = snapshot_size; h.overlap = overlap_size; h.F = fft_len; h.lg_f = lg_f;
+        h.N = inputs; h.win.K = snapshot_size; h.win.overlap = overlap_size; h.F = fft_len; h.lg_f = lg_f;
         h.first_bin = 0; h.num_bins = fft_len;
         h.inv = (float)(1.0 / ((double)(snapshot_size / fft_len) * w2));
         // twiddles and window: built here in double, rounded once, read by every launch of the handle
@@ -373,27 +373,22 @@ doa_channel_covariance_t *doa_channel_covariance_create(int inputs, int snapshot
 
 void doa_channel_covariance_destroy(doa_channel_covariance_t *h) { doa::destroy_block(h); }
 
-int doa_channel_covariance_history(const doa_channel_covariance_t *h) { return h ? h->overlap + 1 : DOA_ERR_INVALID_ARG; }
+int doa_channel_covariance_history(const doa_channel_covariance_t *h) { return h ? h->win.history() : DOA_ERR_INVALID_ARG; }
 
 int doa_channel_covariance_forecast(const doa_channel_covariance_t *h, int noutput_items)
 {
-    if (!h || noutput_items < 0) return DOA_ERR_INVALID_ARG;
-    return (h->K - h->overlap) * noutput_items;
+    return h && noutput_items >= 0 ? h->win.forecast(noutput_items) : DOA_ERR_INVALID_ARG;
 }
 
 long long doa_channel_covariance_input_span(const doa_channel_covariance_t *h, int noutput_items)
 {
-    if (!h || noutput_items <= 0) return 0;
-    return (long long)(noutput_items - 1) * (h->K - h->overlap) + h->K;
+    return h ? h->win.input_span(noutput_items) : 0;
 }
 
 int doa_channel_covariance_set_input_format(doa_channel_covariance_t *h, int format, float scale)
 {
     doa::clear_error();
-    if (!h) { doa::set_error("channel_covariance_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (const int rc = doa::check_input_format("channel_covariance", format, scale); rc != DOA_OK) return rc;
-    h->format = format; h->scale = scale;
-    return DOA_OK;
+    return doa::set_input_format("channel_covariance", h ? &h->fmt : nullptr, format, scale);
 }
 
 int doa_channel_covariance_set_bins(doa_channel_covariance_t *h, int first_bin, int num_bins)
@@ -418,29 +413,23 @@ int doa_channel_covariance_work_dev(doa_channel_covariance_t *h, int noutput_ite
     if (int rc = doa::work_args("channel_covariance_work_dev", h, noutput_items, {d_input_items, d_out_cov}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const int sb = (int)doa::sample_bytes(h->format);
     bool pair_aligned = true;
+    if (int rc = doa::check_streams("channel_covariance_work_dev", d_input_items, h->N, h->fmt.sample_bytes(), &pair_aligned); rc != DOA_OK) return rc;
     doa::ChanCovArgs g;
     memset(&g, 0, sizeof g);
-    for (int k = 0; k < h->N; k++) {
-        const uintptr_t p = reinterpret_cast<uintptr_t>(d_input_items[k]);
-        if (!p) { doa::set_error("channel_covariance_work_dev: input stream %d is NULL", k); return DOA_ERR_INVALID_ARG; }
-        if (p % sb) { doa::set_error("channel_covariance_work_dev: input stream %d is not %d-byte aligned", k, sb); return DOA_ERR_INVALID_ARG; }
-        if (p % (2 * sb)) pair_aligned = false;
-    }
     for (int k = 0; k < doa::kChanMaxInputs; k++) g.in[k] = d_input_items[k < h->N ? k : 0];
     g.out = static_cast<float2 *>(d_out_cov);
     g.power = static_cast<float *>(d_out_power);
     g.twiddle = h->d_table.as<float2>();
     g.window = h->d_table.as<float>() + h->F;
-    g.K = h->K; g.S = h->K - h->overlap; g.F = h->F; g.lg_f = h->lg_f; g.B = h->K / h->F;
+    g.K = h->win.K; g.S = h->win.step(); g.F = h->F; g.lg_f = h->lg_f; g.B = h->win.K / h->F;
     g.first_bin = h->first_bin; g.num_bins = h->num_bins;
     g.inv = h->inv;
-    g.scale = h->format == DOA_SAMPLE_SC16 ? h->scale : 1.0f;
+    g.scale = h->fmt.kernel_scale();
     // pair loads: every block of every snapshot starts on a sample pair (F is even, so only the snapshot step matters)
     const bool vec2 = pair_aligned && (g.S % 2 == 0);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (h->format == DOA_SAMPLE_SC16) doa::launch_chan<doa::Sc16Samples>(h->N, vec2, g, noutput_items, st);
+    if (h->fmt.format == DOA_SAMPLE_SC16) doa::launch_chan<doa::Sc16Samples>(h->N, vec2, g, noutput_items, st);
     else                              doa::launch_chan<doa::Fc32Samples>(h->N, vec2, g, noutput_items, st);
     DOA_HIP_TRY(hipGetLastError());
     return noutput_items;
@@ -453,31 +442,14 @@ int doa_channel_covariance_work(doa_channel_covariance_t *h, int noutput_items, 
     if (int rc = doa::work_args("channel_covariance_work", h, noutput_items, {input_items, out_cov}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     const int N = h->N;
-    const size_t sb = doa::sample_bytes(h->format);
-    const size_t span = (size_t)doa_channel_covariance_input_span(h, noutput_items);
-    for (int k = 0; k < N; k++) {
-        if (!input_items[k]) { doa::set_error("channel_covariance_work: input_items[%d] is NULL", k); return DOA_ERR_INVALID_ARG; }
-        if (reinterpret_cast<uintptr_t>(input_items[k]) % sb) {
-            doa::set_error("channel_covariance_work: input_items[%d] is not %d-byte aligned", k, (int)sb);
-            return DOA_ERR_INVALID_ARG;
-        }
-    }
-    // the device copy of a stream keeps the caller's offset inside 16 bytes, so the load route follows the caller's alignment
-    const size_t stride = doa::stream_stride_bytes(span * sb + 16);
+    const size_t sb = h->fmt.sample_bytes();
     doa::HostCall io(*h);
-    int rc = io.status();
-    if (rc == DOA_OK) rc = h->d_in.reserve(stride * N);
     const void *d_ptrs[doa::kChanMaxInputs];
-    for (int k = 0; k < N && rc == DOA_OK; k++) {
-        char *dst = h->d_in.as<char>() + k * stride + reinterpret_cast<uintptr_t>(input_items[k]) % 16;
-        if (hipMemcpyAsync(dst, input_items[k], span * sb, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-            doa::set_error("channel_covariance_work: the copy of stream %d to the device failed", k);
-            rc = DOA_ERR_HIP;
-        }
-        d_ptrs[k] = dst;
-    }
-    if (rc == DOA_OK) rc = io.out(h->d_out, out_cov, (size_t)noutput_items * h->num_bins * N * N * sizeof(float2));
-    if (rc == DOA_OK && out_power) rc = io.out(h->d_power, out_power, (size_t)noutput_items * h->F * sizeof(float));
+    // the device copy of a stream keeps the caller's offset inside 16 bytes, so the load route follows the caller's alignment
+    io.in_streams("channel_covariance_work", h->d_in, input_items, N, (size_t)h->win.input_span(noutput_items) * sb, d_ptrs, 0, sb);
+    io.out(h->d_out, out_cov, (size_t)noutput_items * h->num_bins * N * N * sizeof(float2));
+    if (out_power) io.out(h->d_power, out_power, (size_t)noutput_items * h->F * sizeof(float));
+    int rc = io.status();
     if (rc == DOA_OK)
         rc = doa_channel_covariance_work_dev(h, noutput_items, d_ptrs, h->d_out.p, out_power ? h->d_power.p : nullptr, h->stream);
     return io.finish(rc);

@@ -2,6 +2,7 @@
 #include "common.hpp"
 
 #include <atomic>
+#include <cmath>
 #include <mutex>
 
 namespace doa {
@@ -131,6 +132,23 @@ void PinnedBuf::release()
 }
 
 int internal_precision_bits() { return g_prec_bits.load(); }
+
+int check_input_format(const char *what, int format, float scale)
+{
+    if (format != DOA_SAMPLE_FC32 && format != DOA_SAMPLE_SC16) {
+        set_error("%s_set_input_format: unknown format %d (DOA_SAMPLE_FC32 = 0, DOA_SAMPLE_SC16 = 1)", what, format);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(scale) || !(scale > 0.0f)) {
+        set_error("%s_set_input_format: scale must be finite and > 0 (got %g)", what, (double)scale);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (format == DOA_SAMPLE_FC32 && scale != 1.0f) {
+        set_error("%s_set_input_format: fc32 samples are not rescaled (scale must be 1.0, got %g)", what, (double)scale);
+        return DOA_ERR_INVALID_ARG;
+    }
+    return DOA_OK;
+}
 
 }  // namespace doa
 

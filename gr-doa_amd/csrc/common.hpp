@@ -73,6 +73,11 @@ struct PinnedBuf {
 
 int internal_precision_bits();  // 32 or 64 (doa_set_internal_precision)
 
+// the input sample formats (DOA_SAMPLE_FC32 / DOA_SAMPLE_SC16): bytes per sample, and the validation behind every
+// doa_*_set_input_format entry (DOA_OK, or DOA_ERR_INVALID_ARG with the error set)
+inline size_t sample_bytes(int format) { return format == DOA_SAMPLE_SC16 ? 4 : 8; }
+int check_input_format(const char *what, int format, float scale);
+
 // Launch-shape knobs for same-box A/B runs exist only in lab builds (make LAB=1); the default build has none of them
 // compiled in and this is the constant `dflt`.
 #ifdef DOA_LAB

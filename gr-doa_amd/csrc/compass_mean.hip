@@ -13,6 +13,7 @@
 // numpy.mean of a float32 array accumulates pairwise in float32; here the sum is carried in double
 // and rounded once, so the result is the correctly rounded mean (numpy's differs from it by <= a few
 // ulp).  ninput_items == 0 gives NaN, as numpy.mean of an empty array does.
+#include "block_host.hpp"
 #include "kernels.hpp"
 
 #include <cmath>
@@ -36,10 +37,8 @@ __global__ __launch_bounds__(256) void compass_mean_kernel(const float *__restri
 
 }  // namespace doa
 
-struct doa_compass_mean {
+struct doa_compass_mean : doa::BlockBase {
     int M = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;
     doa::DevBuf d_in, d_out;
 };
 
@@ -52,35 +51,18 @@ doa_compass_mean_t *doa_compass_mean_create(int num_streams)
         doa::set_error("compass_mean: num_streams=%d outside 1..%d", num_streams, DOA_MAX_PEAKS);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_compass_mean();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->M = num_streams; h->device = dev;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("compass_mean: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_compass_mean>("compass_mean", [&](doa_compass_mean &h) { h.M = num_streams; return (int)DOA_OK; });
 }
 
-void doa_compass_mean_destroy(doa_compass_mean_t *h)
-{
-    if (!h) return;
-    h->d_in.release(); h->d_out.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_compass_mean_destroy(doa_compass_mean_t *h) { doa::destroy_block(h); }
 
+// Zero items is a call like any other: the kernel runs and writes NaN.  next_angle is therefore required then too, which
+// work_args does not ask of its pointer list: without it the call is refused as one without a handle is.
 int doa_compass_mean_work_dev(doa_compass_mean_t *h, int ninput_items, const void *d_input_items0, float *d_next_angle,
                               void *hip_stream)
 {
     doa::clear_error();
-    if (!h || ninput_items < 0 || !d_next_angle || (ninput_items > 0 && !d_input_items0)) {
-        doa::set_error("compass_mean_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("compass_mean_work_dev", d_next_angle ? h : nullptr, ninput_items, {d_input_items0}); rc != DOA_OK) return rc;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipLaunchKernelGGL(doa::compass_mean_kernel, dim3(h->M), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
                        static_cast<const float *>(d_input_items0), d_next_angle, ninput_items, h->M);
@@ -91,21 +73,12 @@ int doa_compass_mean_work_dev(doa_compass_mean_t *h, int ninput_items, const voi
 int doa_compass_mean_work(doa_compass_mean_t *h, int ninput_items, const void *input_items0, float *next_angle)
 {
     doa::clear_error();
-    if (!h || ninput_items < 0 || !next_angle || (ninput_items > 0 && !input_items0)) {
-        doa::set_error("compass_mean_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t bytes = (size_t)ninput_items * h->M * sizeof(float);
-    int rc = h->d_in.reserve(bytes ? bytes : sizeof(float));
-    if (rc == DOA_OK) rc = h->d_out.reserve(h->M * sizeof(float));
-    if (rc != DOA_OK) return rc;
-    if (bytes) DOA_HIP_TRY(hipMemcpyAsync(h->d_in.p, input_items0, bytes, hipMemcpyHostToDevice, h->stream));
-    rc = doa_compass_mean_work_dev(h, ninput_items, h->d_in.p, h->d_out.as<float>(), h->stream);
-    if (rc < 0) return rc;
-    DOA_HIP_TRY(hipMemcpyAsync(next_angle, h->d_out.p, h->M * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    return ninput_items;
+    if (int rc = doa::work_args("compass_mean_work", next_angle ? h : nullptr, ninput_items, {input_items0}); rc != DOA_OK) return rc;
+    doa::HostCall io(*h);
+    if (ninput_items > 0) io.in(h->d_in, input_items0, (size_t)ninput_items * h->M * sizeof(float));
+    int rc = io.out(h->d_out, next_angle, h->M * sizeof(float));
+    if (rc == DOA_OK) rc = doa_compass_mean_work_dev(h, ninput_items, h->d_in.p, h->d_out.as<float>(), h->stream);
+    return io.finish(rc);
 }
 
 }  // extern "C"

@@ -12,9 +12,6 @@ namespace doa {
 int launch_autocorrelate(int N, int K, int ovl, int avg, int n_out, const void *const *d_in, void *d_out,
                          hipStream_t st, const void *d_gain_outer = nullptr, void *d_workspace = nullptr,
                          int format = DOA_SAMPLE_FC32, float scale = 1.0f);
-// validation shared by the three doa_*_set_input_format entries (DOA_OK, or DOA_ERR_INVALID_ARG with the error set)
-int check_input_format(const char *what, int format, float scale);
-inline size_t sample_bytes(int format) { return format == DOA_SAMPLE_SC16 ? 4 : 8; }
 
 // ---- multi-batch ("grouped") launches of the lean route: the shapes evd_route and scan_route accept in their group modes -----
 // One K1, one EVD and one scan launch each cover a GROUP of up to kMaxGroup batches of `n` items each: item

@@ -17,6 +17,7 @@
 //   in a fixed order (thread t takes chunks t, t + 256, ...; fixed LDS tree).  No atomics; the result does not depend on
 //   the grid, on the alignment route or on how a host caller's samples were staged.
 // atan2f is the device library's (see DESIGN.md section 7 for the instruction count and where the kernel sits).
+#include "block_host.hpp"
 #include "kernels.hpp"
 #include "sample_loaders.hpp"
 
@@ -205,13 +206,10 @@ __global__ __launch_bounds__(256) void poe_combine_kernel(const PoePartial *__re
 
 static bool poe_fill_streams(PoeArgs &g, const char *what, int N, const void *const *d_in, size_t skip_samples, size_t sb)
 {
-    g.vec2 = 1;
-    for (int k = 0; k < N; k++) {
-        if (!d_in[k]) { set_error("%s: input stream %d is NULL", what, k); return false; }
-        if (reinterpret_cast<uintptr_t>(d_in[k]) % sb) { set_error("%s: input stream %d is not %d-byte aligned", what, k, (int)sb); return false; }
-        g.in[k] = static_cast<const char *>(d_in[k]) + skip_samples * sb;
-        if (reinterpret_cast<uintptr_t>(g.in[k]) % (2 * sb)) g.vec2 = 0;
-    }
+    bool pair_aligned;                  // judged after the skip, where the kernel starts to read
+    if (check_streams(what, d_in, N, sb, &pair_aligned, -1, skip_samples * sb) != DOA_OK) return false;
+    g.vec2 = pair_aligned;
+    for (int k = 0; k < N; k++) g.in[k] = static_cast<const char *>(d_in[k]) + skip_samples * sb;
     for (int k = N; k < DOA_MAX_ANT_ELE; k++) g.in[k] = g.in[0];
     return true;
 }
@@ -288,15 +286,12 @@ static long long poe_stage_samples(int N, size_t sb)
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-struct doa_phase_offset_est {
+struct doa_phase_offset_est : doa::BlockBase {
     int N = 0;
     long long n_skip = 0;               // blocks.skiphead's argument
-    long long skipped = 0;              // samples dropped so far (the skiphead state)
-    int device = 0;
-    int format = DOA_SAMPLE_FC32;
-    float scale = 1.0f;
-    hipStream_t stream = nullptr;
-    doa::DevBuf d_in, d_out, d_part, d_res;
+    long long skipped = 0;              // samples dropped so far (the skiphead state): moves only when a call has succeeded
+    doa::InputFormat fmt;
+    doa::DevBuf d_in, d_out, d_part, d_res[3];
     long long owed() const { return n_skip > skipped ? n_skip - skipped : 0; }
 };
 
@@ -310,26 +305,13 @@ doa_phase_offset_est_t *doa_phase_offset_est_create(int num_ports, int n_skip_ah
         return nullptr;
     }
     if (n_skip_ahead < 0) { doa::set_error("phase_offset_est: n_skip_ahead=%d is negative", n_skip_ahead); return nullptr; }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_phase_offset_est();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    h->N = num_ports; h->n_skip = n_skip_ahead; h->device = dev;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("phase_offset_est: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+    return doa::create_block<doa_phase_offset_est>("phase_offset_est", [&](doa_phase_offset_est &h) {
+        h.N = num_ports; h.n_skip = n_skip_ahead;
+        return (int)DOA_OK;
+    });
 }
 
-void doa_phase_offset_est_destroy(doa_phase_offset_est_t *h)
-{
-    if (!h) return;
-    h->d_in.release(); h->d_out.release(); h->d_part.release(); h->d_res.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_phase_offset_est_destroy(doa_phase_offset_est_t *h) { doa::destroy_block(h); }
 
 int doa_phase_offset_est_reset(doa_phase_offset_est_t *h)
 {
@@ -342,24 +324,19 @@ int doa_phase_offset_est_reset(doa_phase_offset_est_t *h)
 int doa_phase_offset_est_set_input_format(doa_phase_offset_est_t *h, int format, float scale)
 {
     doa::clear_error();
-    if (!h) { doa::set_error("phase_offset_est_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (const int rc = doa::check_input_format("phase_offset_est", format, scale); rc != DOA_OK) return rc;
-    h->format = format; h->scale = scale;
-    return DOA_OK;
+    return doa::set_input_format("phase_offset_est", h ? &h->fmt : nullptr, format, scale);
 }
 
 int doa_phase_offset_est_work_dev(doa_phase_offset_est_t *h, int n_items, const void *const *d_input_items,
                                   void *const *d_output_items, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || n_items < 0 || !d_input_items || !d_output_items) {
-        doa::set_error("phase_offset_est_work_dev: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::work_args("phase_offset_est_work_dev", h, n_items, {d_input_items, d_output_items}); rc != DOA_OK) return rc;
+    if (n_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     const long long drop = h->owed() < n_items ? h->owed() : n_items;
     const int produce = (int)(n_items - drop);
-    const int rc = doa::launch_poe_stream(h->N, h->format, h->scale, d_input_items, (size_t)drop, produce, d_output_items,
+    const int rc = doa::launch_poe_stream(h->N, h->fmt.format, h->fmt.scale, d_input_items, (size_t)drop, produce, d_output_items,
                                           static_cast<hipStream_t>(hip_stream));
     if (rc != DOA_OK) return rc;
     h->skipped += drop;
@@ -370,42 +347,26 @@ int doa_phase_offset_est_work(doa_phase_offset_est_t *h, int n_items, const void
                               void *const *output_items)
 {
     doa::clear_error();
-    if (!h || n_items < 0 || !input_items || !output_items) {
-        doa::set_error("phase_offset_est_work: bad arguments");
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
+    if (int rc = doa::work_args("phase_offset_est_work", h, n_items, {input_items, output_items}); rc != DOA_OK) return rc;
+    if (n_items == 0) return 0;
     const int N = h->N;
-    for (int k = 0; k < N; k++)
+    for (int k = 0; k < N; k++)         // every port, also in a call the skip swallows whole
         if (!input_items[k] || (k < N - 1 && !output_items[k])) { doa::set_error("phase_offset_est_work: port %d is NULL", k); return DOA_ERR_INVALID_ARG; }
     const long long drop = h->owed() < n_items ? h->owed() : n_items;
     const long long produce = n_items - drop;
-    const size_t sb = doa::sample_bytes(h->format);
+    const size_t sb = h->fmt.sample_bytes();
     const long long stage = doa::poe_stage_samples(N, sb);
-    const long long first = produce < stage ? produce : stage;
-    const size_t in_stride = doa::stream_stride_bytes((size_t)first * sb), out_stride = ((size_t)first * sizeof(float) + 15) & ~(size_t)15;
-    if (produce > 0) {
-        int rc = h->d_in.reserve(in_stride * N);
-        if (rc == DOA_OK) rc = h->d_out.reserve(out_stride * (N - 1));
-        if (rc != DOA_OK) return rc;
-    }
+    // one round trip per staged piece (the first is the largest, so the buffers grow once)
     for (long long s0 = 0; s0 < produce; s0 += stage) {
         const long long cnt = produce - s0 < stage ? produce - s0 : stage;
+        doa::HostCall io(*h);
         const void *di[DOA_MAX_ANT_ELE];
         void *dout[DOA_MAX_ANT_ELE];
-        for (int k = 0; k < N; k++) {
-            char *dst = h->d_in.as<char>() + k * in_stride;
-            DOA_HIP_TRY(hipMemcpyAsync(dst, static_cast<const char *>(input_items[k]) + (size_t)(drop + s0) * sb, (size_t)cnt * sb,
-                                       hipMemcpyHostToDevice, h->stream));
-            di[k] = dst;
-            if (k < N - 1) dout[k] = h->d_out.as<char>() + k * out_stride;
-        }
-        const int rc = doa::launch_poe_stream(N, h->format, h->scale, di, 0, cnt, dout, h->stream);
-        if (rc != DOA_OK) return rc;
-        for (int p = 0; p < N - 1; p++)
-            DOA_HIP_TRY(hipMemcpyAsync(static_cast<float *>(output_items[p]) + s0, dout[p], (size_t)cnt * sizeof(float),
-                                       hipMemcpyDeviceToHost, h->stream));
-        DOA_HIP_TRY(hipStreamSynchronize(h->stream));
+        io.in_streams("phase_offset_est_work", h->d_in, input_items, N, (size_t)cnt * sb, di, (size_t)(drop + s0) * sb);
+        int rc = io.out_streams("phase_offset_est_work", h->d_out, output_items, N - 1, (size_t)cnt * sizeof(float),
+                                ((size_t)cnt * sizeof(float) + 15) & ~(size_t)15, dout, (size_t)s0 * sizeof(float));
+        if (rc == DOA_OK) rc = doa::launch_poe_stream(N, h->fmt.format, h->fmt.scale, di, 0, cnt, dout, h->stream);
+        if (rc = io.finish(rc); rc != DOA_OK) return rc;
     }
     h->skipped += drop;
     return (int)produce;
@@ -439,7 +400,7 @@ int doa_phase_offset_est_estimate_dev(doa_phase_offset_est_t *h, long long n_ite
     // per-chunk partials (grow-only; growing frees the old buffer, which waits for the device)
     int rc = h->d_part.reserve((size_t)doa::poe_chunks(samples) * (h->N - 1) * sizeof(doa::PoePartial));
     if (rc != DOA_OK) return rc;
-    rc = doa::launch_poe_partial(h->N, h->format, h->scale, d_input_items, (size_t)drop, samples, 0, h->d_part.p, st);
+    rc = doa::launch_poe_partial(h->N, h->fmt.format, h->fmt.scale, d_input_items, (size_t)drop, samples, 0, h->d_part.p, st);
     if (rc == DOA_OK) rc = doa::launch_poe_combine(h->N, samples, h->d_part.p, d_mean_out, d_max_out, d_circ_out, st);
     if (rc != DOA_OK) return rc;
     h->skipped += drop;
@@ -453,38 +414,23 @@ int doa_phase_offset_est_estimate(doa_phase_offset_est_t *h, long long n_items, 
     long long drop = 0;
     if (const int rc = poe_estimate_args("phase_offset_est_estimate", h, n_items, input_items, samples, &drop); rc != DOA_OK) return rc;
     const int N = h->N;
-    for (int k = 0; k < N; k++)
-        if (!input_items[k]) { doa::set_error("phase_offset_est_estimate: input_items[%d] is NULL", k); return DOA_ERR_INVALID_ARG; }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t sb = doa::sample_bytes(h->format);
+    const size_t sb = h->fmt.sample_bytes();
     const long long stage = doa::poe_stage_samples(N, sb);              // a whole number of chunks: the partition is that of
-    const long long first = samples < stage ? samples : stage;          // the device entry, whatever the staging
-    const size_t stride = doa::stream_stride_bytes((size_t)first * sb);
-    int rc = h->d_in.reserve(stride * N);
+    doa::HostCall io(*h);                                               // the device entry, whatever the staging
+    int rc = io.status();
     if (rc == DOA_OK) rc = h->d_part.reserve((size_t)doa::poe_chunks(samples) * (N - 1) * sizeof(doa::PoePartial));
-    if (rc == DOA_OK) rc = h->d_res.reserve(3 * (N - 1) * sizeof(float));
-    if (rc != DOA_OK) return rc;
-    for (long long s0 = 0; s0 < samples; s0 += stage) {
+    // (the pieces follow one another on the stream, so one staging buffer serves them all; the first is the largest)
+    for (long long s0 = 0; s0 < samples && rc == DOA_OK; s0 += stage) {
         const long long cnt = samples - s0 < stage ? samples - s0 : stage;
         const void *di[DOA_MAX_ANT_ELE];
-        for (int k = 0; k < N; k++) {
-            char *dst = h->d_in.as<char>() + k * stride;
-            DOA_HIP_TRY(hipMemcpyAsync(dst, static_cast<const char *>(input_items[k]) + (size_t)(drop + s0) * sb, (size_t)cnt * sb,
-                                       hipMemcpyHostToDevice, h->stream));
-            di[k] = dst;
-        }
-        rc = doa::launch_poe_partial(N, h->format, h->scale, di, 0, cnt, (int)(s0 / doa::kChunk), h->d_part.p, h->stream);
-        if (rc != DOA_OK) return rc;
+        rc = io.in_streams("phase_offset_est_estimate", h->d_in, input_items, N, (size_t)cnt * sb, di, (size_t)(drop + s0) * sb);
+        if (rc == DOA_OK) rc = doa::launch_poe_partial(N, h->fmt.format, h->fmt.scale, di, 0, cnt, (int)(s0 / doa::kChunk), h->d_part.p, h->stream);
     }
-    float *res = h->d_res.as<float>();
-    rc = doa::launch_poe_combine(N, samples, h->d_part.p, res, res + (N - 1), res + 2 * (N - 1), h->stream);
-    if (rc != DOA_OK) return rc;
-    float host[3 * (DOA_MAX_ANT_ELE - 1)];
-    DOA_HIP_TRY(hipMemcpyAsync(host, res, 3 * (N - 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (mean_out) memcpy(mean_out, host, (N - 1) * sizeof(float));
-    if (max_out) memcpy(max_out, host + (N - 1), (N - 1) * sizeof(float));
-    if (circ_out) memcpy(circ_out, host + 2 * (N - 1), (N - 1) * sizeof(float));
+    float *const host[3] = {mean_out, max_out, circ_out};
+    for (int i = 0; i < 3 && rc == DOA_OK; i++) rc = io.out(h->d_res[i], host[i], (N - 1) * sizeof(float));
+    if (rc == DOA_OK)
+        rc = doa::launch_poe_combine(N, samples, h->d_part.p, h->d_res[0].as<float>(), h->d_res[1].as<float>(), h->d_res[2].as<float>(), h->stream);
+    if (rc = io.finish(rc); rc != DOA_OK) return rc;
     h->skipped += drop;
     return DOA_OK;
 }

@@ -448,7 +448,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         out[2] = d_max_out[b]; out[3] = d_argmax_out[b];
         nb.store = (out[1] != nullptr);
         nb.lean = lean_shape && reinterpret_cast<uintptr_t>(out[1]) % 16 == 0;
-        nb.vec2 = nb.lean && doa::autocorrelate_pair_loads(N, h->K, h->ovl, d_input_items + (size_t)b * N, h->format);
+        nb.vec2 = nb.lean && doa::autocorrelate_pair_loads(N, h->K, h->ovl, d_input_items + (size_t)b * N, h->fmt.format);
         nb.cap = !nb.lean ? 1 : (nb.store ? G : G_angles);
         if (b == 0 && group_first() > 0 && group_first() < nb.cap) nb.cap = group_first();
     };
@@ -479,7 +479,7 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
         }
         const unsigned skip = ~h->stages & 7u;                   // doa_music_pipeline_set_stages
         int rc = DOA_OK;
-        if (!(skip & 1)) rc = doa::launch_autocorrelate_group(N, h->K, h->avg, grp, ln.st, h->has_gain ? h->d_gain.p : nullptr, h->format, h->scale);
+        if (!(skip & 1)) rc = doa::launch_autocorrelate_group(N, h->K, h->avg, grp, ln.st, h->has_gain ? h->d_gain.p : nullptr, h->fmt.format, h->fmt.scale);
         if (rc == DOA_OK && !(skip & 2)) rc = doa::launch_music_evd_group(N, h->music.M, grp, nullptr, ws.rec.cheb, ln.st);
         if (rc == DOA_OK && !(skip & 4)) rc = doa::launch_music_scan_group(h->music, h->peaks, grp, ws.rec.cheb, g.store, ln.st);
         return rc;

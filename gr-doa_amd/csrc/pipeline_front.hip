@@ -57,13 +57,6 @@ int PipeFront::fuse_antenna_correction(const float *gains_re_im)
     return DOA_OK;
 }
 
-int PipeFront::set_input_format(const char *who, int format_, float scale_)
-{
-    if (const int rc = check_input_format(who, format_, scale_); rc != DOA_OK) return rc;
-    format = format_; scale = scale_;
-    return DOA_OK;
-}
-
 int PipeFront::smoothing_args(const char *who, int M, int S_, int forward_backward) const
 {
     if (S_ == 0 || (S_ >= 2 && S_ <= N && M < S_ && (forward_backward == 0 || forward_backward == 1))) return DOA_OK;
@@ -112,7 +105,7 @@ int PipeFront::host_run(const char *who, int n_items, const void *const *input_i
     fail_chunk = -1; lanes.fail_batch = -1;             // one-shot: armed for THIS call only, wherever it ends
     const size_t n_all = (size_t)n_items;
     const size_t nonoverlap = (size_t)(K - ovl);
-    const size_t sb = sample_bytes(format);             // bytes per input sample: 8 (fc32) or 4 (sc16)
+    const size_t sb = fmt.sample_bytes();            // bytes per input sample: 8 (fc32) or 4 (sc16)
     // The result block of the staged path holds the present sections in the order given, each on a 256-byte boundary (the
     // scan kernels' 16-byte stores need aligned spectrum rows); the chunked path keeps the sections without a device area of
     // their own in d_res, laid out the same way for max_batch items.

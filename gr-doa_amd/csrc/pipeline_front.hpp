@@ -4,6 +4,7 @@
 // handle adds its estimator stage: its own members, a callback that queues its chain, and the list of its output sections.
 // Host-only; the kernels are launched through kernels.hpp.  INTEGRATION.md ("Adding a block") shows what a handle writes.
 #pragma once
+#include "block_host.hpp"
 #include "kernels.hpp"
 #include "pipeline_lanes.hpp"
 
@@ -32,8 +33,7 @@ struct PipeFront {
     int device = 0;
     DevBuf d_gain;
     bool has_gain = false;
-    int format = DOA_SAMPLE_FC32;   // set_input_format
-    float scale = 1.0f;
+    InputFormat fmt;                // set_input_format
     int S = 0, fb = 0;              // spatial smoothing: subarray size (0 = off), forward-backward
     // The handle's own workspace is a lane without a stream of its own (a call sets self.st to the caller's stream): work_dev,
     // work_dev_auto, the host entry and a solo work_dev_batches call use it, every other work_dev_batches call the lanes below.
@@ -58,7 +58,7 @@ struct PipeFront {
     static void destroy(PipeFront *h);
 
     int fuse_antenna_correction(const float *gains_re_im);
-    int set_input_format(const char *who, int format_, float scale_);
+    int set_input_format(const char *who, int format, float scale) { return fmt.set(who, format, scale); }
     // set_spatial_smoothing in two steps, with room for a handle's own refusals between them and its own tables after them.
     // smoothing_args: the range and flag check (M = the handle's source count).  smoothing_reserve: 0 = the handle has
     // (S_, fb_) already, nothing to do; 1 = device bound, the caller reserves `self` for S_, finishes and stores S and fb.
@@ -88,7 +88,7 @@ struct PipeFront {
     // the front of a chain: K1 for n items on `st` into `cov` (`work`: its piece sums, or NULL) ...
     int run_k1(int n, const void *const *d_in_ptrs, void *cov, void *work, hipStream_t st) const
     {
-        return launch_autocorrelate(N, K, ovl, avg, n, d_in_ptrs, cov, st, has_gain ? d_gain.p : nullptr, work, format, scale);
+        return launch_autocorrelate(N, K, ovl, avg, n, d_in_ptrs, cov, st, has_gain ? d_gain.p : nullptr, work, fmt.format, fmt.scale);
     }
     // ... and the smoothing launch into `smooth` (none when it is off); `cov` stays the N x N item and is returned as what the
     // eigen stage reads

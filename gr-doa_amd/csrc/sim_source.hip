@@ -22,6 +22,7 @@
 // The kernel is write-bound in principle (8 N bytes per sample); at small N the Philox rounds make it
 // ALU-bound instead, which is irrelevant for a setup step.  One thread produces two consecutive samples
 // of every stream (16-byte stores, 1 KiB contiguous per wave instruction per stream).
+#include "block_host.hpp"
 #include "kernels.hpp"
 
 #include <cmath>
@@ -124,11 +125,9 @@ __global__ __launch_bounds__(256) void sim_source_kernel(SimArgs a)
 
 }  // namespace doa
 
-struct doa_sim_source {
+struct doa_sim_source : doa::BlockBase {
     doa::SimArgs a;
-    int device = 0;
     long long pos = 0;      // next sample index
-    hipStream_t stream = nullptr;
     doa::DevBuf d_out;
 };
 
@@ -145,42 +144,28 @@ doa_sim_source_t *doa_sim_source_create(int num_ant_ele, int num_sources, float 
                        num_sources, (double)norm_spacing);
         return nullptr;
     }
-    int dev = 0;
-    if (doa::ensure_device(&dev) != DOA_OK) return nullptr;
-    auto *h = new (std::nothrow) doa_sim_source();
-    if (!h) { doa::set_error("out of memory"); return nullptr; }
-    memset(&h->a, 0, sizeof h->a);
-    h->device = dev;
-    h->a.N = num_ant_ele; h->a.M = num_sources;
-    h->a.ant_sigma = antenna_noise_sigma;
-    h->a.key0 = (unsigned)(seed & 0xFFFFFFFFull); h->a.key1 = (unsigned)(seed >> 32);
-    const double pi = 3.14159265358979323846;
-    for (int m = 0; m < num_sources; m++) {
-        h->a.freq[m] = tone_freq[m];
-        h->a.ampl[m] = tone_ampl ? tone_ampl[m] : 1.0f;
-        h->a.src_noise[m] = source_noise_ampl ? source_noise_ampl[m] : 0.0f;
-        const double c = cos((double)theta_deg[m] * pi / 180.0);
-        for (int k = 0; k < num_ant_ele; k++) {
-            const double loc = (double)norm_spacing * ((num_ant_ele - 1) / 2.0 - k);
-            const double ph = -2.0 * pi * c * loc;
-            h->a.A[k * num_sources + m] = make_float2((float)cos(ph), (float)sin(ph));
+    return doa::create_block<doa_sim_source>("sim_source", [&](doa_sim_source &h) {
+        memset(&h.a, 0, sizeof h.a);
+        h.a.N = num_ant_ele; h.a.M = num_sources;
+        h.a.ant_sigma = antenna_noise_sigma;
+        h.a.key0 = (unsigned)(seed & 0xFFFFFFFFull); h.a.key1 = (unsigned)(seed >> 32);
+        const double pi = 3.14159265358979323846;
+        for (int m = 0; m < num_sources; m++) {
+            h.a.freq[m] = tone_freq[m];
+            h.a.ampl[m] = tone_ampl ? tone_ampl[m] : 1.0f;
+            h.a.src_noise[m] = source_noise_ampl ? source_noise_ampl[m] : 0.0f;
+            const double c = cos((double)theta_deg[m] * pi / 180.0);
+            for (int k = 0; k < num_ant_ele; k++) {
+                const double loc = (double)norm_spacing * ((num_ant_ele - 1) / 2.0 - k);
+                const double ph = -2.0 * pi * c * loc;
+                h.a.A[k * num_sources + m] = make_float2((float)cos(ph), (float)sin(ph));
+            }
         }
-    }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        doa::set_error("sim_source: hipStreamCreate failed");
-        delete h;
-        return nullptr;
-    }
-    return h;
+        return (int)DOA_OK;
+    });
 }
 
-void doa_sim_source_destroy(doa_sim_source_t *h)
-{
-    if (!h) return;
-    h->d_out.release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void doa_sim_source_destroy(doa_sim_source_t *h) { doa::destroy_block(h); }
 
 int doa_sim_source_seek(doa_sim_source_t *h, long long sample_index)
 {
@@ -216,12 +201,19 @@ static int sim_launch(doa_sim_source_t *h, int n, void *const *d_out, hipStream_
 }
 
 // Positions stay even between calls (a Philox block covers a sample pair): every call but the last of a
-// run must ask for an even number of samples.
+// run must ask for an even number of samples.  The position moves only when the call has succeeded.
+static int sim_position_even(const doa_sim_source_t *h)
+{
+    if (!(h->pos & 1)) return DOA_OK;
+    doa::set_error("sim_source: the previous call produced an odd number of samples; seek first");
+    return DOA_ERR_INVALID_ARG;
+}
+
 int doa_sim_source_work_dev(doa_sim_source_t *h, int noutput_items, void *const *d_output_items, void *hip_stream)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || !d_output_items) { doa::set_error("sim_source_work_dev: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (h->pos & 1) { doa::set_error("sim_source: the previous call produced an odd number of samples; seek first"); return DOA_ERR_INVALID_ARG; }
+    if (int rc = doa::work_args("sim_source_work_dev", h, noutput_items, {d_output_items}); rc != DOA_OK) return rc;
+    if (int rc = sim_position_even(h); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     int rc = sim_launch(h, noutput_items, d_output_items, static_cast<hipStream_t>(hip_stream));
@@ -233,25 +225,18 @@ int doa_sim_source_work_dev(doa_sim_source_t *h, int noutput_items, void *const 
 int doa_sim_source_work(doa_sim_source_t *h, int noutput_items, void *const *output_items)
 {
     doa::clear_error();
-    if (!h || noutput_items < 0 || !output_items) { doa::set_error("sim_source_work: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (h->pos & 1) { doa::set_error("sim_source: the previous call produced an odd number of samples; seek first"); return DOA_ERR_INVALID_ARG; }
+    if (int rc = doa::work_args("sim_source_work", h, noutput_items, {output_items}); rc != DOA_OK) return rc;
+    if (int rc = sim_position_even(h); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const size_t n = (size_t)noutput_items, n_al = (n + 1) & ~(size_t)1;
-    int rc = h->d_out.reserve(n_al * h->a.N * sizeof(float2));
-    if (rc != DOA_OK) return rc;
+    const size_t bytes = (size_t)noutput_items * sizeof(float2);
+    doa::HostCall io(*h);
     void *d[DOA_MAX_ANT_ELE];
-    for (int k = 0; k < h->a.N; k++) {
-        if (!output_items[k]) { doa::set_error("sim_source_work: output stream %d is NULL", k); return DOA_ERR_INVALID_ARG; }
-        d[k] = h->d_out.as<float2>() + k * n_al;
-    }
-    rc = sim_launch(h, noutput_items, d, h->stream);
-    if (rc != DOA_OK) return rc;
-    for (int k = 0; k < h->a.N; k++)
-        DOA_HIP_TRY(hipMemcpyAsync(output_items[k], d[k], n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    DOA_HIP_TRY(hipStreamSynchronize(h->stream));
-    h->pos += noutput_items;
-    return noutput_items;
+    // (n rounded up to even: every stream stays 16-byte aligned, which the kernel requires)
+    int rc = io.out_streams("sim_source_work", h->d_out, output_items, h->a.N, bytes, (bytes + 15) & ~(size_t)15, d);
+    if (rc == DOA_OK) rc = sim_launch(h, noutput_items, d, h->stream);
+    rc = io.finish(rc == DOA_OK ? noutput_items : rc);
+    if (rc >= 0) h->pos += noutput_items;
+    return rc;
 }
 
 }  // extern "C"
