@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "launch_routes.hpp"
 #include "sample_loaders.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 #include <cstdlib>

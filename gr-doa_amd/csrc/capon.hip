@@ -18,6 +18,7 @@
 // result on nothing but the item.  A failing item (status 1) computes on with whatever its arithmetic gives -- no lane leaves
 // a cross-lane operation -- and its record is replaced by NaN at the end.
 #include "kernels.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -25,14 +26,6 @@ namespace doa {
 namespace {
 
 constexpr double kPivotMin = DOA_CAPON_PIVOT_MIN;
-
-__device__ __forceinline__ double group_fetch(double v, int src_lane) { return __shfl(v, src_lane, kWave); }
-template <int G> __device__ __forceinline__ double group_sum_d(double v, int lane)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) v += __shfl(v, lane ^ m, kWave);
-    return v;
-}
 
 // ---- N <= 4: one lane per item ---------------------------------------------------------------------------------------------
 template <int N, bool WOUT>
@@ -196,7 +189,7 @@ __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *_
         ai[c] = low ? -(double)x.y : 0.0;
         if (c == r) dg = (double)x.x;
     }
-    const double mu = group_sum_d<G>(row ? dg : 0.0, lane) / (double)N;
+    const double mu = group_sum<G, double>(row ? dg : 0.0, lane) / (double)N;
     bool bad = !(mu > 0.0);
     const double rmu = 1.0 / mu;
 #pragma unroll
@@ -209,14 +202,14 @@ __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *_
 #pragma unroll
     for (int j = 0; j < G; j++) {
         if (j < N) {
-            const double rs = 1.0 / sqrt(group_fetch(dg, base + j));        // 1 / L[j][j]
+            const double rs = 1.0 / sqrt(lane_fetch<double>(dg, base + j));        // 1 / L[j][j]
             const bool below = r > j;
             const double lr = below ? ar[j] * rs : 0.0, li = below ? ai[j] * rs : 0.0;      // L[r][j]
             ar[j] = lr; ai[j] = li;
             dg -= fma(lr, lr, li * li);
 #pragma unroll
             for (int c = j + 1; c < G; c++) {
-                const double cr = group_fetch(lr, base + c), ci = group_fetch(li, base + c);      // L[c][j]
+                const double cr = lane_fetch<double>(lr, base + c), ci = lane_fetch<double>(li, base + c);      // L[c][j]
                 ar[c] -= fma(lr, cr, li * ci);                       // A[r][c] -= L[r][j] conj(L[c][j]), r > c
                 ai[c] -= fma(li, cr, -(lr * ci));
             }
@@ -236,11 +229,11 @@ __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *_
             const double lkr = ar[k], lki = ai[k];
 #pragma unroll
             for (int c = 0; c < k; c++) {
-                const double vr = group_fetch(mr[c] * rd, base + k), vi = group_fetch(mi[c] * rd, base + k);   // M[k][c]
+                const double vr = lane_fetch<double>(mr[c] * rd, base + k), vi = lane_fetch<double>(mi[c] * rd, base + k);   // M[k][c]
                 mr[c] -= fma(lkr, vr, -(lki * vi));
                 mi[c] -= fma(lkr, vi, lki * vr);
             }
-            const double vd = group_fetch(rd, base + k);                                                         // M[k][k]
+            const double vd = lane_fetch<double>(rd, base + k);                                                         // M[k][k]
             mr[k] -= lkr * vd;
             mi[k] -= lki * vd;
         }
@@ -262,19 +255,14 @@ __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *_
                 tr = fma(mr[c + l], mr[c], fma(mi[c + l], mi[c], tr));
                 ti = fma(mr[c + l], mi[c], fma(-mi[c + l], mr[c], ti));
             }
-            tr = group_sum_d<G>(tr, lane);
-            ti = (l == 0) ? 0.0 : group_sum_d<G>(ti, lane);
+            tr = group_sum<G, double>(tr, lane);
+            ti = (l == 0) ? 0.0 : group_sum<G, double>(ti, lane);
             fin = fma(tr, 0.0, fma(ti, 0.0, fin));
             if (r == l) { ur = tr; ui = ti; }
         }
     }
     bad = bad || !(fin == 0.0);
-    {
-        int b = bad ? 1 : 0;
-#pragma unroll
-        for (int m = 1; m < G; m <<= 1) b |= __shfl(b, lane ^ m, kWave);
-        bad = b != 0;
-    }
+    bad = group_or<G>(bad ? 1 : 0, lane) != 0;
     if (bad) { ur = (double)NAN; ui = (double)NAN; }
     if (real_item && r == 0 && status) status[item] = bad ? 1 : 0;
     if (real_item && row && coef_d) {                    // (NULL on a steering-table handle: its scan reads the full record)
@@ -294,8 +282,8 @@ __global__ __launch_bounds__(64) void capon_inverse_group_kernel(const float2 *_
                 if (j < N) {
                     double wr = fma(mr[i], mr[j], mi[i] * mi[j]);                  // conj(M[r][i]) M[r][j]
                     double wi = fma(mr[i], mi[j], -(mi[i] * mr[j]));
-                    wr = group_sum_d<G>(wr, lane);
-                    wi = group_sum_d<G>(wi, lane);
+                    wr = group_sum<G, double>(wr, lane);
+                    wi = group_sum<G, double>(wi, lane);
                     if (bad) { wr = (double)NAN; wi = (double)NAN; }
                     if (real_item && r == 0 && w_out) {
                         float2 *wo = w_out + off;
@@ -319,7 +307,7 @@ __global__ __launch_bounds__(256) void capon_invalid_rows_kernel(const int *__re
                                                                  float *__restrict__ mx, float *__restrict__ am, int M, int n_items)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    const int item = wave_index();
     if (item >= n_items) return;
     if (status[item] == 0) return;
     if (spec) {

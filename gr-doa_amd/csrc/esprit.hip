@@ -17,6 +17,7 @@
 // Every loop that holds a barrier is wave-uniform (bounds from the launch's W, the per-item work under predicates); no lane
 // returns before the end.  An item's result depends on nothing but the item and its count.
 #include "kernels.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -62,13 +63,6 @@ __device__ __forceinline__ void eig2(Cplx a, Cplx b, Cplx c, Cplx d, Cplx &l1, C
     const Cplx det = {ad.re - bc.re, ad.im - bc.im};
     if (l1.re == 0.0 && l1.im == 0.0) l2 = {0.0, 0.0};
     else l2 = cdiv(det, l1);
-}
-
-template <int G> __device__ __forceinline__ double group_sum_d(double v, int lane)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) v += __shfl(v, lane ^ m, kWave);
-    return v;
 }
 
 template <int G>
@@ -117,8 +111,8 @@ __global__ __launch_bounds__(64) void esprit_kernel(const float2 *__restrict__ R
             else tr = (double)x.x;
         }
     }
-    tr = group_sum_d<G>(tr, lane);
-    poison = group_sum_d<G>(poison, lane);
+    tr = group_sum<G, double>(tr, lane);
+    poison = group_sum<G, double>(poison, lane);
     __syncthreads();
 
     // gamma, F = Es1^H Es2 and Psi: lane j owns column j

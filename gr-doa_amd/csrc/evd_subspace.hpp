@@ -32,29 +32,11 @@
 
 namespace doa {
 
-template <int CTRL> __device__ __forceinline__ double dpp_mov_d(double v)
-{
-    const long long x = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(x & 0xFFFFFFFFll), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(x >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-// sum over the 16 lanes of a DPP row, result in every lane of the row
-__device__ __forceinline__ double row_sum16(double v)
-{
-    v += dpp_mov_d<0xB1>(v);        // quad_perm [1,0,3,2]
-    v += dpp_mov_d<0x4E>(v);        // quad_perm [2,3,0,1]
-    v += dpp_mov_d<0x124>(v);       // row_ror:4
-    v += dpp_mov_d<0x128>(v);       // row_ror:8
-    return v;
-}
-__device__ __forceinline__ double shfl_d(double v, int src_lane) { return __shfl(v, src_lane, kWave); }
-
 // y += As[S] * rot_S(x), S = 1..G-1 (rot_S: lane r' takes the value of lane (r' + S) mod 16 = row_ror:(16 - S))
 template <int G, int S> struct SkewMac {
     static __device__ __forceinline__ void run(const double (&ar)[G], const double (&ai)[G], double xr, double xi, double &yr, double &yi)
     {
-        const double pr = dpp_mov_d<0x120 + (16 - S)>(xr), pi = dpp_mov_d<0x120 + (16 - S)>(xi);
+        const double pr = dpp<row_ror<16 - S>>(0.0, xr), pi = dpp<row_ror<16 - S>>(0.0, xi);
         yr = fma(ar[S], pr, fma(-ai[S], pi, yr));
         yi = fma(ar[S], pi, fma(ai[S], pr, yi));
         if constexpr (S + 1 < G) SkewMac<G, S + 1>::run(ar, ai, xr, xi, yr, yi);
@@ -176,7 +158,7 @@ __device__ __forceinline__ bool evd_subspace_item(const float2 *__restrict__ Ri,
         SkewMac<G, 1>::run(ar, ai, xr, xi, yr, yi);
         // all columns of Y at this row
 #pragma unroll
-        for (int c = 0; c < MC; c++) { ycr[c] = shfl_d(yr, 16 * c + rp); yci[c] = shfl_d(yi, 16 * c + rp); }
+        for (int c = 0; c < MC; c++) { ycr[c] = lane_fetch<double>(yr, 16 * c + rp); yci[c] = lane_fetch<double>(yi, 16 * c + rp); }
         if (it == next_check) {
             // T' = X^H Y = X^H A X - mu I (upper triangle, mirrored), residual ||Y - X T'||_F
             double tr_[MC][MC], ti_[MC][MC];
@@ -281,8 +263,8 @@ __device__ __forceinline__ bool evd_subspace_item(const float2 *__restrict__ Ri,
                 }
             }
         }
-        tr += shfl_d(tr, lane ^ 1); ti += shfl_d(ti, lane ^ 1);
-        tr += shfl_d(tr, lane ^ 2); ti += shfl_d(ti, lane ^ 2);
+        tr += lane_fetch<double>(tr, lane ^ 1); ti += lane_fetch<double>(ti, lane ^ 1);
+        tr += lane_fetch<double>(tr, lane ^ 2); ti += lane_fetch<double>(ti, lane ^ 2);
         if (c4 == 0 && l < N) {
             float *co = out.coef ? out.coef + (size_t)item * (2 * N) : nullptr;
             double *cd = out.coef_d ? out.coef_d + (size_t)item * (2 * N) : nullptr;

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void find_local_max_kernel(const float *__rest
 {
     const int W = ms.width();
     const int lane = threadIdx.x & (kWave - 1);
-    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    const int item = wave_index();
     if (item >= n_items) return;
     const float *v_in = in + (size_t)item * L;
 
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void find_local_max_stream_kernel(const float 
 {
     const int W = ms.width();
     const int lane = threadIdx.x & (kWave - 1);
-    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    const int item = wave_index();
     if (item >= n_items) return;
     const float *v_in = in + (size_t)item * L;
     const int M = ms.begin(item, lane, out_val + (size_t)item * W, out_loc + (size_t)item * W);
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void find_local_max_blocked_kernel(const float
     const int W = ms.width();
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = threadIdx.x / kWave;
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + wib);
+    const int wave = wave_index();
     const int n_waves = gridDim.x * (blockDim.x / kWave);
     float *lrow = rows[wib];
     struct PaddedRow {

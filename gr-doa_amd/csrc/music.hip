@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void music_invalid_rows_kernel(const int *__re
                                                                  int P, int n_items)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    const int item = wave_index();
     if (item >= n_items) return;
     const int m = counts[item];
     if (m >= 0 && m < N) return;

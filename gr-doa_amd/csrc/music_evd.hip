@@ -10,6 +10,7 @@
 // Rotations: jacobi_rotation (float angle, T-precision unitarity); matrices pre-scaled to max |entry| in [1, 2).
 // Output: one 2N-value coefficient record per item ([u0, Re u1, Im u1, ...]); P_N itself on request.
 #include "jacobi.hpp"
+#include "wave_ops.hpp"
 #include "evd_subspace.hpp"
 #include "launch_routes.hpp"
 #include <mutex>
@@ -118,32 +119,8 @@ template <int G> struct Tournament {
     static constexpr int q(int t, int j) { return a(t, j) < b(t, j) ? b(t, j) : a(t, j); }
 };
 
-template <typename T> __device__ __forceinline__ T lane_fetch(T v, int src_lane);
-template <> __device__ __forceinline__ float lane_fetch<float>(float v, int src_lane) { return __shfl(v, src_lane, kWave); }
-template <> __device__ __forceinline__ double lane_fetch<double>(double v, int src_lane) { return __shfl(v, src_lane, kWave); }
-
-// sum over the G lanes of a group (G = 4, 8, 16; groups are aligned inside a DPP row of 16)
-template <int G, typename T> __device__ __forceinline__ T group_sum(T v, int lane)
-{
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) v += lane_fetch<T>(v, lane ^ m);
-    return v;
-}
-
 // G == 4: a group is a DPP quad, so every cross-lane fetch of the round is a quad_perm with a compile-time pattern
 // (a few cycles on the vector pipe instead of a ~100-cycle ds_bpermute round trip -- this kernel is a pure latency chain)
-template <int PATTERN> __device__ __forceinline__ float quad_fetch(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), PATTERN, 0xF, 0xF, false));
-}
-template <int PATTERN> __device__ __forceinline__ double quad_fetch(double v)
-{
-    const long long x = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp((int)(x & 0xFFFFFFFFll), (int)(x & 0xFFFFFFFFll), PATTERN, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(x >> 32), (int)(x >> 32), PATTERN, 0xF, 0xF, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-constexpr int quad_pattern(int s0, int s1, int s2, int s3) { return s0 | (s1 << 2) | (s2 << 4) | (s3 << 6); }
 // partner of quad lane r in round t of the 4-player tournament: t=0: 0<->3, 1<->2; t=1: 0<->2, 1<->3; t=2: 0<->1, 2<->3
 constexpr int quad_partner(int t, int r) { return (r == 3) ? t : ((r == t) ? 3 : (2 * t - r + 6) % 3); }
 constexpr int quad_lower(int t, int r) { return r < quad_partner(t, r) ? r : quad_partner(t, r); }
@@ -157,8 +134,8 @@ __device__ __forceinline__ void jacobi_round(T (&ar)[G], T (&ai)[G], T (&vr)[G],
     constexpr int RT = (G == 4) ? ROUND : 0;
     constexpr int PAT_PARTNER = quad_pattern(quad_partner(RT, 0), quad_partner(RT, 1), quad_partner(RT, 2), quad_partner(RT, 3));
     constexpr int PAT_LOWER = quad_pattern(quad_lower(RT, 0), quad_lower(RT, 1), quad_lower(RT, 2), quad_lower(RT, 3));
-    auto from_partner = [&](T v) { if constexpr (G == 4) return quad_fetch<PAT_PARTNER>(v); else return lane_fetch<T>(v, base + partner); };
-    auto from_lower = [&](T v, int lo_lane) { if constexpr (G == 4) return quad_fetch<PAT_LOWER>(v); else return lane_fetch<T>(v, base + lo_lane); };
+    auto from_partner = [&](T v) { if constexpr (G == 4) return dpp<PAT_PARTNER>(v, v); else return lane_fetch<T>(v, base + partner); };
+    auto from_lower = [&](T v, int lo_lane) { if constexpr (G == 4) return dpp<PAT_LOWER>(v, v); else return lane_fetch<T>(v, base + lo_lane); };
     // own diagonal, partner diagonal, pivot element A[r][partner]
     T d_own = 0, xr = 0, xi = 0;
 #pragma unroll
@@ -184,7 +161,7 @@ __device__ __forceinline__ void jacobi_round(T (&ar)[G], T (&ai)[G], T (&vr)[G],
         constexpr int P0 = TT::p(RT, 0) & 3, P1 = TT::p(RT, 1) & 3;       // G == 4: the two pairs' lower lanes
         constexpr int PB0 = quad_pattern(P0, P0, P0, P0), PB1 = quad_pattern(P1, P1, P1, P1);
         auto bcast = [&](T v) {
-            if constexpr (G == 4) return (j == 0) ? quad_fetch<PB0>(v) : quad_fetch<PB1>(v);
+            if constexpr (G == 4) return (j == 0) ? dpp<PB0>(v, v) : dpp<PB1>(v, v);
             else return lane_fetch<T>(v, base + P);
         };
         const T cj = bcast(c);
@@ -508,17 +485,6 @@ __global__ __launch_bounds__(64) void music_evd_group_counts_kernel(const float2
 // consequence: a quad that fails any of them takes the cyclic Jacobi -- evd_group_wave<4> in the same wave, which keeps
 // the reference's behaviour for ties (ranks by index).  Rows r >= N are zero padding (they stay zero through the iteration).
 // ---------------------------------------------------------------------------------------------
-template <int S> __device__ __forceinline__ double quad_rot(double v)      // lane r takes the value of quad lane (r + S) mod 4
-{
-    return quad_fetch<quad_pattern(S & 3, (1 + S) & 3, (2 + S) & 3, (3 + S) & 3)>(v);
-}
-__device__ __forceinline__ double quad_sum(double v)
-{
-    v += quad_fetch<quad_pattern(1, 0, 3, 2)>(v);
-    v += quad_fetch<quad_pattern(2, 3, 0, 1)>(v);
-    return v;                                                  // the same bits in the four lanes (a + b == b + a)
-}
-
 // ok (quad-uniform): X holds an orthonormal basis of the top-MC eigenspace, certified
 template <int MC>
 __device__ __forceinline__ bool evd_quad_subspace(const float2 *__restrict__ Ri, int N, int r, double (&xcr)[MC], double (&xci)[MC])
@@ -538,8 +504,8 @@ __device__ __forceinline__ bool evd_quad_subspace(const float2 *__restrict__ Ri,
         ar[s] = (double)e.x; ai[s] = (double)e.y;
         m = fmaxf(m, fmaxf(fabsf(e.x), fabsf(e.y)));
     }
-    m = fmaxf(m, quad_fetch<quad_pattern(1, 0, 3, 2)>(m));
-    m = fmaxf(m, quad_fetch<quad_pattern(2, 3, 0, 1)>(m));
+    m = fmaxf(m, dpp<kQuadXor1>(m, m));
+    m = fmaxf(m, dpp<kQuadXor2>(m, m));
     bool ok = (m > 0.f) && (m < INFINITY);                     // zero, NaN (fmaxf drops it: the poison below) or inf -> Jacobi
     const double sc = jacobi_prescale<double>(ok ? m : 1.f);
     double nrm2 = 0.0, poison = 0.0;
@@ -830,27 +796,6 @@ __global__ __launch_bounds__(64) void music_evd_quad_kernel(const float2 *__rest
 // Padding (N < 16): zero rows/columns -- never rotated (pivot 0 -> identity), they only travel; a
 // 16-bit mask that takes the same permutation tells the epilogue which slots are padding.
 // ---------------------------------------------------------------------------------------------
-// DPP move of a float or double: lanes whose source lies outside their 16-lane row, or whose bank is masked
-// off, receive `old`
-template <int CTRL, int BANK_MASK> __device__ __forceinline__ float dpp_row_shift(float old, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, 0xF, BANK_MASK, false));
-}
-template <int CTRL, int BANK_MASK> __device__ __forceinline__ double dpp_row_shift(double old, double v)
-{
-    const long long o = __double_as_longlong(old), x = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp((int)(o & 0xFFFFFFFFll), (int)(x & 0xFFFFFFFFll), CTRL, 0xF, BANK_MASK, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(x >> 32), CTRL, 0xF, BANK_MASK, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-template <typename T> __device__ __forceinline__ T wave_sum_t(T v)
-{
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) v += lane_fetch<T>(v, (int)((threadIdx.x & (kWave - 1)) ^ m));
-    return v;
-}
-
 // one caterpillar step: new[0]=old[0], new[2]=old[1], new[2m]=old[2m-2] (m>=2), new[2m-1]=old[2m+1] (m<=7), new[15]=old[14]
 __device__ __forceinline__ unsigned caterpillar_mask(unsigned m)
 {
@@ -915,7 +860,7 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
                 poison = fma(xr[i][j], (T)0, fma(xi[i][j], (T)0, poison));
                 xr[i][j] *= sc; xi[i][j] *= sc;
             }
-        poison = wave_sum_t<T>(poison);
+        poison = wave_butterfly_sum_fetch<T>(poison);
     }
     unsigned pad = (N >= G) ? 0u : (((1u << G) - 1u) & ~((1u << N) - 1u));      // bit k: physical slot k is padding
     auto lane_of = [](int aa, int bb) { return 16 * (aa >> 1) + 2 * bb + (aa & 1); };
@@ -931,8 +876,8 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
                 const T m = xr[i][j] * xr[i][j] + xi[i][j] * xi[i][j];
                 if (a == b && i == j) dn += m; else off += m;
             }
-        off = wave_sum_t<T>(off);
-        dn = wave_sum_t<T>(dn);
+        off = wave_butterfly_sum_fetch<T>(off);
+        dn = wave_butterfly_sum_fetch<T>(dn);
         if (!((off > Real<T>::tol * dn) && (off > Real<T>::tiny))) break;       // wave-uniform: one item per wave
 #pragma unroll 1
         for (int round = 0; round < G - 1; round++) {
@@ -976,9 +921,9 @@ __device__ __forceinline__ void evd_block16_item(const float2 *__restrict__ Ri, 
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
                     const T s0 = m[i][0], s1 = m[i][1];
-                    T n0 = dpp_row_shift<0x112, 0xF>(s0, s0);              // row_shr:2, old = own slot 0 (b = 0 keeps it)
-                    n0 = dpp_row_shift<0x112, 0x1>(n0, s1);                // bank 0 only: b = 1 <- slot 1 of b = 0
-                    const T n1 = dpp_row_shift<0x102, 0xF>(s0, s1);        // row_shl:2, old = own slot 0 (b = 7 takes it)
+                    T n0 = dpp<row_shr<2>>(s0, s0);                        // row_shr:2, old = own slot 0 (b = 0 keeps it)
+                    n0 = dpp<row_shr<2>, 0xF, 0x1>(n0, s1);                // bank 0 only: b = 1 <- slot 1 of b = 0
+                    const T n1 = dpp<row_shl<2>>(s0, s1);                  // row_shl:2, old = own slot 0 (b = 7 takes it)
                     m[i][0] = n0;
                     m[i][1] = n1;
                 }

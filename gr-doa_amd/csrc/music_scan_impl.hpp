@@ -144,6 +144,8 @@ __global__ __launch_bounds__(256) void music_scan_kernel(const T *__restrict__ c
     // values long and the missing high-order coefficients are zero, which leaves Q unchanged
     const int rec = 2 * n_ant;
     const int lane = threadIdx.x & (kWave - 1);
+    // wave_index() written out: through the call the compiler schedules this kernel's prologue differently, and the kernels
+    // are kept instruction for instruction (tools/compare_device_code.py)
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
     const int n_waves = gridDim.x * (blockDim.x / kWave);
 
@@ -571,7 +573,7 @@ __global__ __launch_bounds__(256) void music_scan_peak1_kernel(const T *__restri
         __syncthreads();
     }
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    const int wave = wave_index();
     const int n_waves = gridDim.x * (blockDim.x / kWave);
     float *lds_row = (MULTI && PEAKS) ? prow[threadIdx.x / kWave] : nullptr;
     T zr[CH][4], zi[CH][4];
@@ -610,7 +612,7 @@ __global__ __launch_bounds__(256) void music_scan_stream_kernel(const T *__restr
                                                                 float *__restrict__ spec, int P, int n_items, int n_ant)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    const int wave = wave_index();
     const int n_waves = gridDim.x * (blockDim.x / kWave);
     const int rec = 2 * n_ant;
     const int n_chunks = (P + 255) / 256;
@@ -715,7 +717,7 @@ __global__ __launch_bounds__(256) void music_scan_peak_long_kernel(const T *__re
     __shared__ float rows[4][PMAX + PMAX / 64 + 4];      // (+4: the peak pick may read position P itself)
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = threadIdx.x / kWave;
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + wib);
+    const int wave = wave_index();
     const int n_waves = gridDim.x * (blockDim.x / kWave);
     const int rec = 2 * n_ant;
     const int G = P >> 6;
@@ -815,7 +817,7 @@ __global__ __launch_bounds__(256) void music_scan_generic_kernel(const T *__rest
                                                                  int n_items, int n_ant)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    const int wave = wave_index();
     const int n_waves = gridDim.x * (blockDim.x / kWave);
     const int rec = 2 * n_ant;
     for (int item = wave; item < n_items; item += n_waves) {

@@ -2,49 +2,9 @@
 // Shared by the standalone find_local_max kernel (K5) and the fused scan+peak kernel (K4+K5).
 // Algorithm and reference citations: see find_local_max.hip.
 #pragma once
-#include "common.hpp"
-
-#include <climits>
+#include "wave_ops.hpp"
 
 namespace doa {
-
-// (value, index) ordering used for ranking: larger value first, then lower index; idx == INT_MAX
-// marks "no candidate".
-__device__ __forceinline__ bool cand_better(float v, int i, float bv, int bi)
-{
-    if (i == INT_MAX) return false;
-    if (bi == INT_MAX) return true;
-    return (v > bv) || (v == bv && i < bi);
-}
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ void argbest_step(float &v, int &i)
-{
-    // lanes of rows masked off receive their own (v, i) back, which never beats itself
-    const float ov = dpp_move<CTRL, ROW_MASK>(v, v);
-    const int oi = __builtin_amdgcn_update_dpp(i, i, CTRL, ROW_MASK, 0xF, false);
-    if (cand_better(ov, oi, v, i)) { v = ov; i = oi; }
-}
-// wave-wide best (value, index) pair, returned wave-uniform; DPP only (no LDS traffic)
-__device__ __forceinline__ void wave_argbest(float &v, int &i)
-{
-    argbest_step<0xB1, 0xF>(v, i);
-    argbest_step<0x4E, 0xF>(v, i);
-    argbest_step<0x124, 0xF>(v, i);
-    argbest_step<0x128, 0xF>(v, i);
-    argbest_step<0x142, 0xA>(v, i);
-    argbest_step<0x143, 0xC>(v, i);
-    v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-    i = __builtin_amdgcn_readlane(i, 63);
-}
-__device__ __forceinline__ int wave_sum_int(int x)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);
-    return __builtin_amdgcn_readlane(x, 63);
-}
 
 // v[j][e] = element 256*j + 4*lane + e of the vector (positions >= L hold anything).  Writes the
 // item's M peak values (rank order) and M locations (descending) — lanes 0..M-1 do the stores.
@@ -138,7 +98,7 @@ __device__ __forceinline__ void peak_pick(const float (&v)[CH][4], int lane, int
                 if (p >= 1 && p <= L - 2 && sp == 1 && s[j][e] == -1) pk |= 1ull << (4 * j + e);
             }
         }
-        n_valid = wave_sum_int(__popcll(pk));
+        n_valid = wave_allreduce_sum((int)__popcll(pk));
         // --- top-M by value (descending), ties -> lowest index ---
         const int rounds = (n_valid < M) ? n_valid : M;
         for (int r = 0; r < rounds; r++) {
@@ -161,7 +121,7 @@ __device__ __forceinline__ void peak_pick(const float (&v)[CH][4], int lane, int
 #pragma unroll
                     for (int e = 0; e < 4; e++)
                         if (((pk >> (4 * j + e)) & 1ull) && (256 * j + 4 * lane + e) < bi) before++;
-                best_list_pos = wave_sum_int(before);
+                best_list_pos = wave_allreduce_sum(before);
             }
             // owner drops the winner from its candidate set
             if (bi != INT_MAX && ((bi & 255) >> 2) == lane) pk &= ~(1ull << (4 * (bi >> 8) + (bi & 3)));
@@ -362,7 +322,7 @@ __device__ __forceinline__ void peak_pick_stream(Fetch v_at, int L, int M, const
         unsigned long long pk = neg_mine & ~((neg_mine << 1) | ((lane > 0) ? (below >> (BS - 1)) : 0ull)) & kBlockMask;
         if (lane == 0) pk &= ~1ull;
         const unsigned long long pk_all = pk;
-        n_valid = wave_sum_int(__builtin_popcountll(pk));
+        n_valid = wave_allreduce_sum(__builtin_popcountll(pk));
         const int rounds = (n_valid < M) ? n_valid : M;
         for (int r = 0; r < rounds; r++) {
             float bv = 0.f;
@@ -377,7 +337,7 @@ __device__ __forceinline__ void peak_pick_stream(Fetch v_at, int L, int M, const
                 // position of the best peak inside the ascending peak list (= #peaks before it)
                 const int rel = bi - BS * lane;
                 const unsigned long long lower = (rel >= BS) ? ~0ull : ((rel <= 0) ? 0ull : ((1ull << rel) - 1ull));
-                best_list_pos = wave_sum_int(__builtin_popcountll(pk_all & lower));
+                best_list_pos = wave_allreduce_sum(__builtin_popcountll(pk_all & lower));
             }
             if (bi != INT_MAX && (bi >> LOG_BS) == lane) pk &= ~(1ull << (bi & (BS - 1)));
             if (lane == r) { sel_idx = bi; sel_val = bv; }

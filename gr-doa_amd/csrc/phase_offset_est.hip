@@ -20,6 +20,7 @@
 #include "block_host.hpp"
 #include "kernels.hpp"
 #include "sample_loaders.hpp"
+#include "wave_ops.hpp"
 
 #include <cmath>
 
@@ -59,9 +60,6 @@ __device__ __forceinline__ float poe_arg(float2 x)
     return (__builtin_isfinite(x.x) && __builtin_isfinite(x.y)) ? a : __builtin_nanf("");
 }
 __device__ __forceinline__ float poe_diff(float a0, float2 xp) { return __fsub_rn(a0, poe_arg(xp)); }
-
-// maximum as numpy.amax takes it: a NaN sticks
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
 
 template <class L> __global__ __launch_bounds__(256) void poe_stream_kernel(PoeArgs g)
 {
@@ -116,19 +114,6 @@ template <int TCAP> __device__ __forceinline__ void poe_sample(PoeAcc<TCAP> &acc
         }
 }
 
-__device__ __forceinline__ double wave_butterfly_sum(double v)
-{
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
-__device__ __forceinline__ float wave_butterfly_nan_max(float v)
-{
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) v = nan_max(v, __shfl_xor(v, m, kWave));
-    return v;
-}
-
 // TCAP: streams the kernel is unrolled for (n_ch <= TCAP; the unused ones are skipped by wave-uniform branches)
 template <class L, int TCAP> __global__ __launch_bounds__(256) void poe_partial_kernel(PoeArgs g)
 {
@@ -164,9 +149,9 @@ template <class L, int TCAP> __global__ __launch_bounds__(256) void poe_partial_
         for (int p = 0; p < TCAP - 1; p++)
             if (p < g.n_ch - 1) {
                 PoePartial r;
-                r.sum = wave_butterfly_sum(acc.sum[p]);
-                r.re = wave_butterfly_sum(acc.re[p]);
-                r.im = wave_butterfly_sum(acc.im[p]);
+                r.sum = wave_butterfly_sum_xor(acc.sum[p]);
+                r.re = wave_butterfly_sum_xor(acc.re[p]);
+                r.im = wave_butterfly_sum_xor(acc.im[p]);
                 r.mx = wave_butterfly_nan_max(acc.mx[p]);
                 r.pad = 0.f;
                 if (lane == 0) po[p] = r;

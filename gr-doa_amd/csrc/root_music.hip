@@ -31,13 +31,6 @@ constexpr double kResidualFloor = 16.0 * 2.220446049250313e-16;
 // the other roots with cross-lane fetches for the Aberth correction, and all roots move
 // simultaneously.  The dependent chain per item is ~1/(2N-2) of the one-lane-per-item kernel's.
 // ---------------------------------------------------------------------------------------------
-template <int GR> __device__ __forceinline__ double group_max_d(double v, int lane)
-{
-#pragma unroll
-    for (int m = 1; m < GR; m <<= 1) v = fmax(v, __shfl(v, lane ^ m, kWave));
-    return v;
-}
-
 // 1/x for a finite positive double well inside the exponent range: hardware seed + two Newton steps
 // (what the compiler's IEEE division expands to, minus its scaling / fix-up instructions: ~6 instead
 // of ~18 instructions, and one reciprocal serves both parts of a complex quotient)

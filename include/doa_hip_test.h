@@ -157,6 +157,24 @@ DOA_HIP_API int doa_hip_spectrum_plan_debug(int estimator, int steering_table, i
  * the launcher's status with its error text set; DOA_ERR_INVALID_ARG for bad arguments of this entry. */
 DOA_HIP_API int doa_hip_launch_route_debug(int stage, const int *shape, int n_shape, int cu_count, char *text_out, int text_cap);
 
+/* One primitive of gr-doa_amd/csrc/wave_ops.hpp (the moves and reductions between the lanes of a wave) applied by ONE workgroup
+ * of 256 threads -- four waves -- to host data: thread t starts from in[t] and out[t] is what it holds afterwards (256 elements
+ * of the op's type; wave_argbest's element is a (float value, int32 index) pair).  n = the number of input elements: 256, and 512
+ * for the DPP move, whose `old` operand of thread t is in[256 + t].  op:
+ *   0           wave_index() (int32; the input is not read)
+ *   10 + g      group_sum<G, double>, G = 4, 8, 16 for g = 0, 1, 2;  20 + g the same in float;  30 + g group_max<G, double>;
+ *               40 + g group_or<G> (int32)
+ *   51, 52, 53  quad_rot<1>, <2>, <3>;  54 quad_sum;  55 row_sum16 (double)
+ *   60 .. 65    wave_allreduce_sum (float), wave_allreduce_sum (int32), wave_allreduce_max, wave_allreduce_min,
+ *               wave_allreduce_min_int, wave_argbest
+ *   70, 71      wave_butterfly_sum_fetch in float and double;  72 wave_butterfly_sum_xor (double);  73 wave_butterfly_nan_max
+ *   1000 + 100 t + c   dpp<control, row mask, bank mask>(old, v) on int32, float, double for t = 0, 1, 2; full masks for c = 0 .. 3:
+ *               the two quad swaps (i ^ 1, i ^ 2), row_shl:2, row_shr:2; c = 4: row_shr:2 with bank mask 0x1; c = 5: row_bcast:15
+ *               with row mask 0xA; c = 6: row_bcast:31 with row mask 0xC; c = 7: the first quad swap with row mask 0x5 and bank
+ *               mask 0x6; c = 10 + k: row_ror:k, k = 1 .. 15
+ * Returns 256, or DOA_ERR_INVALID_ARG. */
+DOA_HIP_API int doa_hip_wave_ops_debug(int op, int n, const void *in, void *out);
+
 #ifdef __cplusplus
 }
 #endif

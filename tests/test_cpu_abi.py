@@ -98,6 +98,22 @@ def test_product_never_touches_the_oracle():
     assert "oracle" not in open(HEADER).read()
 
 
+def test_cross_lane_primitives_live_in_wave_ops_only():
+    """One copy of the DPP move and of every reduction between lanes: csrc/wave_ops.hpp.  No other file reaches for the DPP
+    builtins, and the names of the copies it replaced are gone."""
+    csrc = os.path.join(ROOT, "gr-doa_amd", "csrc")
+    gone = ("dpp_move", "dpp_mov_d", "quad_fetch", "dpp_row_shift", "group_fetch", "shfl_d", "group_sum_d", "group_max_d",
+            "wave_sum_t", "wave_sum_int")
+    files = sorted(os.listdir(csrc))
+    assert "wave_ops.hpp" in files
+    for f in files:
+        text = open(os.path.join(csrc, f), errors="replace").read()
+        if f != "wave_ops.hpp":
+            assert "__builtin_amdgcn_update_dpp" not in text and "__builtin_amdgcn_mov_dpp" not in text, f
+        for name in gone:
+            assert not re.search(r"\b" + name + r"\b", text), (f, name)
+
+
 def test_sharding_helper():
     from doa import sharding
     K, ovl, n = 2048, 512, 1001
