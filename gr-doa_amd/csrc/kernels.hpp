@@ -63,6 +63,12 @@ struct MusicTables {
     void release() { d_z.release(); d_zd.release(); }
 };
 
+// The two host steps of that table, shared with WidebandTables below (music.hip).  ula_theta_grid: theta[P], the float
+// accumulator of the reference.  ula_phase_row: z_i = (cos psi_i, sin psi_i), psi_i = -2 pi cos(theta_i) d in double, for P
+// directions and an element spacing of d wavelengths; zd (doubles) and z (the same values rounded to float), either may be NULL.
+void ula_theta_grid(int P, float *theta);
+void ula_phase_row(const float *theta, int P, double d, double2 *zd, float2 *z);
+
 // coefficient record per item: [u0, Re u1, Im u1, ..., Re u_{N-1}, Im u_{N-1}, pad] = 2N floats
 inline int coef_stride(int N) { return 2 * N; }
 
@@ -193,6 +199,34 @@ int steering_table_args(const char *who, int num_ant_ele, int pspectrum_len, con
 // Q_i = sum_k record[k] T[k][i] in double, q = (float) Q, out = 1 / q, dB against the row maximum with the scan kernels' own
 // normalisation (music_scan_impl.hpp: LeanNorm / db_from_ratio).  d_q (optional): q, P floats per item.
 int launch_array_scan(const ArrayTable &t, int n_items, const void *d_full, void *d_spec, void *d_q, hipStream_t st);
+// ---- incoherent wideband MUSIC (wideband_music.hip; definition in include/doa_hip.h) --------------------------------------
+// nu_f of bin f of an fft_len-point FFT (numpy.fft.fftfreq) and the element spacing in wavelengths at that bin; pure
+inline double wideband_bin_nu(int fft_len, int bin) { return (bin < fft_len / 2 ? (double)bin : (double)bin - fft_len) / fft_len; }
+inline double wideband_bin_spacing(float norm_spacing, double rate_over_carrier, int fft_len, int bin)
+{
+    const double s = wideband_bin_nu(fft_len, bin) * rate_over_carrier;
+    return (double)norm_spacing * (1.0 + s);
+}
+// The phase table of a handle: Z[j][p] = (cos psi, sin psi), psi = -2 pi cos(theta_p) d_f at the spacing d_f of bin
+// f = (first_bin + j) mod fft_len: num_bins rows of P double2, each row by ula_phase_row on ula_theta_grid (a row at
+// rate_over_carrier = 0 is MusicTables::d_zd).
+struct WidebandTables {
+    int N = 0, M = 0, P = 0, F = 0, first_bin = 0, num_bins = 0, combine = 0;
+    DevBuf d_z;   // num_bins x P double2
+    int build(float norm_spacing, int num_targets, int num_ant_ele, int pspectrum_len, int fft_len, int first_bin, int num_bins,
+              double rate_over_carrier, int combine);
+    void release() { d_z.release(); }
+};
+// One workgroup per snapshot: the double coefficient records of its num_bins items (d_coef, item i num_bins + j, coef_stride(N)
+// doubles each) -> Q_ij by the double scan's Horner chain at row j of the table, combined over the used bins in item order
+// by t.combine (DOA_WIDEBAND_*), q = (float) Q_i, dB against the row maximum with the scan kernels' own normalisation.
+// d_weights (optional): n x num_bins floats, NULL = all ones.  d_counts (optional): n x num_bins int32, the counts the records
+// were made with; NULL = every record is for t.M sources.  A bin is used if 0 < w < +inf and (with counts) 1 <= c <= N - 1;
+// a usable weight with c == 0 skips the bin, with any other c the snapshot has status 2.  d_q (optional): q, P floats per
+// snapshot.  d_status (optional): int32 per snapshot, 0 ok / 1 no bin used / 2 bad count / 3 a used record not finite; a
+// status other than 0 gives NaN rows (d_spec and d_q).  The records of unused bins are not read.
+int launch_wideband_scan(const WidebandTables &t, int n_snapshots, const void *d_coef, const void *d_weights, const void *d_counts,
+                         void *d_spec, void *d_q, void *d_status, hipStream_t st);
 // diagnostics: items that left the signal-subspace fast path of K2+K3 for the Jacobi fall-back since the last reset
 long long evd_fallback_count(bool reset);
 // the calling thread's current device's counter (allocated on first use; nullptr if that fails) and, for the tests, the device

@@ -23,11 +23,9 @@ namespace doa {
 // ---------------------------------------------------------------------------------------------
 // host-side tables (constructor work of the reference block)
 // ---------------------------------------------------------------------------------------------
-int MusicTables::build(float norm_spacing_, int num_targets, int num_ant_ele, int pspectrum_len)
+void ula_theta_grid(int P, float *theta)
 {
-    N = num_ant_ele; M = num_targets; P = pspectrum_len; norm_spacing = norm_spacing_;
     // theta grid: float accumulator, sum formed in double (lib/MUSIC_lin_array_impl.cc:64-72)
-    std::vector<float> theta(P);
     theta[0] = 0.0f;
     float theta_prev = 0.0f;
     for (int ii = 1; ii < P; ii++) {
@@ -35,18 +33,29 @@ int MusicTables::build(float norm_spacing_, int num_targets, int num_ant_ele, in
         theta_prev = th;
         theta[ii] = (float)(M_PI * th / 180.0);
     }
+}
+
+void ula_phase_row(const float *theta, int P, double d, double2 *zd, float2 *z)
+{
     // amv (:98-104): a_i[n] = exp(j * (-2 pi cos(theta_i)) * loc_n), loc_n = d*0.5*(N-1-2n) (:57-61), so
     // the phase step between neighbouring elements is psi_i = -2 pi cos(theta_i) * d.  Evaluated in
     // double from the float theta grid; the reference's float roundings of the scalar, of loc_n and of
     // each phase (~2e-7 rad) are not replayed (they are part of its own fp32 error budget).
-    std::vector<float2> z(P);
-    std::vector<double2> zd(P);
-    const double d = (double)norm_spacing;
     for (int ii = 0; ii < P; ii++) {
         const double psi = -1.0 * 2 * M_PI * std::cos((double)theta[ii]) * d;
-        z[ii] = make_float2((float)std::cos(psi), (float)std::sin(psi));
-        zd[ii] = make_double2(std::cos(psi), std::sin(psi));
+        if (z) z[ii] = make_float2((float)std::cos(psi), (float)std::sin(psi));
+        if (zd) zd[ii] = make_double2(std::cos(psi), std::sin(psi));
     }
+}
+
+int MusicTables::build(float norm_spacing_, int num_targets, int num_ant_ele, int pspectrum_len)
+{
+    N = num_ant_ele; M = num_targets; P = pspectrum_len; norm_spacing = norm_spacing_;
+    std::vector<float> theta(P);
+    ula_theta_grid(P, theta.data());
+    std::vector<float2> z(P);
+    std::vector<double2> zd(P);
+    ula_phase_row(theta.data(), P, (double)norm_spacing, zd.data(), z.data());
     int rc = d_z.reserve(sizeof(float2) * (size_t)P);
     if (rc == DOA_OK) rc = d_zd.reserve(sizeof(double2) * (size_t)P);
     if (rc != DOA_OK) return rc;

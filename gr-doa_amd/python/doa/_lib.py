@@ -213,6 +213,14 @@ SIGNATURES = {
     "doa_channel_covariance_num_bins": (C.c_int, [_vp]),
     "doa_channel_covariance_work": (C.c_int, [_vp, C.c_int, _vpp, _vp, _vp]),
     "doa_channel_covariance_work_dev": (C.c_int, [_vp, C.c_int, _vpp, _vp, _vp, _vp]),
+    "doa_wideband_music_create": (_vp, [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]),
+    "doa_wideband_music_destroy": (None, [_vp]),
+    "doa_wideband_music_items_total": (C.c_longlong, [_vp]),
+    "doa_wideband_music_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_wideband_music_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "doa_wideband_music_work_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_wideband_music_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "doa_wideband_bin_spacing": (C.c_double, [C.c_float, C.c_double, C.c_int, C.c_int]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

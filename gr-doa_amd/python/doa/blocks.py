@@ -449,6 +449,85 @@ class MUSIC_lin_array(_ItemBlock):
         return int(lib.doa_MUSIC_lin_array_items_total(self._h))
 
 
+_COMBINE = {"null_mean": 0, "power_sum": 1}     # DOA_WIDEBAND_NULL_MEAN / DOA_WIDEBAND_POWER_SUM (include/doa_hip.h)
+
+
+def wideband_bin_spacing(norm_spacing, rate_over_carrier, fft_len, bin) -> float:
+    """The element spacing in wavelengths at FFT bin `bin`: float32(norm_spacing) * (1 + fftfreq(fft_len)[bin] * rate_over_carrier)
+    (doa_wideband_bin_spacing; no device)."""
+    return float(lib.doa_wideband_bin_spacing(float(norm_spacing), float(rate_over_carrier), int(fft_len), int(bin)))
+
+
+class wideband_music(_ItemBlock):
+    """doa.wideband_music(norm_spacing, num_targets, inputs, pspectrum_len, fft_len, first_bin=0, num_bins=None,
+    rate_over_carrier=0.0, combine="null_mean") — incoherent wideband MUSIC (include/doa_hip.h has the definition): one
+    spectrum per snapshot from the num_bins covariance items channel_covariance writes for it, every bin with its own noise
+    subspace and a steering vector at its own spacing in wavelengths (norm_spacing is the spacing at the carrier,
+    rate_over_carrier the sample rate divided by the carrier frequency).  combine: "null_mean" for sources that occupy every
+    used bin, "power_sum" for bins that hold different sources.  Not a block of the reference.
+    Items: input [n * num_bins, inputs**2] complex64, item i * num_bins + j = bin (first_bin + j) mod fft_len of snapshot i;
+    weights (optional) [n, num_bins] float32, a bin with a weight that is not positive and finite is skipped; output
+    [n, pspectrum_len] float32 and an optional int32 status per snapshot.  noutput_items counts snapshots."""
+
+    _destroy = staticmethod(lib.doa_wideband_music_destroy)
+
+    def __init__(self, norm_spacing, num_targets, inputs, pspectrum_len, fft_len, first_bin=0, num_bins=None,
+                 rate_over_carrier=0.0, combine="null_mean"):
+        super().__init__()
+        self.norm_spacing, self.num_targets = float(norm_spacing), int(num_targets)
+        self.num_ant_ele, self.pspectrum_len = int(inputs), int(pspectrum_len)
+        self.fft_len, self.first_bin = int(fft_len), int(first_bin)
+        self.num_bins = self.fft_len if num_bins is None else int(num_bins)
+        self.rate_over_carrier = float(rate_over_carrier)
+        if isinstance(combine, str):
+            if combine.lower() not in _COMBINE:
+                raise ValueError(f"unknown combine rule {combine!r} (null_mean or power_sum)")
+            combine = _COMBINE[combine.lower()]
+        self.combine = int(combine)
+        self._h = check_handle(lib.doa_wideband_music_create(self.norm_spacing, self.num_targets, self.num_ant_ele,
+                                                             self.pspectrum_len, self.fft_len, self.first_bin, self.num_bins,
+                                                             self.rate_over_carrier, self.combine), "wideband_music")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_F32, self.pspectrum_len), (_I32, 1)]
+
+    def bin_spacings(self) -> np.ndarray:
+        """The element spacing in wavelengths at every selected bin, in item order."""
+        sel = (self.first_bin + np.arange(self.num_bins)) % self.fft_len
+        return np.array([wideband_bin_spacing(self.norm_spacing, self.rate_over_carrier, self.fft_len, f) for f in sel])
+
+    def _weights(self, weights, n) -> C.c_void_p:
+        return C.c_void_p(0) if weights is None else self._items_in(weights, _F32, n, self.num_bins)
+
+    def work(self, noutput_items, input_items, output_items, weights=None) -> int:
+        """output_items[0]: the spectra; output_items[1] (optional): the status words."""
+        n = int(noutput_items)
+        return check(lib.doa_wideband_music_work(self._h, n, self._items_in(input_items[0], _C64, n * self.num_bins, self.num_ant_ele ** 2),
+                                                 self._weights(weights, n), self._items_out(output_items[0], _F32, n, self.pspectrum_len),
+                                                 self._opt_out(output_items, 1, _I32, n, 1)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_weights_ptr=None, d_q_ptr=None, d_status_ptr=None, stream=None) -> int:
+        return check(lib.doa_wideband_music_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _opt_ptr(d_weights_ptr),
+                                                     _dev_ptr(d_out_ptr), _opt_ptr(d_q_ptr), _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+    def work_counts(self, noutput_items, input_items, counts, output_items, weights=None) -> int:
+        """work with a source count PER ITEM (int32 [n * num_bins], source_count's output) in place of num_targets: a count of 0
+        skips the bin, a count outside 0..inputs-1 gives the snapshot status 2 and a NaN row."""
+        n = int(noutput_items)
+        return check(lib.doa_wideband_music_work_counts(self._h, n, self._items_in(input_items[0], _C64, n * self.num_bins, self.num_ant_ele ** 2),
+                                                        self._items_in(counts, _I32, n * self.num_bins, 1), self._weights(weights, n),
+                                                        self._items_out(output_items[0], _F32, n, self.pspectrum_len),
+                                                        self._opt_out(output_items, 1, _I32, n, 1)))
+
+    def work_dev_counts(self, noutput_items, d_in_ptr, d_counts_ptr, d_out_ptr, d_weights_ptr=None, d_q_ptr=None, d_status_ptr=None,
+                        stream=None) -> int:
+        return check(lib.doa_wideband_music_work_dev_counts(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _opt_ptr(d_counts_ptr),
+                                                            _opt_ptr(d_weights_ptr), _dev_ptr(d_out_ptr), _opt_ptr(d_q_ptr),
+                                                            _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+    def nout_items_total(self) -> int:
+        return int(lib.doa_wideband_music_items_total(self._h))
+
+
 class find_local_max(_ItemBlock):
     """doa.find_local_max(num_max_vals, vector_len, x_min, x_max) — gr::sync_block with two
     outputs (reference lib/find_local_max_impl.cc:47-71)."""

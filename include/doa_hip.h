@@ -998,6 +998,68 @@ DOA_HIP_API int doa_channel_covariance_work_dev(doa_channel_covariance_t *h, int
                                                 void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * wideband_music — incoherent wideband MUSIC on a uniform linear array (Wax, Shan and Kailath 1984): ONE spectrum per
+ *   snapshot from the covariance items of all its frequency bins, for an emitter that fills many bins (a modem, a radar,
+ *   a noise source).  Every bin gets its own noise subspace and a steering vector at that bin's own element spacing in
+ *   wavelengths, and the null spectra are combined over the bins.  The chain is channel_covariance -> [source_count ->]
+ *   wideband_music -> find_local_max.  Not a block of the reference.
+ * The definition, one for every entry (tests/wideband_ref.py restates it in numpy).
+ *   Parameters: norm_spacing d (the spacing in wavelengths AT THE CARRIER, held as float32 as in MUSIC_lin_array),
+ *   num_targets M, num_ant_ele N, pspectrum_len P; fft_len F, first_bin, num_bins nb: the selection as
+ *   doa_channel_covariance_set_bins makes it, item i nb + j = bin f_j = (first_bin + j) mod F of snapshot i;
+ *   rate_over_carrier rho = sample rate / carrier frequency (0: every bin at the carrier's spacing); combine.
+ *       nu_f     = f / F for f < F/2, else f / F - 1          (numpy.fft.fftfreq, channel_covariance's bin frequencies)
+ *       d_f      = double(float(d)) (1 + nu_f rho)            the element spacing in wavelengths at bin f
+ *       psi_j,p  = -2 pi cos(theta_p) d_fj                    theta: the float-accumulated grid of MUSIC_lin_array
+ *       Q_ij(p)  = Re(a^H P_N a),  a_n = exp(i psi_j,p (N - 1 - 2n) / 2),  P_N = the noise projector of item (i, j) for M
+ *                  sources (the *_counts entries: for the item's own count c_ij); everything but theta in double.
+ *   A bin is USED when 0 < w_ij < +inf (weights: optional n x nb floats, NULL = all ones) and, in the *_counts entries,
+ *   1 <= c_ij <= N - 1.  A bin whose weight is not usable is skipped whatever its count; with a usable weight a count of 0
+ *   skips the bin and any other count outside 1..N-1 gives the snapshot status 2.  The item of a bin that is not used may
+ *   hold anything, NaN included, and does not change a bit of the output.  Combined in double over the used bins in item order:
+ *       DOA_WIDEBAND_NULL_MEAN   Q_i(p) = sum_j w_ij Q_ij(p) / sum_j w_ij          for sources that occupy every used bin
+ *       DOA_WIDEBAND_POWER_SUM   Q_i(p) = sum_j w_ij / sum_j (w_ij / Q_ij(p))      for bins that hold different sources
+ *   (the mean of the null spectra is tilted by bins that hold only some of the sources; the sum of the pseudo-spectra
+ *   1 / Q_ij is ruled by its luckiest bin when all bins hold the same sources.)
+ *   Output: q = (float) Q_i(p); the row is 10 log10(out / max out), out = 1 / q, with MUSIC_lin_array's normalisation and
+ *   tie rule, so the maximum is exactly 0 dB and find_local_max follows unchanged.
+ *   Status (optional port, one int32 per snapshot): 0 ok; 1 no bin used; 2 a count outside 0..N-1; 3 the coefficient record
+ *   of a used bin is not finite (2 wins over 3).  A status other than 0 gives an all-NaN row (and q row) and leaves the
+ *   other snapshots as they are.  A row does not depend on noutput_items, on the snapshot's position in the call or on its
+ *   neighbours.
+ * create validates before the device is looked for: 0 < M < N <= DOA_MAX_ANT_ELE, 0 < d <= 0.5, 1 <= P <= 16384, F one of
+ *   16, 32, 64, 128, 256, 0 <= first_bin < F, 1 <= nb <= F, rho finite and >= 0, every selected bin's d_f in (0, 0.5] (the
+ *   message names the bin), combine 0 or 1.  doa_wideband_bin_spacing is d_f itself (pure, no device; NaN for a bin outside
+ *   0..F-1).
+ * noutput_items counts snapshots.  cov_items: noutput_items * nb column-major N x N gr_complex items; counts: noutput_items
+ *   * nb int32.  work_dev is two launches on the caller's stream, the eigen stage of MUSIC_lin_array over all items and one
+ *   scan that evaluates all bins of a snapshot in registers; d_q_out (optional): q, P floats per snapshot.  Internal
+ *   precision 64 only: a handle created while the process default is 32 returns DOA_ERR_UNSUPPORTED from its work entries.
+ *   The host work returns with its stream synchronised whether it worked or not.
+ * --------------------------------------------------------------------------------------------- */
+#define DOA_WIDEBAND_NULL_MEAN 0
+#define DOA_WIDEBAND_POWER_SUM 1
+typedef struct doa_wideband_music doa_wideband_music_t;
+
+DOA_HIP_API doa_wideband_music_t *doa_wideband_music_create(float norm_spacing, int num_targets, int num_ant_ele,
+                                                            int pspectrum_len, int fft_len, int first_bin, int num_bins,
+                                                            double rate_over_carrier, int combine);
+DOA_HIP_API void doa_wideband_music_destroy(doa_wideband_music_t *h);
+DOA_HIP_API long long doa_wideband_music_items_total(const doa_wideband_music_t *h);
+DOA_HIP_API int doa_wideband_music_work(doa_wideband_music_t *h, int noutput_items, const void *cov_items,
+                                        const float *weights, void *spectrum_out, void *status_out);
+DOA_HIP_API int doa_wideband_music_work_dev(doa_wideband_music_t *h, int noutput_items, const void *d_cov_items,
+                                            const void *d_weights, void *d_spectrum_out, void *d_q_out,
+                                            void *d_status_out, void *hip_stream);
+DOA_HIP_API int doa_wideband_music_work_counts(doa_wideband_music_t *h, int noutput_items, const void *cov_items,
+                                               const void *counts, const float *weights, void *spectrum_out,
+                                               void *status_out);
+DOA_HIP_API int doa_wideband_music_work_dev_counts(doa_wideband_music_t *h, int noutput_items, const void *d_cov_items,
+                                                   const void *d_counts, const void *d_weights, void *d_spectrum_out,
+                                                   void *d_q_out, void *d_status_out, void *hip_stream);
+DOA_HIP_API double doa_wideband_bin_spacing(float norm_spacing, double rate_over_carrier, int fft_len, int bin);
+
+/* ---------------------------------------------------------------------------------------------
  * sim_source — the signal front end of the simulation flowgraphs as one generator
  *   (reference apps/run_MUSIC_lin_array_simulation.py:66-74 array manifold, :204-210 sig_source_c +
  *   noise_source_c per source -> add -> multiply_matrix_cc):
