@@ -227,6 +227,21 @@ struct WidebandTables {
 // status other than 0 gives NaN rows (d_spec and d_q).  The records of unused bins are not read.
 int launch_wideband_scan(const WidebandTables &t, int n_snapshots, const void *d_coef, const void *d_weights, const void *d_counts,
                          void *d_spec, void *d_q, void *d_status, hipStream_t st);
+// ---- coherent focusing (focus_covariance.hip; definition in include/doa_hip.h) --------------------------------------------
+// The focusing table of a handle: num_bins matrices of N x N double2, row-major per matrix (T_j[a][b] at (j N + a) N + b).
+struct FocusTables {
+    int N = 0, num_bins = 0;
+    DevBuf d_t;
+    // matrices: HOST pointer, num_bins N N complex doubles in that layout
+    int build(int num_ant_ele, int num_bins, const double *matrices);
+    void release() { d_t.release(); }
+};
+// One wave per snapshot: out_i = sum_j w_ij T_j H(R_ij) T_j^H / sum_j w_ij over the used bins (0 < w < +inf), in double,
+// rounded once.  d_items: n x num_bins column-major N x N float2 items (8-byte aligned); d_weights (optional): n x num_bins
+// floats, NULL = all ones; d_out: n items, exactly Hermitian, must not overlap d_items (not checked); d_status (optional):
+// int32 per snapshot, 0 ok / 1 no bin used / 3 a used item not finite; a status other than 0 gives an all-NaN item.
+int launch_focus_covariance(const FocusTables &t, int n_snapshots, const void *d_items, const void *d_weights, void *d_out,
+                            void *d_status, hipStream_t st);
 // diagnostics: items that left the signal-subspace fast path of K2+K3 for the Jacobi fall-back since the last reset
 long long evd_fallback_count(bool reset);
 // the calling thread's current device's counter (allocated on first use; nullptr if that fails) and, for the tests, the device

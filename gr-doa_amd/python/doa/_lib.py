@@ -221,6 +221,12 @@ SIGNATURES = {
     "doa_wideband_music_work_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "doa_wideband_music_work_dev_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "doa_wideband_bin_spacing": (C.c_double, [C.c_float, C.c_double, C.c_int, C.c_int]),
+    "doa_rss_focusing_matrices": (C.c_int, [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _vp, C.c_double, _vp]),
+    "doa_focus_covariance_create": (_vp, [C.c_int, C.c_int, _vp]),
+    "doa_focus_covariance_destroy": (None, [_vp]),
+    "doa_focus_covariance_items_total": (C.c_longlong, [_vp]),
+    "doa_focus_covariance_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_focus_covariance_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

@@ -528,6 +528,73 @@ class wideband_music(_ItemBlock):
         return int(lib.doa_wideband_music_items_total(self._h))
 
 
+def rss_focusing_matrices(norm_spacing, inputs, fft_len, focus_angles, first_bin=0, num_bins=None, rate_over_carrier=0.0,
+                          regularization=1e-3) -> np.ndarray:
+    """The [num_bins, inputs, inputs] complex128 focusing table of a uniform linear array for focus_covariance, by
+    rotational-signal-subspace focusing: T_j is the unitary polar factor of A_0 A_j^H + regularization * J * I, with A_0 / A_j
+    the steering matrices of the J focus angles (degrees) at the carrier's spacing and at the spacing of bin
+    (first_bin + j) mod fft_len (doa_rss_focusing_matrices, include/doa_hip.h; host only, no device needed).  [j, a, b] is
+    T_j[a, b].  A fan over the field of view serves a first pass; the estimates and a few degrees either side of each a second."""
+    ang = np.ascontiguousarray(focus_angles, dtype=np.float64).reshape(-1)
+    n, f = int(inputs), int(fft_len)
+    nb = f if num_bins is None else int(num_bins)
+    out = np.empty((max(nb, 0), max(n, 0), max(n, 0)), dtype=np.complex128)
+    check(lib.doa_rss_focusing_matrices(float(norm_spacing), n, f, int(first_bin), nb, float(rate_over_carrier), ang.size, _vp(ang),
+                                        float(regularization), _vp(out)))
+    return out
+
+
+class focus_covariance(_ItemBlock):
+    """doa.focus_covariance(inputs, num_bins, matrices) — coherent wideband focusing (include/doa_hip.h has the definition):
+    one focused covariance item per snapshot, sum_j w_j T_j H(R_j) T_j^H / sum_j w_j over the num_bins covariance items
+    channel_covariance writes for it.  matrices: [num_bins, inputs, inputs] complex128, [j, a, b] = T_j[a, b]
+    (rss_focusing_matrices builds one for a uniform linear array; for_ula does both); the table belongs to the block, not to a
+    snapshot.  The output is an ordinary covariance item for MUSIC_lin_array, capon_lin_array, rootMUSIC_linear_array,
+    esprit_linear_array, source_count or spatial_smooth, which all assume white noise: T must be unitary for that.  A source
+    and its echo, which no per-bin estimator separates, are two sources in the focused item.  Not a block of the reference.
+    Items: input [n * num_bins, inputs**2] complex64, item i * num_bins + j = bin j of snapshot i; weights (optional)
+    [n, num_bins] float32, a bin with a weight that is not positive and finite is skipped; output [n, inputs**2] complex64 and
+    an optional int32 status per snapshot (0 ok, 1 no bin used, 3 a used item not finite; not 0: a NaN item).
+    noutput_items counts snapshots."""
+
+    _destroy = staticmethod(lib.doa_focus_covariance_destroy)
+
+    def __init__(self, inputs, num_bins, matrices):
+        super().__init__()
+        self.num_ant_ele, self.num_bins = int(inputs), int(num_bins)
+        t = None if matrices is None else np.ascontiguousarray(matrices, dtype=np.complex128)
+        if t is not None and t.size != max(self.num_bins, 0) * max(self.num_ant_ele, 0) ** 2:
+            raise ValueError(f"matrices holds {t.size} entries, not num_bins * inputs**2 = {self.num_bins} * {self.num_ant_ele}**2")
+        self.matrices = t
+        self._h = check_handle(lib.doa_focus_covariance_create(self.num_ant_ele, self.num_bins,
+                                                               C.c_void_p(0) if t is None else _vp(t)), "focus_covariance")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_C64, self.num_ant_ele ** 2), (_I32, 1)]
+
+    @classmethod
+    def for_ula(cls, norm_spacing, inputs, fft_len, focus_angles, first_bin=0, num_bins=None, rate_over_carrier=0.0,
+                regularization=1e-3):
+        """The block for a uniform linear array with the table of rss_focusing_matrices (same arguments)."""
+        t = rss_focusing_matrices(norm_spacing, inputs, fft_len, focus_angles, first_bin, num_bins, rate_over_carrier, regularization)
+        return cls(inputs, t.shape[0], t)
+
+    def work(self, noutput_items, input_items, output_items, weights=None) -> int:
+        """output_items[0]: the focused items; output_items[1] (optional): the status words."""
+        n = int(noutput_items)
+        w = C.c_void_p(0) if weights is None else self._items_in(weights, _F32, n, self.num_bins)
+        return check(lib.doa_focus_covariance_work(self._h, n, self._items_in(input_items[0], _C64, n * self.num_bins, self.num_ant_ele ** 2),
+                                                   w, self._items_out(output_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                   self._opt_out(output_items, 1, _I32, n, 1)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_weights_ptr=None, d_status_ptr=None, stream=None) -> int:
+        """d_out_ptr must not overlap d_in_ptr."""
+        return check(lib.doa_focus_covariance_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _opt_ptr(d_weights_ptr),
+                                                       _dev_ptr(d_out_ptr), _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+    def nout_items_total(self) -> int:
+        return int(lib.doa_focus_covariance_items_total(self._h))
+
+
 class find_local_max(_ItemBlock):
     """doa.find_local_max(num_max_vals, vector_len, x_min, x_max) — gr::sync_block with two
     outputs (reference lib/find_local_max_impl.cc:47-71)."""

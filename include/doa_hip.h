@@ -1060,6 +1060,70 @@ DOA_HIP_API int doa_wideband_music_work_dev_counts(doa_wideband_music_t *h, int 
 DOA_HIP_API double doa_wideband_bin_spacing(float norm_spacing, double rate_over_carrier, int fft_len, int bin);
 
 /* ---------------------------------------------------------------------------------------------
+ * focus_covariance — coherent wideband focusing (the coherent signal-subspace method, CSSM: Wang and Kaveh 1985): ONE
+ *   focused covariance item per snapshot from the covariance items of all its frequency bins.  Where wideband_music keeps
+ *   one subspace per bin, a focusing matrix T_j per bin maps the bin's steering vectors onto the carrier's, and the
+ *   transformed items are averaged.  A source and its echo are rank one in every bin (no per-bin estimator can separate
+ *   them), but the echo's phase turns across the band, so the average has rank two.  The output is an ordinary covariance
+ *   item: MUSIC_lin_array, capon_lin_array, rootMUSIC_linear_array, esprit_linear_array, source_count, spatial_smooth and
+ *   find_local_max follow unchanged, over n items instead of n * nb.  The chain is channel_covariance -> focus_covariance ->
+ *   any of them.  Not a block of the reference.
+ * The definition, one for every entry (tests/focus_ref.py restates it in numpy).  Snapshot i, bins j < nb, items R_ij
+ *   (item i nb + j, column-major N x N gr_complex), optional weights w_ij (n x nb floats, NULL = all ones), the handle's
+ *   table of nb matrices T_j (N x N complex double):
+ *       used_ij : 0 < w_ij < +inf
+ *       R_i     = sum_{j used} w_ij T_j H(R_ij) T_j^H / sum_{j used} w_ij
+ *   H(R) is R's upper triangle with the real part of its diagonal, completed Hermitian: what the eigen stage and
+ *   spatial_smooth read; the lower triangle and the diagonal's imaginary parts may hold anything.  The arithmetic is in
+ *   double and the result is rounded once to gr_complex.  The output is exactly Hermitian: the imaginary parts on the
+ *   diagonal are +0.0 and out[b,a] is bit for bit the conjugate of out[a,b].  The item of a bin that is not used may hold
+ *   anything, NaN included, and does not change a bit of the output.
+ *   Status (optional port, one int32 per snapshot, wideband_music's numbers): 0 ok; 1 no bin used; 3 a used bin's item (the
+ *   part H reads) is not finite.  A status other than 0 gives an all-NaN item and leaves the other snapshots as they are; a
+ *   NaN item is never an error return.  A snapshot's output bits do not depend on noutput_items, on its position in the
+ *   call or on the stream.
+ * TABLE LAYOUT: matrices[(j N + a) N + b] = T_j[a][b], ROW-MAJOR per matrix, re then im (numpy: a C-ordered [nb, N, N]
+ *   complex128 array).  The table belongs to the handle, not to a snapshot: it is uploaded once at create.
+ * create validates before the device is looked for: 2 <= N <= DOA_MAX_ANT_ELE, 1 <= nb <= 256 (channel_covariance's
+ *   largest fft_len), matrices not NULL and every entry finite.  A table need NOT be unitary (a measured or otherwise
+ *   non-unitary focusing table is the caller's business), but MUSIC, Root-MUSIC, ESPRIT and MDL behind the block assume
+ *   white noise, which only a unitary T keeps white.
+ * noutput_items counts snapshots: the input is noutput_items * nb items, the output noutput_items items.  work_dev is one
+ *   launch on the caller's stream.  d_out must not overlap d_cov_items (not checked).  Internal precision 64 only: a handle
+ *   created while the process default is 32 returns DOA_ERR_UNSUPPORTED from its work entries.  The host work returns with
+ *   its stream synchronised whether it worked or not.
+ *
+ * doa_rss_focusing_matrices (pure, no device) builds the table for a uniform linear array by rotational-signal-subspace
+ *   focusing (Hung and Kaveh 1988), regularised so that it is unique.  With J = n_focus focus angles theta_k (degrees),
+ *   A_d[n][k] = exp(i psi_k (N - 1 - 2n) / 2), psi_k = -2 pi cos(theta_k) d (wideband_music's steering vector),
+ *   d_0 = double(float(norm_spacing)) and d_j = doa_wideband_bin_spacing of bin (first_bin + j) mod fft_len:
+ *       B_j = A_{d_0} A_{d_j}^H + regularization J I
+ *       T_j = the unitary polar factor of B_j (U V^H of its singular value decomposition)
+ *   which is the unitary T that minimises |A_{d_0} - T A_{d_j}|^2 + regularization J |I - T|^2 (Frobenius norms).  Without
+ *   the second term fewer angles than elements leave T arbitrary on the complement of the steering vectors; with it the
+ *   carrier's bin gives the identity.  The polar factor is found by the scaled Newton iteration X <- (g X + (g X)^-H) / 2.
+ *   Refused (DOA_ERR_INVALID_ARG, doa_last_error says why): N outside 2..DOA_MAX_ANT_ELE, norm_spacing outside (0, 0.5],
+ *   fft_len not one of 16..256, a selection outside the FFT, rate_over_carrier not finite or < 0, n_focus < 1, an angle that
+ *   is not finite, a selected bin whose d_j is outside (0, 0.5] (the message names the bin), regularization not positive
+ *   and finite, NULL pointers.  matrices_out: nb N N complex doubles in the table layout above.
+ *   Choosing the angles: a fan over the field of view (as many as elements) for a first pass; then the first pass's
+ *   estimates and a few degrees either side of each.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct doa_focus_covariance doa_focus_covariance_t;
+
+DOA_HIP_API int doa_rss_focusing_matrices(float norm_spacing, int num_ant_ele, int fft_len, int first_bin, int num_bins,
+                                          double rate_over_carrier, int n_focus, const double *focus_angles_deg,
+                                          double regularization, double *matrices_out);
+DOA_HIP_API doa_focus_covariance_t *doa_focus_covariance_create(int num_ant_ele, int num_bins, const double *matrices);
+DOA_HIP_API void doa_focus_covariance_destroy(doa_focus_covariance_t *h);
+DOA_HIP_API long long doa_focus_covariance_items_total(const doa_focus_covariance_t *h);
+DOA_HIP_API int doa_focus_covariance_work(doa_focus_covariance_t *h, int noutput_items, const void *cov_items,
+                                          const float *weights, void *focused_items, void *status_out);
+DOA_HIP_API int doa_focus_covariance_work_dev(doa_focus_covariance_t *h, int noutput_items, const void *d_cov_items,
+                                              const void *d_weights, void *d_focused_items, void *d_status_out,
+                                              void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
  * sim_source — the signal front end of the simulation flowgraphs as one generator
  *   (reference apps/run_MUSIC_lin_array_simulation.py:66-74 array manifold, :204-210 sig_source_c +
  *   noise_source_c per source -> add -> multiply_matrix_cc):
