@@ -242,6 +242,23 @@ struct FocusTables {
 // int32 per snapshot, 0 ok / 1 no bin used / 3 a used item not finite; a status other than 0 gives an all-NaN item.
 int launch_focus_covariance(const FocusTables &t, int n_snapshots, const void *d_items, const void *d_weights, void *d_out,
                             void *d_status, hipStream_t st);
+// ---- difference co-array (coarray_covariance.hip; definition in include/doa_hip.h) ----------------------------------------
+// The pair list of a layout, built once on the host: for every lag l < Lv the entries of the item's upper triangle that
+// make up s[l], in the definition's order.  pair[k] = (row + col N) of the entry read, | kCoarrayConj if H[a,b] is its
+// conjugate (a > b); the pairs of lag l are pair[start[l] .. start[l+1]).  At most N (N - 1) / 2 + N = 136 entries.
+constexpr int kCoarrayMaxPairs = DOA_MAX_ANT_ELE * (DOA_MAX_ANT_ELE + 1) / 2;
+constexpr unsigned short kCoarrayConj = 0x8000;
+struct CoarrayTables {
+    int N = 0, Lv = 0, mode = 0;
+    // device: [0 .. kCoarrayMaxPairs) the pairs, then start[0 .. DOA_MAX_ANT_ELE], all unsigned short
+    DevBuf d_pairs;
+    // positions: N distinct integers (validated by the caller); Lv <= the contiguous size
+    int build(const int *positions, int num_ant_ele, int virtual_size, int mode);
+    void release() { d_pairs.release(); }
+};
+// n_items column-major N x N items (upper triangle read) -> Lv x Lv items, exactly Hermitian.  d_out must not overlap d_R (not
+// checked).  16-byte loads and stores when both pointers are 16-byte aligned, 8-byte ones otherwise: the same bits either way.
+int launch_coarray_covariance(const CoarrayTables &t, int n_items, const void *d_R, void *d_out, hipStream_t st);
 // diagnostics: items that left the signal-subspace fast path of K2+K3 for the Jacobi fall-back since the last reset
 long long evd_fallback_count(bool reset);
 // the calling thread's current device's counter (allocated on first use; nullptr if that fails) and, for the tests, the device

@@ -10,17 +10,18 @@
 // elements of its item along one diagonal -- about one double addition per byte moved, so the kernel is traffic-bound.  A
 // 256-thread workgroup takes a TILE of consecutive items (at most kTileBytes of input, an even number of items so that every
 // tile starts on a 16-byte boundary), stages it in LDS with coalesced 16-byte loads (the next tile's loads are already in
-// flight: SmoothStage), and each thread then produces PAIRS of consecutive elements of the tile's contiguous output range
+// flight: ItemTileStage, item_tile.hpp), and each thread then produces PAIRS of consecutive elements of the tile's contiguous output range
 // (items * S^2 gr_complex): one 16-byte store per pair.  A lower-triangle element is computed as its mirror and conjugated, so
 // nothing is exchanged between threads after the staging.
 // Grid-stride over tiles.  The 8-byte form (either base pointer not 16-byte aligned) differs in the width of the global
 // loads and stores only.
 #include "kernels.hpp"
+#include "item_tile.hpp"
 
 namespace doa {
 
-constexpr int kSmoothTileBytes = 8192;
-constexpr int kSmoothThreads = 256;
+constexpr int kSmoothTileBytes = kItemTileBytes;
+constexpr int kSmoothThreads = kItemTileThreads;
 
 struct SmoothArgs {
     const float2 *in;
@@ -66,45 +67,6 @@ __device__ __forceinline__ float2 smooth_element(const float2 *tile, const Smoot
     return make_float2(re, row > col ? -im : im);
 }
 
-// A tile on its way from global memory to LDS: the loads of the NEXT tile are issued before the current one is worked on and
-// wait in these registers (kSmoothTileBytes / 256 threads = 32 B per thread), so a workgroup has two tiles in flight with one
-// tile of LDS.  (Native vector members: as HIP float4 members the compiler kept the struct in memory and moved it to LDS.)
-static_assert(kSmoothTileBytes == 2 * (int)sizeof(float4) * kSmoothThreads, "SmoothStage holds two 16-byte loads per thread");
-template <bool V16> struct SmoothStage {
-    doa_f32x4 v0, v1;
-    float tail_re, tail_im;
-    __device__ __forceinline__ void load(const float2 *src, int n_in)
-    {
-        const int q = threadIdx.x;
-        if constexpr (V16) {
-            const doa_f32x4 *src4 = reinterpret_cast<const doa_f32x4 *>(src);
-            if (q < n_in / 2) v0 = src4[q];
-            if (q + kSmoothThreads < n_in / 2) v1 = src4[q + kSmoothThreads];
-            if ((n_in & 1) && q == 0) { tail_re = src[n_in - 1].x; tail_im = src[n_in - 1].y; }
-        } else {
-            if (q < n_in) { v0.x = src[q].x; v0.y = src[q].y; }
-            if (q + kSmoothThreads < n_in) { v0.z = src[q + kSmoothThreads].x; v0.w = src[q + kSmoothThreads].y; }
-            if (q + 2 * kSmoothThreads < n_in) { v1.x = src[q + 2 * kSmoothThreads].x; v1.y = src[q + 2 * kSmoothThreads].y; }
-            if (q + 3 * kSmoothThreads < n_in) { v1.z = src[q + 3 * kSmoothThreads].x; v1.w = src[q + 3 * kSmoothThreads].y; }
-        }
-    }
-    __device__ __forceinline__ void put(float2 *tile, int n_in) const
-    {
-        const int q = threadIdx.x;
-        if constexpr (V16) {
-            doa_f32x4 *tile4 = reinterpret_cast<doa_f32x4 *>(tile);
-            if (q < n_in / 2) tile4[q] = v0;
-            if (q + kSmoothThreads < n_in / 2) tile4[q + kSmoothThreads] = v1;
-            if ((n_in & 1) && q == 0) tile[n_in - 1] = make_float2(tail_re, tail_im);
-        } else {
-            if (q < n_in) tile[q] = make_float2(v0.x, v0.y);
-            if (q + kSmoothThreads < n_in) tile[q + kSmoothThreads] = make_float2(v0.z, v0.w);
-            if (q + 2 * kSmoothThreads < n_in) tile[q + 2 * kSmoothThreads] = make_float2(v1.x, v1.y);
-            if (q + 3 * kSmoothThreads < n_in) tile[q + 3 * kSmoothThreads] = make_float2(v1.z, v1.w);
-        }
-    }
-};
-
 template <bool V16>
 __global__ __launch_bounds__(kSmoothThreads) void spatial_smooth_kernel(SmoothArgs a)
 {
@@ -114,7 +76,7 @@ __global__ __launch_bounds__(kSmoothThreads) void spatial_smooth_kernel(SmoothAr
     const int n_tiles = (a.n_items + a.tile_items - 1) / a.tile_items;
     auto items_of = [&](int tb) { const int left = a.n_items - tb * a.tile_items; return left < a.tile_items ? left : a.tile_items; };
     // (tile tb starts at item tb * tile_items, an even number: 16-byte aligned in both arrays when their bases are)
-    SmoothStage<V16> stage;
+    ItemTileStage<V16> stage;
     int tb = blockIdx.x;
     if (tb < n_tiles) stage.load(a.in + (size_t)tb * a.tile_items * nn, items_of(tb) * nn);
     for (; tb < n_tiles; tb += gridDim.x) {
@@ -154,7 +116,7 @@ int launch_spatial_smooth(int N, int S, int fb, int n_items, const void *d_R, vo
     SmoothArgs a;
     a.in = static_cast<const float2 *>(d_R); a.out = static_cast<float2 *>(d_Rs);
     a.N = N; a.S = S; a.L = N - S + 1; a.fb = fb; a.n_items = n_items;
-    a.tile_items = (kSmoothTileBytes / (int)sizeof(float2) / (N * N)) & ~1;     // 4 (N = 16) .. 256 (N = 2), even
+    a.tile_items = item_tile_items(N * N);                       // 4 (N = 16) .. 256 (N = 2), even
     a.by_ss = GroupSplit::make(S * S); a.by_s = GroupSplit::make(S);
     a.inv_l = 1.0 / a.L;
     int blocks = (n_items + a.tile_items - 1) / a.tile_items;

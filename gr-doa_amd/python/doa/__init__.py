@@ -32,6 +32,11 @@ Root-MUSIC, ESPRIT, Capon and the source count on wideband data:
 
     blk = doa.focus_covariance.for_ula(norm_spacing, inputs, fft_len, focus_angles, rate_over_carrier=fs / fc)
 
+the difference co-array of a sparse linear array (minimum-redundancy, nested, coprime), for more sources than antennas: the
+covariance item of a virtual uniform array for MUSIC_lin_array, rootMUSIC_linear_array and esprit_linear_array:
+
+    blk = doa.coarray_covariance((0, 1, 4, 6))            # 4 antennas -> blk.virtual_size == 7: up to 6 sources
+
 least-squares ESPRIT, the grid-free estimate without a polynomial or a search (also `root_pipeline.set_estimator("esprit")`):
 
     blk = doa.esprit_linear_array(norm_spacing, num_targets, inputs)
@@ -59,7 +64,7 @@ Importing fails if gr-doa_amd/lib/libdoa_hip.so has not been built; constructing
 no HIP device is usable.  There is no CPU fallback.
 """
 from ._lib import DoaError, LIB_PATH, last_error  # noqa: F401
-from .blocks import (autocorrelate, channel_covariance, wideband_music, wideband_bin_spacing, focus_covariance, rss_focusing_matrices, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, rootMUSIC_linear_array,  # noqa: F401
+from .blocks import (autocorrelate, channel_covariance, wideband_music, wideband_bin_spacing, focus_covariance, rss_focusing_matrices, coarray_covariance, coarray_lags, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, rootMUSIC_linear_array,  # noqa: F401
                      esprit_linear_array,
                      MUSIC_array, capon_array, planar_steering_table, uca_positions, planar_steering_grid, find_local_max_2d, array_grid_debug,
                      music_pipeline, root_pipeline, root_music_pipeline, autocorrelate_sc16, music_pipeline_sc16,

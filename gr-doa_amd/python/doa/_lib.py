@@ -227,6 +227,12 @@ SIGNATURES = {
     "doa_focus_covariance_items_total": (C.c_longlong, [_vp]),
     "doa_focus_covariance_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_focus_covariance_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_coarray_lags": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "doa_coarray_covariance_create": (_vp, [_vp, C.c_int, C.c_int, C.c_int]),
+    "doa_coarray_covariance_destroy": (None, [_vp]),
+    "doa_coarray_covariance_virtual_size": (C.c_int, [_vp]),
+    "doa_coarray_covariance_work": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "doa_coarray_covariance_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

@@ -697,6 +697,70 @@ class spatial_smooth(_ItemBlock):
                                                      _dev_ptr(d_out_ptr), _stream_ptr(stream)))
 
 
+# modes of coarray_covariance (DOA_COARRAY_SMOOTHED / DOA_COARRAY_TOEPLITZ, include/doa_hip.h)
+_COARRAY_MODES = {"smoothed": 0, "toeplitz": 1}
+
+
+def _positions(positions) -> np.ndarray:
+    """Element positions as the int32 array the C entries take; anything that is not a whole number is refused here."""
+    p = np.asarray(positions).reshape(-1)
+    q = p.astype(np.int64) if p.size else np.zeros(0, np.int64)
+    if p.size and (not np.array_equal(q, p) or np.abs(q).max() >= 2 ** 31):
+        raise ValueError(f"positions must be integers (multiples of the element spacing), got {positions!r}")
+    return np.ascontiguousarray(q, dtype=_I32)
+
+
+def coarray_lags(positions):
+    """(contiguous_size, counts) of a sparse linear array's difference co-array: the largest L such that every lag 0 .. L-1
+    occurs among positions[a] - positions[b], and the number of ordered pairs with each of those lags
+    (doa_coarray_lags, include/doa_hip.h; host only, no device needed).  coarray_covariance offers a virtual array of up to
+    min(contiguous_size, 16) elements."""
+    p = _positions(positions)
+    size = C.c_int(0)
+    check(lib.doa_coarray_lags(_vp(p), p.size, C.byref(size), C.c_void_p(0)))
+    counts = np.zeros(size.value, _I32)
+    check(lib.doa_coarray_lags(_vp(p), p.size, C.byref(size), _vp(counts)))
+    return size.value, counts.tolist()
+
+
+class coarray_covariance(_ItemBlock):
+    """doa.coarray_covariance(positions, virtual_size=0, mode="smoothed") — the difference co-array of a sparse linear array
+    (include/doa_hip.h has the definition): each len(positions) x len(positions) covariance item of elements at the integer
+    positions (in units of norm_spacing, counted as MUSIC_lin_array numbers its elements) becomes the covariance item of a
+    virtual uniform array of virtual_size elements (0: as many as the layout gives, at most 16; coarray_lags tells), so that
+    MUSIC_lin_array, rootMUSIC_linear_array and esprit_linear_array created for self.virtual_size inputs find up to
+    virtual_size - 1 sources: more than there are antennas.  mode "smoothed" (positive semidefinite, T T^H / virtual_size; its
+    eigenvalues are squared, so source_count is not valid on it) or "toeplitz" (T itself, which may be indefinite).
+    Not a block of the reference."""
+
+    _destroy = staticmethod(lib.doa_coarray_covariance_destroy)
+
+    def __init__(self, positions, virtual_size=0, mode="smoothed"):
+        super().__init__()
+        self.positions = _positions(positions)
+        self.num_ant_ele = int(self.positions.size)
+        if isinstance(mode, str):
+            if mode.lower() not in _COARRAY_MODES:
+                raise ValueError(f"unknown co-array mode {mode!r} (smoothed or toeplitz)")
+            mode = _COARRAY_MODES[mode.lower()]
+        self.mode = int(mode)
+        self._h = check_handle(lib.doa_coarray_covariance_create(_vp(self.positions), self.num_ant_ele, int(virtual_size), self.mode),
+                               "coarray_covariance")
+        self.virtual_size = int(lib.doa_coarray_covariance_virtual_size(self._h))
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_C64, self.virtual_size ** 2)]
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        n = int(noutput_items)
+        return check(lib.doa_coarray_covariance_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                     self._items_out(output_items[0], _C64, n, self.virtual_size ** 2)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, stream=None) -> int:
+        """d_out_ptr must not overlap d_in_ptr."""
+        return check(lib.doa_coarray_covariance_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr),
+                                                         _dev_ptr(d_out_ptr), _stream_ptr(stream)))
+
+
 class capon_lin_array(_ItemBlock):
     """doa.capon_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0) — the Capon (minimum-variance, MVDR)
     spectrum 1 / (a^H R^-1 a) of each covariance item on MUSIC_lin_array's angle grid, in its output format (dB against the

@@ -1124,6 +1124,65 @@ DOA_HIP_API int doa_focus_covariance_work_dev(doa_focus_covariance_t *h, int nou
                                               void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * coarray_covariance — the difference co-array of a SPARSE linear array (minimum-redundancy, nested, coprime): more
+ *   sources than antennas.  Every estimator here needs num_targets < num_ant_ele.  With the N elements at integer
+ *   positions p_n (in units of norm_spacing) the covariance of uncorrelated sources depends on the lag p_a - p_b alone,
+ *   and a sparse array holds many more lags than elements: 0, 1, 4, 6 holds every lag 0..6.  Averaging the entries of
+ *   equal lag into a Hermitian Toeplitz matrix T of size Lv and squaring it gives the spatially smoothed co-array matrix
+ *   (Pal and Vaidyanathan 2010; = T^2 / Lv: Liu and Vaidyanathan 2015), which is the covariance item of a VIRTUAL
+ *   Lv-element uniform array: MUSIC_lin_array(d, M, Lv, P), rootMUSIC_linear_array, esprit_linear_array and
+ *   find_local_max follow unchanged, with M up to Lv - 1.  The chain is autocorrelate -> coarray_covariance -> any of them.
+ *   Not a block of the reference.
+ * positions: N distinct integers in any order, 2 <= N <= DOA_MAX_ANT_ELE, max - min <= 255.  positions[n] is the
+ *   position of stream n, counted as MUSIC_lin_array numbers its elements (element n of its uniform array is position n).
+ *   lag(a, b) = positions[a] - positions[b];  c_l = the number of ordered pairs with lag l;  Lc (the contiguous size) = the
+ *   largest L such that every lag 0..L-1 occurs.  virtual_size Lv: 0 means min(Lc, DOA_MAX_ANT_ELE), otherwise
+ *   2 <= Lv <= that value.  Lags beyond the first hole are not used.
+ * The definition, one for every entry (tests/coarray_ref.py restates it in numpy):
+ *   input item   column-major N x N gr_complex, as spatial_smooth takes it; ONLY THE UPPER TRIANGLE IS READ, and of the
+ *                diagonal the real part: H = the Hermitian matrix these define
+ *   output item  column-major Lv x Lv gr_complex, full and EXACTLY Hermitian: out[j,i] is bit for bit conj(out[i,j]) and
+ *                the diagonal's imaginary part is +0.0
+ *   for l = 0 .. Lv-1:
+ *     s[l] = sum (double) H[a,b] over the pairs with lag(a,b) = l,
+ *            ascending column b, then ascending row a; re and im separately; l = 0: real parts only
+ *     r[l] = s[l] * (1.0 / c_l)                      1.0 / c_l formed in double; r stays in double
+ *   T[i,j] = r[i-j] for i >= j, conj(r[j-i]) for i < j                    (row i, column j)
+ *   DOA_COARRAY_TOEPLITZ:  out[i,j] = (float) T[i,j]
+ *   DOA_COARRAY_SMOOTHED:  out[i,j] = (float)( (sum_k T[i,k] conj(T[j,k])) * (1.0 / Lv) ),  i <= j, in double; the
+ *                          mirror conjugated
+ *   In TOEPLITZ mode no product feeds an addition, so an implementation that does these operations in this order is
+ *   bit-identical to the numpy statement; the device kernel is, for either pointer alignment and any batch size.  In
+ *   SMOOTHED mode the order of the sum over k is free; every component is within 2^-23 of the item's largest component
+ *   of the double result.  With positions 0..N-1 and an exactly Toeplitz input TOEPLITZ mode returns the input.
+ *   Non-finite entries propagate by IEEE rules within their item; there is no status output.
+ * WHICH MODE.  SMOOTHED (the default) is positive semidefinite and is what MUSIC, Root-MUSIC and ESPRIT should read.
+ *   Its eigenvalues are the SQUARES of T's: source_count's MDL / AIC are not valid on it, and its float storage has half
+ *   the dynamic range in dB.  TOEPLITZ keeps the eigenvalues unsquared but can be indefinite at finite snapshot counts;
+ *   it is for callers that know that.  An order estimator for co-array items is not provided.
+ * create validates before the device is looked for and says what is wrong (doa_last_error).  output_items must NOT overlap
+ *   cov_items (not checked).  work_dev is one launch on the caller's stream; it takes 16-byte loads and stores when both
+ *   pointers are 16-byte aligned and 8-byte ones otherwise (gr_complex alignment is the minimum): the same bits either way.
+ * doa_coarray_lags (pure, no device): *contiguous_size = Lc of a layout, and counts[l] = c_l for l < Lc if counts is not
+ *   NULL (the caller provides Lc entries: call once with NULL to learn Lc; Lc <= 256).  Array designers check a layout
+ *   with it.  DOA_ERR_INVALID_ARG for NULL positions or contiguous_size, n < 1, n > DOA_MAX_ANT_ELE, duplicates or a span
+ *   above 255.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct doa_coarray_covariance doa_coarray_covariance_t;
+#define DOA_COARRAY_SMOOTHED 0
+#define DOA_COARRAY_TOEPLITZ 1
+
+DOA_HIP_API int doa_coarray_lags(const int *positions, int n, int *contiguous_size, int *counts);
+DOA_HIP_API doa_coarray_covariance_t *doa_coarray_covariance_create(const int *positions, int num_ant_ele, int virtual_size,
+                                                                    int mode);
+DOA_HIP_API void doa_coarray_covariance_destroy(doa_coarray_covariance_t *h);
+DOA_HIP_API int doa_coarray_covariance_virtual_size(const doa_coarray_covariance_t *h);
+DOA_HIP_API int doa_coarray_covariance_work(doa_coarray_covariance_t *h, int noutput_items, const void *cov_items,
+                                            void *output_items);
+DOA_HIP_API int doa_coarray_covariance_work_dev(doa_coarray_covariance_t *h, int noutput_items, const void *d_cov_items,
+                                                void *d_output_items, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
  * sim_source — the signal front end of the simulation flowgraphs as one generator
  *   (reference apps/run_MUSIC_lin_array_simulation.py:66-74 array manifold, :204-210 sig_source_c +
  *   noise_source_c per source -> add -> multiply_matrix_cc):
