@@ -308,9 +308,9 @@ template <class L> static void launch_chan(int N, bool vec2, const ChanCovArgs &
 // C ABI
 // ---------------------------------------------------------------------------------------------
 struct doa_channel_covariance : doa::BlockBase {
-    int N = 0, F = 0, lg_f = 0;
+    int N = 0, lg_f = 0;
     doa::StreamWindow win;
-    int first_bin = 0, num_bins = 0;
+    doa::BinSelection sel;                 // sel.F: the transform size
     float inv = 0.f;                       // (float)(1 / (B W2))
     doa::InputFormat fmt;
     doa::DevBuf d_table;                   // [F/2] float2 twiddles, then [F] float window
@@ -327,9 +327,8 @@ doa_channel_covariance_t *doa_channel_covariance_create(int inputs, int snapshot
         doa::set_error("channel_covariance: inputs=%d is not built into this library (1..%d are)", inputs, doa::kChanMaxInputs);
         return nullptr;
     }
-    int lg_f = 0;
-    while ((1 << lg_f) < fft_len) lg_f++;
-    if (inputs < 1 || inputs > DOA_MAX_ANT_ELE || fft_len < 16 || fft_len > doa::kChanMaxFft || (1 << lg_f) != fft_len) {
+    const int lg_f = doa::fft_len_log2(fft_len);
+    if (inputs < 1 || inputs > DOA_MAX_ANT_ELE || lg_f < 0) {
         doa::set_error("channel_covariance: invalid argument: need 1 <= inputs <= %d and fft_len 16, 32, 64, 128 or 256 "
                        "(got %d, %d)", doa::kChanMaxInputs, inputs, fft_len);
         return nullptr;
@@ -354,8 +353,8 @@ doa_channel_covariance_t *doa_channel_covariance_create(int inputs, int snapshot
         return nullptr;
     }
     return doa::create_block<doa_channel_covariance>("channel_covariance", [&](doa_channel_covariance &h) -> int {
-        h.N = inputs; h.win.K = snapshot_size; h.win.overlap = overlap_size; h.F = fft_len; h.lg_f = lg_f;
-        h.first_bin = 0; h.num_bins = fft_len;
+        h.N = inputs; h.win.K = snapshot_size; h.win.overlap = overlap_size; h.lg_f = lg_f;
+        h.sel = {fft_len, 0, fft_len};
         h.inv = (float)(1.0 / ((double)(snapshot_size / fft_len) * w2));
         // twiddles and window: built here in double, rounded once, read by every launch of the handle
         float table[doa::kChanMaxFft * 2];
@@ -395,16 +394,12 @@ int doa_channel_covariance_set_bins(doa_channel_covariance_t *h, int first_bin, 
 {
     doa::clear_error();
     if (!h) { doa::set_error("channel_covariance_set_bins: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (first_bin < 0 || first_bin >= h->F || num_bins < 1 || num_bins > h->F) {
-        doa::set_error("channel_covariance_set_bins: need 0 <= first_bin < fft_len and 1 <= num_bins <= fft_len (got %d, %d, "
-                       "fft_len %d)", first_bin, num_bins, h->F);
-        return DOA_ERR_INVALID_ARG;
-    }
-    h->first_bin = first_bin; h->num_bins = num_bins;
+    if (int rc = doa::check_bin_selection("channel_covariance_set_bins", h->sel.F, first_bin, num_bins); rc != DOA_OK) return rc;
+    h->sel.first = first_bin; h->sel.nb = num_bins;
     return DOA_OK;
 }
 
-int doa_channel_covariance_num_bins(const doa_channel_covariance_t *h) { return h ? h->num_bins : DOA_ERR_INVALID_ARG; }
+int doa_channel_covariance_num_bins(const doa_channel_covariance_t *h) { return h ? h->sel.nb : DOA_ERR_INVALID_ARG; }
 
 int doa_channel_covariance_work_dev(doa_channel_covariance_t *h, int noutput_items, const void *const *d_input_items,
                                     void *d_out_cov, void *d_out_power, void *hip_stream)
@@ -421,9 +416,9 @@ int doa_channel_covariance_work_dev(doa_channel_covariance_t *h, int noutput_ite
     g.out = static_cast<float2 *>(d_out_cov);
     g.power = static_cast<float *>(d_out_power);
     g.twiddle = h->d_table.as<float2>();
-    g.window = h->d_table.as<float>() + h->F;
-    g.K = h->win.K; g.S = h->win.step(); g.F = h->F; g.lg_f = h->lg_f; g.B = h->win.K / h->F;
-    g.first_bin = h->first_bin; g.num_bins = h->num_bins;
+    g.window = h->d_table.as<float>() + h->sel.F;
+    g.K = h->win.K; g.S = h->win.step(); g.F = h->sel.F; g.lg_f = h->lg_f; g.B = h->win.K / h->sel.F;
+    g.first_bin = h->sel.first; g.num_bins = h->sel.nb;
     g.inv = h->inv;
     g.scale = h->fmt.kernel_scale();
     // pair loads: every block of every snapshot starts on a sample pair (F is even, so only the snapshot step matters)
@@ -447,8 +442,8 @@ int doa_channel_covariance_work(doa_channel_covariance_t *h, int noutput_items, 
     const void *d_ptrs[doa::kChanMaxInputs];
     // the device copy of a stream keeps the caller's offset inside 16 bytes, so the load route follows the caller's alignment
     io.in_streams("channel_covariance_work", h->d_in, input_items, N, (size_t)h->win.input_span(noutput_items) * sb, d_ptrs, 0, sb);
-    io.out(h->d_out, out_cov, (size_t)noutput_items * h->num_bins * N * N * sizeof(float2));
-    if (out_power) io.out(h->d_power, out_power, (size_t)noutput_items * h->F * sizeof(float));
+    io.out(h->d_out, out_cov, (size_t)noutput_items * h->sel.nb * N * N * sizeof(float2));
+    if (out_power) io.out(h->d_power, out_power, (size_t)noutput_items * h->sel.F * sizeof(float));
     int rc = io.status();
     if (rc == DOA_OK)
         rc = doa_channel_covariance_work_dev(h, noutput_items, d_ptrs, h->d_out.p, out_power ? h->d_power.p : nullptr, h->stream);

@@ -23,7 +23,6 @@
 #include "wave_ops.hpp"
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <complex>
 #include <vector>
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(kWave) void focus_covariance_kernel(const float2 *_
         if (k0 + S::B < nb) stage.load(src + (size_t)(k0 + S::B) * S::NN, min(S::B, nb - k0 - S::B) * S::NN, lane);
         const int j = k0 + b;
         const float wf = (r < N && j < nb) ? (weights ? weights[item0 + j] : 1.0f) : 0.0f;
-        const bool used = wf > 0.0f && wf < INFINITY;
+        const bool used = bin_weight_used(wf);
         const double w = (double)wf;
         double tr[N], ti[N];
         if (used) {
@@ -310,10 +309,7 @@ namespace {
 int focus_args(const char *who, const doa_focus_covariance *h, int n, const void *items, const void *out)
 {
     if (int rc = doa::work_args(who, h, n, {items, out}); rc != DOA_OK) return rc;
-    if ((long long)n * h->tab.num_bins > INT_MAX) {
-        doa::set_error("%s: %d snapshots of %d bins are more items than one call takes", who, n, h->tab.num_bins);
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::snapshot_items(who, n, h->tab.num_bins); rc != DOA_OK) return rc;
     return doa::need_bits64(who, h->bits, "focusing");
 }
 
@@ -331,23 +327,13 @@ int doa_rss_focusing_matrices(float norm_spacing, int num_ant_ele, int fft_len, 
         doa::set_error("%s: need 2 <= num_ant_ele <= %d (got %d)", who, DOA_MAX_ANT_ELE, N);
         return DOA_ERR_INVALID_ARG;
     }
-    if (!(norm_spacing > 0.0f) || norm_spacing > 0.5f) {
-        doa::set_error("%s: need 0 < norm_spacing <= 0.5 (got %g)", who, (double)norm_spacing);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (fft_len != 16 && fft_len != 32 && fft_len != 64 && fft_len != 128 && fft_len != 256) {
+    if (int rc = doa::check_norm_spacing(who, norm_spacing); rc != DOA_OK) return rc;
+    if (doa::fft_len_log2(fft_len) < 0) {
         doa::set_error("%s: fft_len must be 16, 32, 64, 128 or 256 (got %d)", who, fft_len);
         return DOA_ERR_INVALID_ARG;
     }
-    if (first_bin < 0 || first_bin >= fft_len || num_bins < 1 || num_bins > fft_len) {
-        doa::set_error("%s: need 0 <= first_bin < fft_len and 1 <= num_bins <= fft_len (got %d, %d, fft_len %d)", who, first_bin,
-                       num_bins, fft_len);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (!std::isfinite(rate_over_carrier) || rate_over_carrier < 0.0) {
-        doa::set_error("%s: rate_over_carrier must be finite and >= 0 (got %g)", who, rate_over_carrier);
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int rc = doa::check_bin_selection(who, fft_len, first_bin, num_bins); rc != DOA_OK) return rc;
+    if (int rc = doa::check_rate_over_carrier(who, rate_over_carrier); rc != DOA_OK) return rc;
     if (J < 1) {
         doa::set_error("%s: need n_focus >= 1 focus angles (got %d)", who, J);
         return DOA_ERR_INVALID_ARG;
@@ -365,15 +351,8 @@ int doa_rss_focusing_matrices(float norm_spacing, int num_ant_ele, int fft_len, 
         doa::set_error("%s: regularization must be positive and finite (got %g)", who, regularization);
         return DOA_ERR_INVALID_ARG;
     }
-    for (int j = 0; j < num_bins; j++) {
-        const int f = (first_bin + j) % fft_len;
-        const double df = doa::wideband_bin_spacing(norm_spacing, rate_over_carrier, fft_len, f);
-        if (!(df > 0.0) || df > 0.5) {
-            doa::set_error("%s: the element spacing at bin %d is %g wavelengths, outside (0, 0.5] (norm_spacing %g, rate_over_carrier %g)",
-                           who, f, df, (double)norm_spacing, rate_over_carrier);
-            return DOA_ERR_INVALID_ARG;
-        }
-    }
+    const doa::BinSelection sel{fft_len, first_bin, num_bins};
+    if (int rc = doa::check_bin_spacings(who, norm_spacing, rate_over_carrier, sel); rc != DOA_OK) return rc;
     // A_d[n][k] = exp(i psi_k (N - 1 - 2n) / 2), psi_k = -2 pi cos(theta_k) d
     std::vector<double> kk(J);
     for (int k = 0; k < J; k++) kk[k] = -1.0 * 2 * M_PI * std::cos(focus_angles_deg[k] * (M_PI / 180.0));
@@ -384,7 +363,7 @@ int doa_rss_focusing_matrices(float norm_spacing, int num_ant_ele, int fft_len, 
     std::vector<doa::cplx> A0(N * J), Aj(N * J), X(N * N);
     steering((double)norm_spacing, A0);
     for (int j = 0; j < num_bins; j++) {
-        const int f = (first_bin + j) % fft_len;
+        const int f = sel.bin(j);
         steering(doa::wideband_bin_spacing(norm_spacing, rate_over_carrier, fft_len, f), Aj);
         for (int a = 0; a < N; a++)
             for (int b = 0; b < N; b++) {

@@ -1,5 +1,6 @@
 // kernels.hpp — launch entry points shared between the per-block C-ABI files and the pipeline.
 #pragma once
+#include "bin_plan.hpp"
 #include "common.hpp"
 #include "launch_routes.hpp"
 
@@ -200,20 +201,14 @@ int steering_table_args(const char *who, int num_ant_ele, int pspectrum_len, con
 // normalisation (music_scan_impl.hpp: LeanNorm / db_from_ratio).  d_q (optional): q, P floats per item.
 int launch_array_scan(const ArrayTable &t, int n_items, const void *d_full, void *d_spec, void *d_q, hipStream_t st);
 // ---- incoherent wideband MUSIC (wideband_music.hip; definition in include/doa_hip.h) --------------------------------------
-// nu_f of bin f of an fft_len-point FFT (numpy.fft.fftfreq) and the element spacing in wavelengths at that bin; pure
-inline double wideband_bin_nu(int fft_len, int bin) { return (bin < fft_len / 2 ? (double)bin : (double)bin - fft_len) / fft_len; }
-inline double wideband_bin_spacing(float norm_spacing, double rate_over_carrier, int fft_len, int bin)
-{
-    const double s = wideband_bin_nu(fft_len, bin) * rate_over_carrier;
-    return (double)norm_spacing * (1.0 + s);
-}
-// The phase table of a handle: Z[j][p] = (cos psi, sin psi), psi = -2 pi cos(theta_p) d_f at the spacing d_f of bin
-// f = (first_bin + j) mod fft_len: num_bins rows of P double2, each row by ula_phase_row on ula_theta_grid (a row at
-// rate_over_carrier = 0 is MusicTables::d_zd).
+// The phase table of a handle: Z[j][p] = (cos psi, sin psi), psi = -2 pi cos(theta_p) d_f at the spacing d_f
+// (bin_plan.hpp: wideband_bin_spacing) of bin sel.bin(j): sel.nb rows of P double2, each row by ula_phase_row on
+// ula_theta_grid (a row at rate_over_carrier = 0 is MusicTables::d_zd).
 struct WidebandTables {
-    int N = 0, M = 0, P = 0, F = 0, first_bin = 0, num_bins = 0, combine = 0;
-    DevBuf d_z;   // num_bins x P double2
-    int build(float norm_spacing, int num_targets, int num_ant_ele, int pspectrum_len, int fft_len, int first_bin, int num_bins,
+    int N = 0, M = 0, P = 0, combine = 0;
+    BinSelection sel;
+    DevBuf d_z;   // sel.nb x P double2
+    int build(float norm_spacing, int num_targets, int num_ant_ele, int pspectrum_len, const BinSelection &sel,
               double rate_over_carrier, int combine);
     void release() { d_z.release(); }
 };
@@ -221,9 +216,9 @@ struct WidebandTables {
 // doubles each) -> Q_ij by the double scan's Horner chain at row j of the table, combined over the used bins in item order
 // by t.combine (DOA_WIDEBAND_*), q = (float) Q_i, dB against the row maximum with the scan kernels' own normalisation.
 // d_weights (optional): n x num_bins floats, NULL = all ones.  d_counts (optional): n x num_bins int32, the counts the records
-// were made with; NULL = every record is for t.M sources.  A bin is used if 0 < w < +inf and (with counts) 1 <= c <= N - 1;
-// a usable weight with c == 0 skips the bin, with any other c the snapshot has status 2.  d_q (optional): q, P floats per
-// snapshot.  d_status (optional): int32 per snapshot, 0 ok / 1 no bin used / 2 bad count / 3 a used record not finite; a
+// were made with; NULL = every record is for t.M sources.  A bin is used if bin_weight_used(w) and (with counts) 1 <= c <=
+// N - 1; a usable weight with c == 0 skips the bin, with any other c the snapshot has status 2.  d_q (optional): q, P floats
+// per snapshot.  d_status (optional): int32 per snapshot, 0 ok / 1 no bin used / 2 bad count / 3 a used record not finite; a
 // status other than 0 gives NaN rows (d_spec and d_q).  The records of unused bins are not read.
 int launch_wideband_scan(const WidebandTables &t, int n_snapshots, const void *d_coef, const void *d_weights, const void *d_counts,
                          void *d_spec, void *d_q, void *d_status, hipStream_t st);
@@ -236,7 +231,7 @@ struct FocusTables {
     int build(int num_ant_ele, int num_bins, const double *matrices);
     void release() { d_t.release(); }
 };
-// One wave per snapshot: out_i = sum_j w_ij T_j H(R_ij) T_j^H / sum_j w_ij over the used bins (0 < w < +inf), in double,
+// One wave per snapshot: out_i = sum_j w_ij T_j H(R_ij) T_j^H / sum_j w_ij over the used bins (bin_weight_used), in double,
 // rounded once.  d_items: n x num_bins column-major N x N float2 items (8-byte aligned); d_weights (optional): n x num_bins
 // floats, NULL = all ones; d_out: n items, exactly Hermitian, must not overlap d_items (not checked); d_status (optional):
 // int32 per snapshot, 0 ok / 1 no bin used / 3 a used item not finite; a status other than 0 gives an all-NaN item.

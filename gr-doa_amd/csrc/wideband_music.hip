@@ -21,7 +21,6 @@
 #include "kernels.hpp"
 #include "music_scan_impl.hpp"
 
-#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -35,7 +34,7 @@ constexpr int kWbDirs = 4;          // directions per thread and step
 __device__ __forceinline__ int wb_bin_state(const float *__restrict__ w, const int *__restrict__ c, size_t item, int n_ant)
 {
     const float wf = w ? w[item] : 1.0f;
-    if (!(wf > 0.0f && wf < INFINITY)) return 0;
+    if (!bin_weight_used(wf)) return 0;
     if (!c) return 1;
     const int m = c[item];
     if (m == 0) return 0;
@@ -166,7 +165,7 @@ void launch_wideband_form(const WidebandTables &t, int n, const void *d_coef, co
 #define DOA_WB_LAUNCH(C_)                                                                                                  \
     hipLaunchKernelGGL((wideband_scan_kernel<NP, PMAX, C_>), dim3(n), dim3(kWbThreads), 0, st, (const double *)d_coef,        \
                        t.d_z.as<double2>(), (const float *)d_w, (const int *)d_counts, (float *)d_spec, (float *)d_q,         \
-                       (int *)d_status, t.P, t.num_bins, t.N)
+                       (int *)d_status, t.P, t.sel.nb, t.N)
     if (t.combine == DOA_WIDEBAND_NULL_MEAN) DOA_WB_LAUNCH(DOA_WIDEBAND_NULL_MEAN);
     else DOA_WB_LAUNCH(DOA_WIDEBAND_POWER_SUM);
 #undef DOA_WB_LAUNCH
@@ -182,15 +181,15 @@ void launch_wideband_n(const WidebandTables &t, int n, const void *d_coef, const
 
 }  // namespace
 
-int WidebandTables::build(float norm_spacing, int num_targets, int num_ant_ele, int pspectrum_len, int fft_len, int first_bin_,
-                          int num_bins_, double rate_over_carrier, int combine_)
+int WidebandTables::build(float norm_spacing, int num_targets, int num_ant_ele, int pspectrum_len, const BinSelection &sel_,
+                          double rate_over_carrier, int combine_)
 {
-    N = num_ant_ele; M = num_targets; P = pspectrum_len; F = fft_len; first_bin = first_bin_; num_bins = num_bins_; combine = combine_;
+    N = num_ant_ele; M = num_targets; P = pspectrum_len; sel = sel_; combine = combine_;
     std::vector<float> theta(P);
     ula_theta_grid(P, theta.data());
-    std::vector<double2> z((size_t)num_bins * P);
-    for (int j = 0; j < num_bins; j++)
-        ula_phase_row(theta.data(), P, wideband_bin_spacing(norm_spacing, rate_over_carrier, F, (first_bin + j) % F),
+    std::vector<double2> z((size_t)sel.nb * P);
+    for (int j = 0; j < sel.nb; j++)
+        ula_phase_row(theta.data(), P, wideband_bin_spacing(norm_spacing, rate_over_carrier, sel.F, sel.bin(j)),
                       z.data() + (size_t)j * P, nullptr);
     const size_t bytes = z.size() * sizeof(double2);
     if (int rc = d_z.reserve(bytes); rc != DOA_OK) return rc;
@@ -202,9 +201,9 @@ int launch_wideband_scan(const WidebandTables &t, int n, const void *d_coef, con
                          void *d_q, void *d_status, hipStream_t st)
 {
     if (n <= 0) return DOA_OK;
-    if (t.N < 2 || t.N > DOA_MAX_ANT_ELE || t.P < 1 || t.P > 16384 || t.num_bins < 1 || !t.d_z.p || !d_coef || !d_spec ||
+    if (t.N < 2 || t.N > DOA_MAX_ANT_ELE || t.P < 1 || t.P > 16384 || t.sel.nb < 1 || !t.d_z.p || !d_coef || !d_spec ||
         (t.combine != DOA_WIDEBAND_NULL_MEAN && t.combine != DOA_WIDEBAND_POWER_SUM)) {
-        set_error("wideband scan: bad arguments (N=%d, P=%d, %d bins, combine %d)", t.N, t.P, t.num_bins, t.combine);
+        set_error("wideband scan: bad arguments (N=%d, P=%d, %d bins, combine %d)", t.N, t.P, t.sel.nb, t.combine);
         return DOA_ERR_INVALID_ARG;
     }
     switch (scan_poly_size(t.N)) {
@@ -240,10 +239,7 @@ int wb_args(const char *who, const doa_wideband_music *h, int n, const void *cov
 {
     const int rc = counted ? doa::work_args(who, h, n, {cov, counts, spec}) : doa::work_args(who, h, n, {cov, spec});
     if (rc != DOA_OK) return rc;
-    if ((long long)n * h->tab.num_bins > INT_MAX) {
-        doa::set_error("%s: %d snapshots of %d bins are more items than one call takes", who, n, h->tab.num_bins);
-        return DOA_ERR_INVALID_ARG;
-    }
+    if (int irc = doa::snapshot_items(who, n, h->tab.sel.nb); irc != DOA_OK) return irc;
     return doa::need_bits64(who, h->bits, "the wideband scan");
 }
 
@@ -255,7 +251,7 @@ int wb_work_dev(const char *who, doa_wideband_music *h, int n, const void *d_cov
     if (n == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int items = n * h->tab.num_bins;
+    const int items = n * h->tab.sel.nb;
     const doa::EvdCounts cnt = doa::evd_counts_forced((const int *)d_counts);
     doa::SpectrumDesc d = h->desc;
     d.bits = h->bits;
@@ -277,7 +273,7 @@ int wb_work(const char *who, const char *who_dev, doa_wideband_music *h, int n, 
     doa::clear_error();
     if (int rc = wb_args(who, h, n, cov, counts, counted, spec); rc != DOA_OK) return rc;
     if (n == 0) return 0;
-    const size_t items = (size_t)n * h->tab.num_bins;
+    const size_t items = (size_t)n * h->tab.sel.nb;
     doa::HostCall io(*h);
     io.in(h->d_in, cov, items * h->tab.N * h->tab.N * sizeof(float2));
     if (weights) io.in(h->d_w, weights, items * sizeof(float));
@@ -313,36 +309,19 @@ doa_wideband_music_t *doa_wideband_music_create(float norm_spacing, int num_targ
         doa::set_error("%s: num_ant_ele=%d exceeds DOA_MAX_ANT_ELE=%d", kWho, num_ant_ele, DOA_MAX_ANT_ELE);
         return nullptr;
     }
-    if (!(norm_spacing > 0.0f) || norm_spacing > 0.5f) {
-        doa::set_error("%s: need 0 < norm_spacing <= 0.5 (got %g)", kWho, (double)norm_spacing);
-        return nullptr;
-    }
+    if (doa::check_norm_spacing(kWho, norm_spacing) != DOA_OK) return nullptr;
     if (pspectrum_len < 1 || pspectrum_len > 16384) {
         doa::set_error("%s: need 1 <= pspectrum_len <= 16384 (got %d)", kWho, pspectrum_len);
         return nullptr;
     }
-    if (fft_len != 16 && fft_len != 32 && fft_len != 64 && fft_len != 128 && fft_len != 256) {
+    if (doa::fft_len_log2(fft_len) < 0) {
         doa::set_error("%s: fft_len must be 16, 32, 64, 128 or 256 (got %d)", kWho, fft_len);
         return nullptr;
     }
-    if (first_bin < 0 || first_bin >= fft_len || num_bins < 1 || num_bins > fft_len) {
-        doa::set_error("%s: need 0 <= first_bin < fft_len and 1 <= num_bins <= fft_len (got %d, %d, fft_len %d)", kWho, first_bin,
-                       num_bins, fft_len);
-        return nullptr;
-    }
-    if (!std::isfinite(rate_over_carrier) || rate_over_carrier < 0.0) {
-        doa::set_error("%s: rate_over_carrier must be finite and >= 0 (got %g)", kWho, rate_over_carrier);
-        return nullptr;
-    }
-    for (int j = 0; j < num_bins; j++) {
-        const int f = (first_bin + j) % fft_len;
-        const double df = doa::wideband_bin_spacing(norm_spacing, rate_over_carrier, fft_len, f);
-        if (!(df > 0.0) || df > 0.5) {
-            doa::set_error("%s: the element spacing at bin %d is %g wavelengths, outside (0, 0.5] (norm_spacing %g, rate_over_carrier %g)",
-                           kWho, f, df, (double)norm_spacing, rate_over_carrier);
-            return nullptr;
-        }
-    }
+    if (doa::check_bin_selection(kWho, fft_len, first_bin, num_bins) != DOA_OK) return nullptr;
+    if (doa::check_rate_over_carrier(kWho, rate_over_carrier) != DOA_OK) return nullptr;
+    const doa::BinSelection sel{fft_len, first_bin, num_bins};
+    if (doa::check_bin_spacings(kWho, norm_spacing, rate_over_carrier, sel) != DOA_OK) return nullptr;
     if (combine != DOA_WIDEBAND_NULL_MEAN && combine != DOA_WIDEBAND_POWER_SUM) {
         doa::set_error("%s: combine must be DOA_WIDEBAND_NULL_MEAN (0) or DOA_WIDEBAND_POWER_SUM (1) (got %d)", kWho, combine);
         return nullptr;
@@ -350,7 +329,7 @@ doa_wideband_music_t *doa_wideband_music_create(float norm_spacing, int num_targ
     return doa::create_block<doa_wideband_music>(kWho, [&](doa_wideband_music &h) {
         h.desc.estimator = DOA_ESTIMATOR_MUSIC; h.desc.N = num_ant_ele; h.desc.M = num_targets; h.desc.ula = &h.ula;
         if (int rc = h.ula.build(norm_spacing, num_targets, num_ant_ele, pspectrum_len); rc != DOA_OK) return rc;
-        return h.tab.build(norm_spacing, num_targets, num_ant_ele, pspectrum_len, fft_len, first_bin, num_bins, rate_over_carrier, combine);
+        return h.tab.build(norm_spacing, num_targets, num_ant_ele, pspectrum_len, sel, rate_over_carrier, combine);
     });
 }
 void doa_wideband_music_destroy(doa_wideband_music_t *h) { doa::destroy_block(h); }

@@ -32,13 +32,23 @@ _I32 = np.int32
 _COUNT_METHODS = {"mdl": 0, "aic": 1}
 
 
+def _named(value, table, what, choices, ints=True) -> int:
+    """The C constant of a named choice: a name of `table` (any case), or with `ints` the constant itself, which is passed
+    on for the library to reject if it is none.  `what` and `choices` word the ValueError."""
+    if isinstance(value, str) and value.lower() in table:
+        return table[value.lower()]
+    if isinstance(value, str) or not ints:
+        raise ValueError(f"unknown {what} {value!r} ({choices})")
+    return int(value)
+
+
 def _count_method(method) -> int:
-    """ "mdl" / "aic" (any case), or the C constant itself; anything else is passed on for the library to reject."""
-    if isinstance(method, str):
-        if method.lower() not in _COUNT_METHODS:
-            raise ValueError(f"unknown source-count method {method!r} (mdl or aic)")
-        return _COUNT_METHODS[method.lower()]
-    return int(method)
+    return _named(method, _COUNT_METHODS, "source-count method", "mdl or aic")
+
+
+def _selected_bins(fft_len, first_bin, num_bins) -> np.ndarray:
+    """The FFT bin of every item of a snapshot, in item order: (first_bin + j) mod fft_len."""
+    return (first_bin + np.arange(num_bins)) % fft_len
 
 
 def _opt_ptr(p) -> C.c_void_p:
@@ -127,6 +137,10 @@ class _ItemBlock(_Block):
         if len(output_items) <= index or output_items[index] is None:
             return C.c_void_p(0)
         return cls._items_out(output_items[index], dtype, n, width)
+
+    def _weights(self, weights, n) -> C.c_void_p:
+        """The optional per-bin weights of a block that takes snapshots of self.num_bins bins: None is NULL."""
+        return C.c_void_p(0) if weights is None else self._items_in(weights, _F32, n, self.num_bins)
 
 
 class _StreamInput:
@@ -285,8 +299,7 @@ class channel_covariance(_StreamInput, _Block):
 
     def bin_frequencies(self, sample_rate=1.0) -> np.ndarray:
         """Centre frequency of every selected bin, in item order: fftfreq(fft_len) * sample_rate."""
-        sel = (self.first_bin + np.arange(self.num_bins())) % self.fft_len
-        return np.fft.fftfreq(self.fft_len)[sel] * float(sample_rate)
+        return np.fft.fftfreq(self.fft_len)[_selected_bins(self.fft_len, self.first_bin, self.num_bins())] * float(sample_rate)
 
     def general_work(self, noutput_items, input_items, output_items):
         """input_items[k]: stream k from its first history sample (at least input_span(noutput_items) long);
@@ -479,11 +492,7 @@ class wideband_music(_ItemBlock):
         self.fft_len, self.first_bin = int(fft_len), int(first_bin)
         self.num_bins = self.fft_len if num_bins is None else int(num_bins)
         self.rate_over_carrier = float(rate_over_carrier)
-        if isinstance(combine, str):
-            if combine.lower() not in _COMBINE:
-                raise ValueError(f"unknown combine rule {combine!r} (null_mean or power_sum)")
-            combine = _COMBINE[combine.lower()]
-        self.combine = int(combine)
+        self.combine = _named(combine, _COMBINE, "combine rule", "null_mean or power_sum")
         self._h = check_handle(lib.doa_wideband_music_create(self.norm_spacing, self.num_targets, self.num_ant_ele,
                                                              self.pspectrum_len, self.fft_len, self.first_bin, self.num_bins,
                                                              self.rate_over_carrier, self.combine), "wideband_music")
@@ -492,11 +501,8 @@ class wideband_music(_ItemBlock):
 
     def bin_spacings(self) -> np.ndarray:
         """The element spacing in wavelengths at every selected bin, in item order."""
-        sel = (self.first_bin + np.arange(self.num_bins)) % self.fft_len
-        return np.array([wideband_bin_spacing(self.norm_spacing, self.rate_over_carrier, self.fft_len, f) for f in sel])
-
-    def _weights(self, weights, n) -> C.c_void_p:
-        return C.c_void_p(0) if weights is None else self._items_in(weights, _F32, n, self.num_bins)
+        return np.array([wideband_bin_spacing(self.norm_spacing, self.rate_over_carrier, self.fft_len, f)
+                         for f in _selected_bins(self.fft_len, self.first_bin, self.num_bins)])
 
     def work(self, noutput_items, input_items, output_items, weights=None) -> int:
         """output_items[0]: the spectra; output_items[1] (optional): the status words."""
@@ -581,9 +587,8 @@ class focus_covariance(_ItemBlock):
     def work(self, noutput_items, input_items, output_items, weights=None) -> int:
         """output_items[0]: the focused items; output_items[1] (optional): the status words."""
         n = int(noutput_items)
-        w = C.c_void_p(0) if weights is None else self._items_in(weights, _F32, n, self.num_bins)
         return check(lib.doa_focus_covariance_work(self._h, n, self._items_in(input_items[0], _C64, n * self.num_bins, self.num_ant_ele ** 2),
-                                                   w, self._items_out(output_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                   self._weights(weights, n), self._items_out(output_items[0], _C64, n, self.num_ant_ele ** 2),
                                                    self._opt_out(output_items, 1, _I32, n, 1)))
 
     def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_weights_ptr=None, d_status_ptr=None, stream=None) -> int:
@@ -739,11 +744,7 @@ class coarray_covariance(_ItemBlock):
         super().__init__()
         self.positions = _positions(positions)
         self.num_ant_ele = int(self.positions.size)
-        if isinstance(mode, str):
-            if mode.lower() not in _COARRAY_MODES:
-                raise ValueError(f"unknown co-array mode {mode!r} (smoothed or toeplitz)")
-            mode = _COARRAY_MODES[mode.lower()]
-        self.mode = int(mode)
+        self.mode = _named(mode, _COARRAY_MODES, "co-array mode", "smoothed or toeplitz")
         self._h = check_handle(lib.doa_coarray_covariance_create(_vp(self.positions), self.num_ant_ele, int(virtual_size), self.mode),
                                "coarray_covariance")
         self.virtual_size = int(lib.doa_coarray_covariance_virtual_size(self._h))
@@ -1252,9 +1253,8 @@ class music_pipeline(_Pipeline):
         launch (capon_lin_array's; diagonal_loading as there) and num_targets only means "how many peaks"; an item that is
         not positive definite enough gets NaN peaks and a NaN row.  work_dev_auto is not available in Capon mode
         (doa_music_pipeline_set_estimator)."""
-        if not isinstance(estimator, str) or estimator.lower() not in _ESTIMATORS:
-            raise ValueError(f"unknown estimator {estimator!r} (music or capon)")
-        check(lib.doa_music_pipeline_set_estimator(self._h, _ESTIMATORS[estimator.lower()], float(diagonal_loading)))
+        code = _named(estimator, _ESTIMATORS, "estimator", "music or capon", ints=False)
+        check(lib.doa_music_pipeline_set_estimator(self._h, code, float(diagonal_loading)))
         self.estimator = estimator.lower()
         self.diagonal_loading = float(diagonal_loading) if self.estimator == "capon" else 0.0
 
@@ -1393,9 +1393,7 @@ class root_pipeline(_Pipeline):
         signal-subspace record and esprit_kernel takes the root finder's place (esprit_linear_array's definition and status
         codes; work() raises DoaError(DOA_ERR_NUMERIC) for any non-zero status).  K1 and the covariance output are unchanged
         (doa_root_pipeline_set_estimator)."""
-        if not isinstance(estimator, str) or estimator.lower() not in _GRIDFREE:
-            raise ValueError(f"unknown estimator {estimator!r} (root_music or esprit)")
-        check(lib.doa_root_pipeline_set_estimator(self._h, _GRIDFREE[estimator.lower()]))
+        check(lib.doa_root_pipeline_set_estimator(self._h, _named(estimator, _GRIDFREE, "estimator", "root_music or esprit", ints=False)))
         self.estimator = estimator.lower()
 
     def work_dev(self, noutput_items, d_input_ptrs, d_cov_ptr, d_angles_ptr, d_status_ptr=None, stream=None) -> int:

@@ -947,6 +947,21 @@ DOA_HIP_API int doa_write_phase_config(const char *filename, const float *values
 DOA_HIP_API int doa_write_antenna_calib(const char *filename, const float *gains, const float *phases, int n);
 
 /* ---------------------------------------------------------------------------------------------
+ * Snapshots of bins — what channel_covariance writes and wideband_music, focus_covariance and doa_rss_focusing_matrices
+ *   read.  The four sections below refer to this paragraph (the library states it once, in csrc/bin_plan.hpp).
+ *   Item order: a snapshot is nb covariance items, one per selected frequency bin; a call of n snapshots is n * nb
+ *   column-major N x N gr_complex items, item i nb + j = bin j of snapshot i.  Per-bin weights and counts are n x nb in the
+ *   same order.
+ *   Selection: fft_len F, first_bin and num_bins nb with 0 <= first_bin < F and 1 <= nb <= F; item j is FFT bin
+ *   f_j = (first_bin + j) mod F, so a selection may wrap past F - 1.  Bins are in natural FFT order: bin f is f / F cycles
+ *   per sample, bins >= F / 2 are negative frequencies.
+ *   Allowed fft_len: 16, 32, 64, 128 or 256.
+ *   Used bins: with weights w_ij (optional, NULL = all ones) bin j of snapshot i is USED when 0 < w_ij < +inf.  The item of
+ *   a bin that is not used is not read: it may hold anything, NaN included, and does not change a bit of the output.
+ *   Call size: n * nb must not exceed INT_MAX; a larger call is refused with DOA_ERR_INVALID_ARG.
+ * --------------------------------------------------------------------------------------------- */
+
+/* ---------------------------------------------------------------------------------------------
  * channel_covariance — one covariance per snapshot AND frequency bin (the Welch / Bartlett cross-spectral matrix): the
  *   front end for several narrowband emitters at different frequencies inside one captured band, which the whole-band
  *   covariance of autocorrelate mixes (an N-element array separates at most N - 1 of them).  Every (snapshot, bin) matrix
@@ -964,15 +979,14 @@ DOA_HIP_API int doa_write_antenna_calib(const char *filename, const float *gains
  *   triangle is the bitwise conjugate of the upper one, diagonal imaginary parts are +0), has no atomics in it and does
  *   not depend on noutput_items or on the item's position in the call.
  * Layouts: input_items as autocorrelate (and its set_input_format contract, sc16 bit-identical to fc32 on the widened
- *   samples).  out_cov = noutput_items * num_bins column-major N x N gr_complex matrices, item i * num_bins + j = bin
- *   (first_bin + j) mod F of snapshot i; bins in natural FFT order (bin f = f / F cycles per sample, bins >= F / 2 are
- *   negative frequencies).  out_power (optional, may be NULL) = noutput_items x F floats, ALWAYS all F bins in natural
+ *   samples).  out_cov = noutput_items snapshots of num_bins bins ("Snapshots of bins" above: item order and selection).
+ *   out_power (optional, may be NULL) = noutput_items x F floats, ALWAYS all F bins in natural
  *   order whatever the selection: power[i,f] = the float sum over p = 0..N-1, in that order, of the real diagonal of R_i,f
  *   -- 4 F bytes per snapshot to find the occupied bins with.
- * create validates before the device is looked for: 1 <= inputs <= 8 (9..16: not built into this library), fft_len one of
- *   16, 32, 64, 128, 256, snapshot_size a positive multiple of fft_len, 0 <= overlap_size < snapshot_size, a finite window
- *   with W2 > 0.  set_bins: 0 <= first_bin < F, 1 <= num_bins <= F (wrapping past F - 1), the default is all F bins; a
- *   refused call returns DOA_ERR_INVALID_ARG and leaves the handle as it was.  Downstream cost scales with num_bins.
+ * create validates before the device is looked for: 1 <= inputs <= 8 (9..16: not built into this library), an allowed
+ *   fft_len, snapshot_size a positive multiple of fft_len, 0 <= overlap_size < snapshot_size, a finite window with W2 > 0.
+ *   set_bins takes a selection; the default is all F bins; a refused call returns DOA_ERR_INVALID_ARG and leaves the handle
+ *   as it was.  Downstream cost scales with num_bins.
  * work_dev queues on the caller's stream and does nothing else.  Device streams aligned to two samples with an even
  *   snapshot_size - overlap_size take 16-byte (sc16: 8-byte) loads, any other stream aligned to one sample the scalar-load
  *   route; both do the same arithmetic in the same order.  The host work returns with its stream synchronised whether it
@@ -1005,18 +1019,17 @@ DOA_HIP_API int doa_channel_covariance_work_dev(doa_channel_covariance_t *h, int
  *   wideband_music -> find_local_max.  Not a block of the reference.
  * The definition, one for every entry (tests/wideband_ref.py restates it in numpy).
  *   Parameters: norm_spacing d (the spacing in wavelengths AT THE CARRIER, held as float32 as in MUSIC_lin_array),
- *   num_targets M, num_ant_ele N, pspectrum_len P; fft_len F, first_bin, num_bins nb: the selection as
- *   doa_channel_covariance_set_bins makes it, item i nb + j = bin f_j = (first_bin + j) mod F of snapshot i;
+ *   num_targets M, num_ant_ele N, pspectrum_len P; fft_len F, first_bin, num_bins nb: the selection the items were made
+ *   with ("Snapshots of bins" above; f_j is the bin of item j);
  *   rate_over_carrier rho = sample rate / carrier frequency (0: every bin at the carrier's spacing); combine.
  *       nu_f     = f / F for f < F/2, else f / F - 1          (numpy.fft.fftfreq, channel_covariance's bin frequencies)
  *       d_f      = double(float(d)) (1 + nu_f rho)            the element spacing in wavelengths at bin f
  *       psi_j,p  = -2 pi cos(theta_p) d_fj                    theta: the float-accumulated grid of MUSIC_lin_array
  *       Q_ij(p)  = Re(a^H P_N a),  a_n = exp(i psi_j,p (N - 1 - 2n) / 2),  P_N = the noise projector of item (i, j) for M
  *                  sources (the *_counts entries: for the item's own count c_ij); everything but theta in double.
- *   A bin is USED when 0 < w_ij < +inf (weights: optional n x nb floats, NULL = all ones) and, in the *_counts entries,
- *   1 <= c_ij <= N - 1.  A bin whose weight is not usable is skipped whatever its count; with a usable weight a count of 0
- *   skips the bin and any other count outside 1..N-1 gives the snapshot status 2.  The item of a bin that is not used may
- *   hold anything, NaN included, and does not change a bit of the output.  Combined in double over the used bins in item order:
+ *   A bin is USED by the rule of "Snapshots of bins" and, in the *_counts entries, when also 1 <= c_ij <= N - 1.  A bin
+ *   whose weight is not usable is skipped whatever its count; with a usable weight a count of 0 skips the bin and any other
+ *   count outside 1..N-1 gives the snapshot status 2.  Combined in double over the used bins in item order:
  *       DOA_WIDEBAND_NULL_MEAN   Q_i(p) = sum_j w_ij Q_ij(p) / sum_j w_ij          for sources that occupy every used bin
  *       DOA_WIDEBAND_POWER_SUM   Q_i(p) = sum_j w_ij / sum_j (w_ij / Q_ij(p))      for bins that hold different sources
  *   (the mean of the null spectra is tilted by bins that hold only some of the sources; the sum of the pseudo-spectra
@@ -1027,12 +1040,12 @@ DOA_HIP_API int doa_channel_covariance_work_dev(doa_channel_covariance_t *h, int
  *   of a used bin is not finite (2 wins over 3).  A status other than 0 gives an all-NaN row (and q row) and leaves the
  *   other snapshots as they are.  A row does not depend on noutput_items, on the snapshot's position in the call or on its
  *   neighbours.
- * create validates before the device is looked for: 0 < M < N <= DOA_MAX_ANT_ELE, 0 < d <= 0.5, 1 <= P <= 16384, F one of
- *   16, 32, 64, 128, 256, 0 <= first_bin < F, 1 <= nb <= F, rho finite and >= 0, every selected bin's d_f in (0, 0.5] (the
- *   message names the bin), combine 0 or 1.  doa_wideband_bin_spacing is d_f itself (pure, no device; NaN for a bin outside
+ * create validates before the device is looked for: 0 < M < N <= DOA_MAX_ANT_ELE, 0 < d <= 0.5, 1 <= P <= 16384, an allowed
+ *   fft_len, a selection inside it, rho finite and >= 0, every selected bin's d_f in (0, 0.5] (the message names the
+ *   bin), combine 0 or 1.  doa_wideband_bin_spacing is d_f itself (pure, no device; NaN for a bin outside
  *   0..F-1).
- * noutput_items counts snapshots.  cov_items: noutput_items * nb column-major N x N gr_complex items; counts: noutput_items
- *   * nb int32.  work_dev is two launches on the caller's stream, the eigen stage of MUSIC_lin_array over all items and one
+ * noutput_items counts snapshots (the call-size limit applies).  cov_items: noutput_items snapshots of nb bins; counts:
+ *   noutput_items * nb int32.  work_dev is two launches on the caller's stream, the eigen stage of MUSIC_lin_array over all items and one
  *   scan that evaluates all bins of a snapshot in registers; d_q_out (optional): q, P floats per snapshot.  Internal
  *   precision 64 only: a handle created while the process default is 32 returns DOA_ERR_UNSUPPORTED from its work entries.
  *   The host work returns with its stream synchronised whether it worked or not.
@@ -1068,16 +1081,14 @@ DOA_HIP_API double doa_wideband_bin_spacing(float norm_spacing, double rate_over
  *   item: MUSIC_lin_array, capon_lin_array, rootMUSIC_linear_array, esprit_linear_array, source_count, spatial_smooth and
  *   find_local_max follow unchanged, over n items instead of n * nb.  The chain is channel_covariance -> focus_covariance ->
  *   any of them.  Not a block of the reference.
- * The definition, one for every entry (tests/focus_ref.py restates it in numpy).  Snapshot i, bins j < nb, items R_ij
- *   (item i nb + j, column-major N x N gr_complex), optional weights w_ij (n x nb floats, NULL = all ones), the handle's
- *   table of nb matrices T_j (N x N complex double):
- *       used_ij : 0 < w_ij < +inf
+ * The definition, one for every entry (tests/focus_ref.py restates it in numpy).  Snapshot i, bins j < nb, items R_ij and
+ *   optional weights w_ij in the item order of "Snapshots of bins" above, its used-bin rule, the handle's table of nb
+ *   matrices T_j (N x N complex double):
  *       R_i     = sum_{j used} w_ij T_j H(R_ij) T_j^H / sum_{j used} w_ij
  *   H(R) is R's upper triangle with the real part of its diagonal, completed Hermitian: what the eigen stage and
  *   spatial_smooth read; the lower triangle and the diagonal's imaginary parts may hold anything.  The arithmetic is in
  *   double and the result is rounded once to gr_complex.  The output is exactly Hermitian: the imaginary parts on the
- *   diagonal are +0.0 and out[b,a] is bit for bit the conjugate of out[a,b].  The item of a bin that is not used may hold
- *   anything, NaN included, and does not change a bit of the output.
+ *   diagonal are +0.0 and out[b,a] is bit for bit the conjugate of out[a,b].
  *   Status (optional port, one int32 per snapshot, wideband_music's numbers): 0 ok; 1 no bin used; 3 a used bin's item (the
  *   part H reads) is not finite.  A status other than 0 gives an all-NaN item and leaves the other snapshots as they are; a
  *   NaN item is never an error return.  A snapshot's output bits do not depend on noutput_items, on its position in the
@@ -1088,7 +1099,8 @@ DOA_HIP_API double doa_wideband_bin_spacing(float norm_spacing, double rate_over
  *   largest fft_len), matrices not NULL and every entry finite.  A table need NOT be unitary (a measured or otherwise
  *   non-unitary focusing table is the caller's business), but MUSIC, Root-MUSIC, ESPRIT and MDL behind the block assume
  *   white noise, which only a unitary T keeps white.
- * noutput_items counts snapshots: the input is noutput_items * nb items, the output noutput_items items.  work_dev is one
+ * noutput_items counts snapshots (the call-size limit applies): the input is noutput_items * nb items, the output
+ *   noutput_items items.  work_dev is one
  *   launch on the caller's stream.  d_out must not overlap d_cov_items (not checked).  Internal precision 64 only: a handle
  *   created while the process default is 32 returns DOA_ERR_UNSUPPORTED from its work entries.  The host work returns with
  *   its stream synchronised whether it worked or not.
@@ -1096,14 +1108,14 @@ DOA_HIP_API double doa_wideband_bin_spacing(float norm_spacing, double rate_over
  * doa_rss_focusing_matrices (pure, no device) builds the table for a uniform linear array by rotational-signal-subspace
  *   focusing (Hung and Kaveh 1988), regularised so that it is unique.  With J = n_focus focus angles theta_k (degrees),
  *   A_d[n][k] = exp(i psi_k (N - 1 - 2n) / 2), psi_k = -2 pi cos(theta_k) d (wideband_music's steering vector),
- *   d_0 = double(float(norm_spacing)) and d_j = doa_wideband_bin_spacing of bin (first_bin + j) mod fft_len:
+ *   d_0 = double(float(norm_spacing)) and d_j = doa_wideband_bin_spacing of bin f_j of the selection:
  *       B_j = A_{d_0} A_{d_j}^H + regularization J I
  *       T_j = the unitary polar factor of B_j (U V^H of its singular value decomposition)
  *   which is the unitary T that minimises |A_{d_0} - T A_{d_j}|^2 + regularization J |I - T|^2 (Frobenius norms).  Without
  *   the second term fewer angles than elements leave T arbitrary on the complement of the steering vectors; with it the
  *   carrier's bin gives the identity.  The polar factor is found by the scaled Newton iteration X <- (g X + (g X)^-H) / 2.
  *   Refused (DOA_ERR_INVALID_ARG, doa_last_error says why): N outside 2..DOA_MAX_ANT_ELE, norm_spacing outside (0, 0.5],
- *   fft_len not one of 16..256, a selection outside the FFT, rate_over_carrier not finite or < 0, n_focus < 1, an angle that
+ *   an fft_len that is not allowed, a selection outside it, rate_over_carrier not finite or < 0, n_focus < 1, an angle that
  *   is not finite, a selected bin whose d_j is outside (0, 0.5] (the message names the bin), regularization not positive
  *   and finite, NULL pointers.  matrices_out: nb N N complex doubles in the table layout above.
  *   Choosing the angles: a fan over the field of view (as many as elements) for a first pass; then the first pass's

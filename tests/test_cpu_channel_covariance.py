@@ -14,6 +14,7 @@ import doa_oracle as oracle
 from doa import _lib
 
 import channel_covariance_ref as ref
+import test_cpu_bin_plan_refusals as refusals
 from channel_covariance_ref import BINS, THETAS, five_emitters
 
 DOA_ERR_INVALID_ARG = -1
@@ -148,9 +149,12 @@ def test_valid_create_needs_a_device_and_set_bins_refuses_bad_ranges():
     lib = _lib.lib
     assert lib.doa_channel_covariance_num_bins(h) == 64
     assert lib.doa_channel_covariance_set_bins(h, 61, 7) == 0 and lib.doa_channel_covariance_num_bins(h) == 7
-    for first, num in [(-1, 4), (64, 1), (0, 0), (0, 65), (3, -2)]:
+    recorded = refusals.load_fixture()["set_bins"]             # the texts of the library before the rule was shared
+    assert len(recorded) == len(refusals.SET_BINS) == 5
+    for first, num in refusals.SET_BINS:                        # (-1, 4), (64, 1), (0, 0), (0, 65), (3, -2)
         assert lib.doa_channel_covariance_set_bins(h, first, num) == DOA_ERR_INVALID_ARG
         assert "channel_covariance_set_bins" in _lib.last_error()
+        assert [DOA_ERR_INVALID_ARG, _lib.last_error()] == recorded[repr((first, num))]
         assert lib.doa_channel_covariance_num_bins(h) == 7           # the handle is as it was
     lib.doa_channel_covariance_destroy(h)
 
