@@ -341,11 +341,14 @@ int launch_esprit(int N, int W, float norm_spacing, int n_items, const void *d_R
 // C ABI
 // ---------------------------------------------------------------------------------------------
 #include "block_host.hpp"
+#include "gridfree_chain.hpp"
 
 struct doa_esprit_linear_array : doa::BlockBase {      // bits: the work entries need 64
     float norm_spacing = 0.f;
     int M = 0, N = 0;
-    doa::DevBuf d_in, d_out, d_rec, d_status, d_counts;
+    doa::DevBuf d_in, d_out, d_status, d_counts;
+    doa::GridfreeBufs rec;              // signal-subspace records (no status words of its own: a caller without a buffer gets none)
+    doa::GridfreeDesc desc() const { return {DOA_GRIDFREE_ESPRIT, N, M, norm_spacing, bits}; }
 };
 
 static int esprit_work_args(const char *who, doa_esprit_linear_array_t *h, int n, const void *in, const void *out, bool counted,
@@ -355,15 +358,16 @@ static int esprit_work_args(const char *who, doa_esprit_linear_array_t *h, int n
     return doa::need_bits64(who, h->bits, "ESPRIT");
 }
 
-// eigen launch with the record, then esprit_kernel
+// records for n items, then the chain on `st` (d_counts, optional: a count per item from the caller)
 static int esprit_run_dev(doa_esprit_linear_array_t *h, int n, const void *d_cov, const void *d_counts, void *d_angles, void *d_status,
                           hipStream_t st)
 {
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    int rc = h->d_rec.reserve((size_t)n * doa::subspace_record_len(h->N) * sizeof(double));
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_music_evd_record(h->N, n, d_cov, h->d_rec.p, st);
-    if (rc == DOA_OK) rc = doa::launch_esprit(h->N, h->M, h->norm_spacing, n, d_cov, h->d_rec.p, d_counts, d_angles, d_status, st);
+    const doa::GridfreeDesc d = h->desc();
+    const doa::EvdCounts counts = doa::evd_counts_forced((const int *)d_counts);
+    const doa::GridfreePlan plan = doa::gridfree_plan(d, d_counts != nullptr);
+    if (int rc = h->rec.reserve(plan, (size_t)n, false); rc != DOA_OK) return rc;
+    const int rc = doa::gridfree_run(d, n, d_cov, d_counts ? &counts : nullptr, h->rec.view(plan), d_angles, d_status, st);
     return rc == DOA_OK ? n : rc;
 }
 
@@ -385,13 +389,13 @@ static int esprit_record_debug(doa_esprit_linear_array_t *h, int n, const void *
 {
     doa::HostCall io(*h);
     io.in(h->d_in, cov, (size_t)n * h->N * h->N * sizeof(float2));
-    io.in(h->d_rec, records, (size_t)n * doa::subspace_record_len(h->N) * sizeof(double));
+    io.in(h->rec.rec, records, (size_t)n * doa::subspace_record_len(h->N) * sizeof(double));
     if (counts) io.in(h->d_counts, counts, (size_t)n * sizeof(int));
     io.out(h->d_out, angles, (size_t)n * h->M * sizeof(float));
     io.out(h->d_status, status, (size_t)n * sizeof(int));
     int rc = io.status();
     if (rc == DOA_OK)
-        rc = doa::launch_esprit(h->N, h->M, h->norm_spacing, n, h->d_in.p, h->d_rec.p, counts ? h->d_counts.p : nullptr, h->d_out.p,
+        rc = doa::launch_esprit(h->N, h->M, h->norm_spacing, n, h->d_in.p, h->rec.rec.p, counts ? h->d_counts.p : nullptr, h->d_out.p,
                                 h->d_status.p, h->stream);
     return io.finish(rc == DOA_OK ? n : rc);
 }

@@ -168,16 +168,12 @@ void doa_music_pipeline_destroy(doa_music_pipeline_t *h) { doa::PipeFront::destr
 
 int doa_music_pipeline_fuse_antenna_correction(doa_music_pipeline_t *h, const float *gains_re_im)
 {
-    doa::clear_error();
-    if (!h) return DOA_ERR_INVALID_ARG;
-    return h->fuse_antenna_correction(gains_re_im);
+    return doa::PipeFront::entry_fuse_antenna_correction(h, gains_re_im);
 }
 
 int doa_music_pipeline_set_input_format(doa_music_pipeline_t *h, int format, float scale)
 {
-    doa::clear_error();
-    if (!h) { doa::set_error("music_pipeline_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    return h->set_input_format("music_pipeline", format, scale);
+    return doa::PipeFront::entry_set_input_format(h, "music_pipeline", format, scale);
 }
 
 int doa_music_pipeline_set_stages(doa_music_pipeline_t *h, int stage_mask)
@@ -380,12 +376,7 @@ int doa_music_pipeline_work_dev_auto(doa_music_pipeline_t *h, int noutput_items,
 
 int doa_music_pipeline_set_lanes(doa_music_pipeline_t *h, int n_lanes)
 {
-    doa::clear_error();
-    if (!h || h->lanes.set_count(n_lanes) != DOA_OK) {
-        doa::set_error("music_pipeline_set_lanes: need 1 <= n_lanes <= %d", doa::PipeLanes::kMaxLanes);
-        return DOA_ERR_INVALID_ARG;
-    }
-    return DOA_OK;
+    return doa::PipeFront::entry_set_lanes(h, "music_pipeline", n_lanes);
 }
 
 // ---- work_dev_batches: groups of batches -------------------------------------------------------------------------------
@@ -490,21 +481,12 @@ int doa_music_pipeline_work_dev_batches(doa_music_pipeline_t *h, int n_batches, 
 
 int doa_music_pipeline_set_lane_streams(doa_music_pipeline_t *h, int n_lanes, void *const *hip_streams)
 {
-    doa::clear_error();
-    if (!h || n_lanes < 1 || n_lanes > doa::PipeLanes::kMaxLanes || !hip_streams) {
-        doa::set_error("music_pipeline_set_lane_streams: need 1 <= n_lanes <= %d and the streams", doa::PipeLanes::kMaxLanes);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    return h->lanes.adopt(n_lanes, hip_streams);
+    return doa::PipeFront::entry_set_lane_streams(h, "music_pipeline", n_lanes, hip_streams);
 }
 
 int doa_music_pipeline_synchronize(doa_music_pipeline_t *h)
 {
-    doa::clear_error();
-    if (!h) { doa::set_error("music_pipeline_synchronize: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    return h->lanes.synchronize();
+    return doa::PipeFront::entry_synchronize(h, "music_pipeline");
 }
 
 int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const void *const *input_items, void *cov_out,
@@ -541,16 +523,12 @@ int doa_music_pipeline_work(doa_music_pipeline_t *h, int noutput_items, const vo
 
 int doa_music_pipeline_inject_failure(doa_music_pipeline_t *h, int chunk_index)
 {
-    doa::clear_error();
-    if (!h || chunk_index < -1) { doa::set_error("music_pipeline_inject_failure: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    return h->inject_failure(chunk_index);
+    return doa::PipeFront::entry_inject_failure(h, "music_pipeline", chunk_index);
 }
 
 int doa_music_pipeline_lanes_idle(doa_music_pipeline_t *h)
 {
-    doa::clear_error();
-    if (!h) { doa::set_error("music_pipeline_lanes_idle: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    return h->lanes_idle();
+    return doa::PipeFront::entry_lanes_idle(h, "music_pipeline");
 }
 
 int doa_music_pipeline_set_internal_precision(doa_music_pipeline_t *h, int bits)

@@ -1,5 +1,5 @@
-// pipeline_front.hip — the bodies of pipeline_front.hpp that are not small: create / destroy, the front's setters and the
-// transport of the host-buffer `work` entries of the fused handles.  Host-only.
+// pipeline_front.hip — the bodies of pipeline_front.hpp that are not small: create / destroy, the front's setters, the C
+// entries the two handles share whole, and the transport of the host-buffer `work` entries of the fused handles.  Host-only.
 #include "pipeline_front.hpp"
 
 #include <cstdlib>
@@ -86,6 +86,65 @@ int PipeFront::lanes_idle()
     for (auto st : hst)
         if (st && hipStreamQuery(st) != hipSuccess) return 0;
     return lanes.idle() ? 1 : 0;
+}
+
+int PipeFront::entry_fuse_antenna_correction(PipeFront *h, const float *gains_re_im)
+{
+    clear_error();
+    if (!h) return DOA_ERR_INVALID_ARG;
+    return h->fuse_antenna_correction(gains_re_im);
+}
+
+// clears the error; a refused call: false, with "<pre>_<entry>: bad arguments" set
+static bool entry_args(bool ok, const char *pre, const char *entry)
+{
+    clear_error();
+    if (!ok) set_error("%s_%s: bad arguments", pre, entry);
+    return ok;
+}
+
+int PipeFront::entry_set_input_format(PipeFront *h, const char *pre, int format, float scale)
+{
+    if (!entry_args(h, pre, "set_input_format")) return DOA_ERR_INVALID_ARG;
+    return h->set_input_format(pre, format, scale);
+}
+
+int PipeFront::entry_set_lanes(PipeFront *h, const char *pre, int n_lanes)
+{
+    clear_error();
+    if (h && h->lanes.set_count(n_lanes) == DOA_OK) return DOA_OK;
+    set_error("%s_set_lanes: need 1 <= n_lanes <= %d", pre, PipeLanes::kMaxLanes);
+    return DOA_ERR_INVALID_ARG;
+}
+
+int PipeFront::entry_set_lane_streams(PipeFront *h, const char *pre, int n_lanes, void *const *hip_streams)
+{
+    clear_error();
+    if (!h || n_lanes < 1 || n_lanes > PipeLanes::kMaxLanes || !hip_streams) {
+        set_error("%s_set_lane_streams: need 1 <= n_lanes <= %d and the streams", pre, PipeLanes::kMaxLanes);
+        return DOA_ERR_INVALID_ARG;
+    }
+    if (int brc = bind_device(h->device); brc != DOA_OK) return brc;
+    return h->lanes.adopt(n_lanes, hip_streams);
+}
+
+int PipeFront::entry_synchronize(PipeFront *h, const char *pre)
+{
+    if (!entry_args(h, pre, "synchronize")) return DOA_ERR_INVALID_ARG;
+    if (int brc = bind_device(h->device); brc != DOA_OK) return brc;
+    return h->lanes.synchronize();
+}
+
+int PipeFront::entry_inject_failure(PipeFront *h, const char *pre, int chunk_index)
+{
+    if (!entry_args(h && chunk_index >= -1, pre, "inject_failure")) return DOA_ERR_INVALID_ARG;
+    return h->inject_failure(chunk_index);
+}
+
+int PipeFront::entry_lanes_idle(PipeFront *h, const char *pre)
+{
+    if (!entry_args(h, pre, "lanes_idle")) return DOA_ERR_INVALID_ARG;
+    return h->lanes_idle();
 }
 
 int PipeFront::host_open(const char *who, const void *const *input_items)

@@ -106,6 +106,15 @@ struct PipeFront {
     // the call finished.
     int host_open(const char *who, const void *const *input_items);
     int host_run(const char *who, int n, const void *const *input_items, const HostSection *sec, int n_sec, const HostChain &chain);
+
+    // The C entries the two handles share word for word, whole: h may be NULL, pre is "music_pipeline" / "root_pipeline".
+    static int entry_fuse_antenna_correction(PipeFront *h, const float *gains_re_im);
+    static int entry_set_input_format(PipeFront *h, const char *pre, int format, float scale);
+    static int entry_set_lanes(PipeFront *h, const char *pre, int n_lanes);
+    static int entry_set_lane_streams(PipeFront *h, const char *pre, int n_lanes, void *const *hip_streams);
+    static int entry_synchronize(PipeFront *h, const char *pre);
+    static int entry_inject_failure(PipeFront *h, const char *pre, int chunk_index);
+    static int entry_lanes_idle(PipeFront *h, const char *pre);
 };
 
 // The tail of a handle's create: device, handle, the front, then init(*h) -> DOA_OK or an error (the handle's tables and records)

@@ -454,26 +454,36 @@ int launch_root_select_counts(int N, int W, float norm_spacing, int n_items, con
 // C ABI
 // ---------------------------------------------------------------------------------------------
 #include "block_host.hpp"
+#include "gridfree_chain.hpp"
 
 struct doa_rootMUSIC_linear_array : doa::BlockBase {
     float norm_spacing = 0.f;
     int M = 0, N = 0;
-    doa::DevBuf d_in, d_out, d_coef, d_status, d_roots, d_counts;
+    doa::DevBuf d_in, d_out, d_roots, d_counts;
+    doa::GridfreeBufs rec;              // coefficient records and status words
     doa::PinnedBuf h_status;
+    doa::GridfreeDesc desc() const { return {DOA_GRIDFREE_ROOT_MUSIC, N, M, norm_spacing, bits}; }
 };
 
-// the host entries' status scan after the synchronise.  With per-item counts, status 2 (no usable count) is what the
-// caller asked for, not an error
+// the host entries' status scan after the synchronise (counted: gridfree_first_error)
 static int root_status_scan(const doa_rootMUSIC_linear_array *h, int n, bool counted)
 {
-    const int *stt = h->h_status.as<int>();
-    for (int i = 0; i < n; i++)
-        if (counted ? stt[i] == 1 : stt[i] != 0) {
-            doa::set_error("rootMUSIC_linear_array: item %d has no root strictly inside the unit circle "
-                           "(the reference raises in arma::index_min here)", i);
-            return DOA_ERR_NUMERIC;
-        }
-    return n;
+    const int bad = doa::gridfree_first_error(h->h_status.as<int>(), n, counted);
+    if (bad < 0) return n;
+    doa::set_error("rootMUSIC_linear_array: item %d has no root strictly inside the unit circle "
+                   "(the reference raises in arma::index_min here)", bad);
+    return DOA_ERR_NUMERIC;
+}
+
+// records for n items, then the chain on `st`; d_status: the caller's status words, or NULL for the handle's
+static int root_run_dev(doa_rootMUSIC_linear_array_t *h, int n, const void *d_cov, const doa::EvdCounts *counts, void *d_angles,
+                        void *d_status, hipStream_t st, void *d_roots = nullptr)
+{
+    const doa::GridfreeDesc d = h->desc();
+    const doa::GridfreePlan plan = doa::gridfree_plan(d, counts != nullptr);
+    if (int rc = h->rec.reserve(plan, (size_t)n, !d_status); rc != DOA_OK) return rc;
+    const int rc = doa::gridfree_run(d, n, d_cov, counts, h->rec.view(plan), d_angles, d_status, st, d_roots);
+    return rc == DOA_OK ? n : rc;
 }
 
 static int root_counts_args(const char *who, doa_rootMUSIC_linear_array_t *h, int n, const void *cov, const void *counts, const void *out)
@@ -516,17 +526,7 @@ int doa_rootMUSIC_linear_array_work_dev(doa_rootMUSIC_linear_array_t *h, int nou
     if (int rc = doa::work_args("rootMUSIC_linear_array_work_dev", h, noutput_items, {d_input_items0, d_output_items0}); rc != DOA_OK) return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    int rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
-    if (rc == DOA_OK) rc = h->d_status.reserve((size_t)noutput_items * sizeof(int));
-    if (rc != DOA_OK) return rc;
-    doa::EvdOut out;
-    out.coef_d = h->d_coef.as<double>();
-    rc = doa::launch_music_evd(h->N, h->M, noutput_items, d_input_items0, out, h->bits, st);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_root_music(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, d_output_items0,
-                                h->d_status.p, st);
-    return rc == DOA_OK ? noutput_items : rc;
+    return root_run_dev(h, noutput_items, d_input_items0, nullptr, d_output_items0, nullptr, static_cast<hipStream_t>(hip_stream));
 }
 
 int doa_rootMUSIC_linear_array_work(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *input_items0,
@@ -542,7 +542,7 @@ int doa_rootMUSIC_linear_array_work(doa_rootMUSIC_linear_array_t *h, int noutput
     if (rc != DOA_OK) return rc;                         // nothing is queued yet
     io.in(h->d_in, input_items0, (size_t)noutput_items * h->N * h->N * sizeof(float2));
     io.out(h->d_out, output_items0, (size_t)noutput_items * h->M * sizeof(float));
-    io.out(h->d_status, h->h_status.p, st_bytes);
+    io.out(h->rec.status, h->h_status.p, st_bytes);
     rc = io.status();
     if (rc == DOA_OK) rc = doa_rootMUSIC_linear_array_work_dev(h, noutput_items, h->d_in.p, h->d_out.p, h->stream);
     rc = io.finish(rc);
@@ -557,19 +557,9 @@ int doa_rootMUSIC_linear_array_work_dev_counts(doa_rootMUSIC_linear_array_t *h, 
         return rc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    int rc = h->d_coef.reserve((size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
-    if (rc == DOA_OK && !d_status_out) rc = h->d_status.reserve((size_t)noutput_items * sizeof(int));
-    if (rc != DOA_OK) return rc;
-    // forced-count mode: each item's record for its own noise set (a count outside 0..N-1: a NaN record, which the root
-    // kernel does not read)
-    doa::EvdOut out;
-    out.coef_d = h->d_coef.as<double>();
-    rc = doa::launch_music_evd_counts(h->N, noutput_items, d_cov_items, doa::evd_counts_forced((const int *)d_counts), out, st);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_root_music_counts(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, d_counts, d_angles_out,
-                                       d_status_out ? (void *)d_status_out : h->d_status.p, st);
-    return rc == DOA_OK ? noutput_items : rc;
+    // forced-count mode
+    const doa::EvdCounts counts = doa::evd_counts_forced((const int *)d_counts);
+    return root_run_dev(h, noutput_items, d_cov_items, &counts, d_angles_out, d_status_out, static_cast<hipStream_t>(hip_stream));
 }
 
 int doa_rootMUSIC_linear_array_work_counts(doa_rootMUSIC_linear_array_t *h, int noutput_items, const void *cov_items,
@@ -587,7 +577,7 @@ int doa_rootMUSIC_linear_array_work_counts(doa_rootMUSIC_linear_array_t *h, int 
     io.in(h->d_in, cov_items, (size_t)noutput_items * h->N * h->N * sizeof(float2));
     io.in(h->d_counts, counts, cnt_bytes);
     io.out(h->d_out, angles_out, (size_t)noutput_items * h->M * sizeof(float));
-    io.out(h->d_status, h->h_status.p, cnt_bytes);
+    io.out(h->rec.status, h->h_status.p, cnt_bytes);
     rc = io.status();
     if (rc == DOA_OK)
         rc = doa_rootMUSIC_linear_array_work_dev_counts(h, noutput_items, h->d_in.p, h->d_counts.p, h->d_out.p, nullptr, h->stream);
@@ -604,16 +594,10 @@ int doa_rootMUSIC_linear_array_debug(doa_rootMUSIC_linear_array_t *h, int noutpu
     io.in(h->d_in, input_items0, (size_t)noutput_items * h->N * h->N * sizeof(float2));
     io.out(h->d_out, output_items0, (size_t)noutput_items * h->M * sizeof(float));
     io.out(h->d_roots, roots_out, (size_t)noutput_items * (2 * h->N - 2) * sizeof(double2));
-    io.out(h->d_status, status_out, (size_t)noutput_items * sizeof(int));
-    io.out(h->d_coef, nullptr, (size_t)noutput_items * doa::coef_stride(h->N) * sizeof(double));
+    io.out(h->rec.status, status_out, (size_t)noutput_items * sizeof(int));
     int rc = io.status();
-    doa::EvdOut out;
-    out.coef_d = h->d_coef.as<double>();
-    if (rc == DOA_OK) rc = doa::launch_music_evd(h->N, h->M, noutput_items, h->d_in.p, out, h->bits, h->stream);
-    if (rc == DOA_OK)
-        rc = doa::launch_root_music(h->N, h->M, h->norm_spacing, noutput_items, h->d_coef.p, h->d_out.p, h->d_status.p,
-                                    h->stream, h->d_roots.p);
-    return io.finish(rc == DOA_OK ? noutput_items : rc);
+    if (rc == DOA_OK) rc = root_run_dev(h, noutput_items, h->d_in.p, nullptr, h->d_out.p, nullptr, h->stream, h->d_roots.p);
+    return io.finish(rc);
 }
 
 // the two select entries: roots (and counts, or NULL) up, the selection kernel alone, angles and status down
@@ -624,12 +608,12 @@ static int root_select_debug(doa_rootMUSIC_linear_array_t *h, int n, const void 
     io.in(h->d_roots, roots_in, (size_t)n * (2 * h->N - 2) * sizeof(double2));
     if (counts) io.in(h->d_counts, counts, (size_t)n * sizeof(int));
     io.out(h->d_out, output_items0, (size_t)n * h->M * sizeof(float));
-    io.out(h->d_status, status_out, (size_t)n * sizeof(int));
+    io.out(h->rec.status, status_out, (size_t)n * sizeof(int));
     int rc = io.status();
     if (rc == DOA_OK)
         rc = counts ? doa::launch_root_select_counts(h->N, h->M, h->norm_spacing, n, h->d_roots.p, h->d_counts.p, h->d_out.p,
-                                                     h->d_status.p, h->stream)
-                    : doa::launch_root_select(h->N, h->M, h->norm_spacing, n, h->d_roots.p, h->d_out.p, h->d_status.p, h->stream);
+                                                     h->rec.status.p, h->stream)
+                    : doa::launch_root_select(h->N, h->M, h->norm_spacing, n, h->d_roots.p, h->d_out.p, h->rec.status.p, h->stream);
     return io.finish(rc == DOA_OK ? n : rc);
 }
 

@@ -5,6 +5,7 @@
 // sums (double records), K6 roots + selection -- with the same entry points, lanes, detached form and error contract as
 // music_pipeline (pipeline.hip, pipeline_lanes.hpp).  Until round 4 this branch had to be driven as two block handles and
 // two calls per batch, which left it host-bound above ~20 us per 4096-snapshot step.
+#include "gridfree_chain.hpp"
 #include "pipeline_front.hpp"
 
 // the front (K1, smoothing, the host entry's transport, the lanes) is doa::PipeFront's; these are the estimator stage's
@@ -16,75 +17,59 @@ struct doa_root_pipeline : doa::PipeFront {
     // a lane's slots after the front's: coefficient records, status words nobody asked for, ESPRIT mode's signal-subspace
     // records between the eigen launch and esprit_kernel
     enum { kCoef = kFrontBufs, kStatus, kRec };
+    // what the chain runs: the estimator on the elements the eigen stage sees
+    doa::GridfreeDesc desc() const { return {estimator, elements(), M, norm_spacing, bits}; }
 };
 
 namespace {
 struct RootWs {
     void *cov;        // covariance items, for a chain whose caller does not ask for them
-    void *coef;       // double coefficient records of the chain's items
-    void *status;     // one int per item (1 = no root strictly inside the unit circle); a chain's caller may bring its own
     void *work;       // K1's piece sums (overlapping windows), or NULL
     void *smooth;     // spatial smoothing on: S * S gr_complex per item (else unused)
-    void *rec;        // ESPRIT mode: signal-subspace records of the chain's items (else unused)
+    doa::GridfreeRecords rec;   // the lane's records; status: one int per item, for a chain whose caller brings no buffer
 };
-size_t coef_bytes(const doa_root_pipeline *h, size_t items) { return items * doa::coef_stride(h->N) * sizeof(double); }
+// a lane's record slots, per item: an estimator's records at 64 bits
 // (sized for the full array: a later set_spatial_smoothing only makes the records smaller)
-size_t rec_bytes(const doa_root_pipeline *h, size_t items) { return items * doa::subspace_record_len(h->N) * sizeof(double); }
+doa::GridfreePlan slot_plan(const doa_root_pipeline *h, int estimator) { return doa::gridfree_plan(estimator, h->N, 64, false); }
 bool esprit_mode(const doa_root_pipeline *h) { return h->estimator == DOA_GRIDFREE_ESPRIT; }
 // The workspace `ln` (the handle's own, or a lane of work_dev_batches) as a chain sees it, from item `item_off` on (the host
-// entry's two copy/compute lanes write disjoint item ranges); status: the caller's buffer, or NULL for the lane's
-RootWs view(doa_root_pipeline *h, doa::PipeLane &ln, size_t item_off, void *status)
+// entry's two copy/compute lanes write disjoint item ranges)
+RootWs view(doa_root_pipeline *h, doa::PipeLane &ln, size_t item_off)
 {
     using H = doa_root_pipeline;
-    return {ln.at(H::kCov, item_off, (size_t)h->N * h->N * sizeof(float2)), ln.at(H::kCoef, item_off, coef_bytes(h, 1)),
-            status ? status : ln.at(H::kStatus, item_off, sizeof(int)), ln.buf[H::kWork].p,
-            ln.at(H::kSmooth, item_off, (size_t)h->S * h->S * sizeof(float2)), ln.at(H::kRec, item_off, rec_bytes(h, 1))};
+    const doa::GridfreePlan root = slot_plan(h, DOA_GRIDFREE_ROOT_MUSIC), esprit = slot_plan(h, DOA_GRIDFREE_ESPRIT);
+    return {ln.at(H::kCov, item_off, (size_t)h->N * h->N * sizeof(float2)), ln.buf[H::kWork].p,
+            ln.at(H::kSmooth, item_off, (size_t)h->S * h->S * sizeof(float2)),
+            {ln.at(H::kCoef, item_off, root.coef), ln.at(H::kRec, item_off, esprit.rec), ln.at(H::kStatus, item_off, root.status)}};
 }
 // Sizes `ln` for one batch with smoothing S and estimator `estimator` (a setter passes what it is about to commit);
-// need_cov / need_status: some batch brings no covariance / status buffer of its own
+// need_cov / need_status: some batch brings no covariance / status buffer of its own.  The coefficient slot is kept in
+// either mode, so that a return to Root-MUSIC reserves nothing.
 int reserve(doa_root_pipeline *h, doa::PipeLane &ln, bool need_cov, bool need_status, int S, int estimator)
 {
     using H = doa_root_pipeline;
     const size_t items = (size_t)h->max_batch;
+    const doa::GridfreePlan root = slot_plan(h, DOA_GRIDFREE_ROOT_MUSIC);
     int rc = h->reserve_front(ln, need_cov ? 1 : 0, S);
-    if (rc == DOA_OK) rc = ln.buf[H::kCoef].reserve(coef_bytes(h, items));
-    if (rc == DOA_OK && need_status) rc = ln.buf[H::kStatus].reserve(items * sizeof(int));
-    if (rc == DOA_OK && estimator == DOA_GRIDFREE_ESPRIT) rc = ln.buf[H::kRec].reserve(rec_bytes(h, items));
+    if (rc == DOA_OK) rc = ln.buf[H::kCoef].reserve(items * root.coef);
+    if (rc == DOA_OK && need_status) rc = ln.buf[H::kStatus].reserve(items * root.status);
+    if (rc == DOA_OK && estimator == DOA_GRIDFREE_ESPRIT) rc = ln.buf[H::kRec].reserve(items * slot_plan(h, estimator).rec);
     return rc;
 }
 int esprit_precision(const char *who, const doa_root_pipeline *h)
 {
-    if (!esprit_mode(h) || h->bits == 64) return DOA_OK;
-    doa::set_error("%s: ESPRIT needs internal precision 64 (handle is at %d)", who, h->bits);
-    return DOA_ERR_UNSUPPORTED;
+    return esprit_mode(h) ? doa::need_bits64(who, h->bits, "ESPRIT") : DOA_OK;
 }
 
-// K1 -> EVD -> roots for n items on `st`
-int run_chain(doa_root_pipeline *h, int n, const void *const *d_in, void *cov, void *angles, const RootWs &ws, hipStream_t st)
+// K1 -> smoothing -> eigen launch -> solver for n items on `st`; counts: work_dev_auto's estimate, or NULL; status: the
+// caller's words, or NULL for the lane's
+int run_chain(doa_root_pipeline *h, int n, const void *const *d_in, void *cov, void *angles, const doa::EvdCounts *counts,
+              void *status, const RootWs &ws, hipStream_t st)
 {
     int rc = h->run_k1(n, d_in, cov, ws.work, st);
     if (rc == DOA_OK) rc = h->run_smoothing(n, cov, ws.smooth, st);
-    if (rc != DOA_OK) return rc;
-    const int elements = h->elements();
-    if (esprit_mode(h)) {                       // the eigen launch that writes the record, then esprit_kernel
-        rc = doa::launch_music_evd_record(elements, n, cov, ws.rec, st);
-        if (rc != DOA_OK) return rc;
-        rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, ws.rec, nullptr, angles, ws.status, st);
-        return rc == DOA_OK ? n : rc;
-    }
-    doa::EvdOut out;
-    out.coef_d = (double *)ws.coef;
-    rc = doa::launch_music_evd(elements, h->M, n, cov, out, h->bits, st);
-    if (rc != DOA_OK) return rc;
-    rc = doa::launch_root_music(elements, h->M, h->norm_spacing, n, ws.coef, angles, ws.status, st);
+    if (rc == DOA_OK) rc = doa::gridfree_run(h->desc(), n, cov, counts, ws.rec, angles, status, st);
     return rc == DOA_OK ? n : rc;
-}
-// first item whose status word is set, or -1
-int first_flagged(const int *status, int n)
-{
-    for (int i = 0; i < n; i++)
-        if (status[i] != 0) return i;
-    return -1;
 }
 int numeric_error(const doa_root_pipeline *h, int item, int status)
 {
@@ -121,16 +106,12 @@ void doa_root_pipeline_destroy(doa_root_pipeline_t *h) { doa::PipeFront::destroy
 
 int doa_root_pipeline_fuse_antenna_correction(doa_root_pipeline_t *h, const float *gains_re_im)
 {
-    doa::clear_error();
-    if (!h) return DOA_ERR_INVALID_ARG;
-    return h->fuse_antenna_correction(gains_re_im);
+    return doa::PipeFront::entry_fuse_antenna_correction(h, gains_re_im);
 }
 
 int doa_root_pipeline_set_input_format(doa_root_pipeline_t *h, int format, float scale)
 {
-    doa::clear_error();
-    if (!h) { doa::set_error("root_pipeline_set_input_format: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    return h->set_input_format("root_pipeline", format, scale);
+    return doa::PipeFront::entry_set_input_format(h, "root_pipeline", format, scale);
 }
 
 int doa_root_pipeline_set_spatial_smoothing(doa_root_pipeline_t *h, int subarray_size, int forward_backward)
@@ -176,8 +157,8 @@ int doa_root_pipeline_work_dev(doa_root_pipeline_t *h, int noutput_items, const 
     if (int prc = esprit_precision("root_pipeline_work_dev", h); prc != DOA_OK) return prc;
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    const RootWs ws = view(h, h->self, 0, d_status_out);
-    return run_chain(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : ws.cov, d_angles_out, ws,
+    const RootWs ws = view(h, h->self, 0);
+    return run_chain(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : ws.cov, d_angles_out, nullptr, d_status_out, ws,
                      static_cast<hipStream_t>(hip_stream));
 }
 
@@ -197,7 +178,7 @@ int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int noutput_items, c
         doa::set_error("root_pipeline_work_dev_auto: noutput_items=%d exceeds max_batch=%d", noutput_items, h->max_batch);
         return DOA_ERR_INVALID_ARG;
     }
-    if (h->bits != 64) {
+    if (h->bits != 64) {                        // (need_bits64's rule, in this entry's own words: "need", not "needs")
         doa::set_error("root_pipeline_work_dev_auto: per-item counts need internal precision 64 (handle is at %d)", h->bits);
         return DOA_ERR_UNSUPPORTED;
     }
@@ -207,56 +188,25 @@ int doa_root_pipeline_work_dev_auto(doa_root_pipeline_t *h, int noutput_items, c
     }
     if (noutput_items == 0) return 0;
     if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const int n = noutput_items;
-    const int elements = h->elements();
-    const RootWs ws = view(h, h->self, 0, d_status_out);
-    void *cov = d_cov_out ? d_cov_out : ws.cov;
-    int rc = h->run_k1(n, d_input_items, cov, ws.work, st);
-    if (rc == DOA_OK) rc = h->run_smoothing(n, cov, ws.smooth, st);
+    const RootWs ws = view(h, h->self, 0);
     const doa::EvdCounts cnt = doa::evd_counts_estimate((int *)d_count_out, (float *)d_eig_out, h->K, method, h->M);
-    doa::EvdOut out;
-    if (rc == DOA_OK && esprit_mode(h)) {       // one estimating eigen launch (counts, eigenvalues, record), the counted ESPRIT kernel
-        out.es_rec = (double *)ws.rec;
-        rc = doa::launch_music_evd_counts(elements, n, cov, cnt, out, st);
-        if (rc == DOA_OK)
-            rc = doa::launch_esprit(elements, h->M, h->norm_spacing, n, cov, ws.rec, d_count_out, d_angles_out, ws.status, st);
-        return rc == DOA_OK ? n : rc;
-    }
-    out.coef_d = (double *)ws.coef;
-    if (rc == DOA_OK) rc = doa::launch_music_evd_counts(elements, n, cov, cnt, out, st);
-    if (rc == DOA_OK)
-        rc = doa::launch_root_music_counts(elements, h->M, h->norm_spacing, n, ws.coef, d_count_out, d_angles_out, ws.status, st);
-    return rc == DOA_OK ? n : rc;
+    return run_chain(h, noutput_items, d_input_items, d_cov_out ? d_cov_out : ws.cov, d_angles_out, &cnt, d_status_out, ws,
+                     static_cast<hipStream_t>(hip_stream));
 }
 
 int doa_root_pipeline_set_lanes(doa_root_pipeline_t *h, int n_lanes)
 {
-    doa::clear_error();
-    if (!h || h->lanes.set_count(n_lanes) != DOA_OK) {
-        doa::set_error("root_pipeline_set_lanes: need 1 <= n_lanes <= %d", doa::PipeLanes::kMaxLanes);
-        return DOA_ERR_INVALID_ARG;
-    }
-    return DOA_OK;
+    return doa::PipeFront::entry_set_lanes(h, "root_pipeline", n_lanes);
 }
 
 int doa_root_pipeline_set_lane_streams(doa_root_pipeline_t *h, int n_lanes, void *const *hip_streams)
 {
-    doa::clear_error();
-    if (!h || n_lanes < 1 || n_lanes > doa::PipeLanes::kMaxLanes || !hip_streams) {
-        doa::set_error("root_pipeline_set_lane_streams: need 1 <= n_lanes <= %d and the streams", doa::PipeLanes::kMaxLanes);
-        return DOA_ERR_INVALID_ARG;
-    }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    return h->lanes.adopt(n_lanes, hip_streams);
+    return doa::PipeFront::entry_set_lane_streams(h, "root_pipeline", n_lanes, hip_streams);
 }
 
 int doa_root_pipeline_synchronize(doa_root_pipeline_t *h)
 {
-    doa::clear_error();
-    if (!h) { doa::set_error("root_pipeline_synchronize: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    if (int brc = doa::bind_device(h->device); brc != DOA_OK) return brc;
-    return h->lanes.synchronize();
+    return doa::PipeFront::entry_synchronize(h, "root_pipeline");
 }
 
 int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, int noutput_items, const void *const *d_input_items,
@@ -289,9 +239,9 @@ int doa_root_pipeline_work_dev_batches(doa_root_pipeline_t *h, int n_batches, in
     auto prepare = [&](doa::PipeLane &ln) { return reserve(h, ln, need_cov, need_status, h->S, h->estimator); };
     auto launch = [&](const doa::PlanGroup &g, doa::PipeLane &ln) -> int {
         const int b = g.b0;                                          // (groups of one)
-        const RootWs ws = view(h, ln, 0, d_status_out ? d_status_out[b] : nullptr);
+        const RootWs ws = view(h, ln, 0);
         return run_chain(h, noutput_items, d_input_items + (size_t)b * N, (d_cov_out && d_cov_out[b]) ? d_cov_out[b] : ws.cov,
-                         d_angles_out[b], ws, ln.st);
+                         d_angles_out[b], nullptr, d_status_out ? d_status_out[b] : nullptr, ws, ln.st);
     };
     const int rc = h->run_planned("root_pipeline_work_dev_batches", n_batches, h->lanes.n_lanes, hip_stream, traits, prepare, launch);
     return rc < 0 ? rc : n_batches * noutput_items;
@@ -321,28 +271,24 @@ int doa_root_pipeline_work(doa_root_pipeline_t *h, int noutput_items, const void
                                      {cov_out, N * N * sizeof(float2), h->self.buf[doa_root_pipeline::kCov].p}};
     const int rc = h->host_run(who, noutput_items, input_items, sec, 3,
                                [h](int n, const void *const *d_in, size_t item_off, void *const *d_sec, hipStream_t st, int lane) {
-        RootWs ws = view(h, h->self, item_off, d_sec[1]);
+        RootWs ws = view(h, h->self, item_off);
         ws.work = h->host_work(lane);
-        return run_chain(h, n, d_in, d_sec[2] ? d_sec[2] : ws.cov, d_sec[0], ws, st);
+        return run_chain(h, n, d_in, d_sec[2] ? d_sec[2] : ws.cov, d_sec[0], nullptr, d_sec[1], ws, st);
     });
     if (rc < 0) return rc;
     // the other items' outputs are valid
-    if (const int bad = first_flagged(h->h_status.as<int>(), noutput_items); bad >= 0) return numeric_error(h, bad, h->h_status.as<int>()[bad]);
+    if (const int bad = doa::gridfree_first_error(h->h_status.as<int>(), noutput_items); bad >= 0) return numeric_error(h, bad, h->h_status.as<int>()[bad]);
     return noutput_items;
 }
 
 int doa_root_pipeline_inject_failure(doa_root_pipeline_t *h, int chunk_index)
 {
-    doa::clear_error();
-    if (!h || chunk_index < -1) { doa::set_error("root_pipeline_inject_failure: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    return h->inject_failure(chunk_index);
+    return doa::PipeFront::entry_inject_failure(h, "root_pipeline", chunk_index);
 }
 
 int doa_root_pipeline_lanes_idle(doa_root_pipeline_t *h)
 {
-    doa::clear_error();
-    if (!h) { doa::set_error("root_pipeline_lanes_idle: bad arguments"); return DOA_ERR_INVALID_ARG; }
-    return h->lanes_idle();
+    return doa::PipeFront::entry_lanes_idle(h, "root_pipeline");
 }
 
 int doa_root_pipeline_set_internal_precision(doa_root_pipeline_t *h, int bits)

@@ -247,6 +247,7 @@ SIGNATURES = {
     "doa_hip_lane_streams_set_aside_debug": (C.c_int, []),
     "doa_hip_batch_plan_debug": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_hip_spectrum_plan_debug": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "doa_hip_gridfree_plan_debug": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "doa_hip_launch_route_debug": (C.c_int, [C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "doa_hip_wave_ops_debug": (C.c_int, [C.c_int, C.c_int, _vp, _vp]),
 }

@@ -140,6 +140,14 @@ DOA_HIP_API int doa_hip_batch_plan_debug(int n_batches, const void *const *outpu
 DOA_HIP_API int doa_hip_spectrum_plan_debug(int estimator, int steering_table, int num_ant_ele, int bits, int counted,
                                             long long *bytes_out);
 
+/* The records a grid-free estimator keeps between its eigen launch and its solver kernel (gr-doa_amd/csrc/gridfree_chain.hpp:
+ * gridfree_plan), as rootMUSIC_linear_array, esprit_linear_array and root_pipeline size them: no handle, no device.
+ * estimator: DOA_GRIDFREE_ROOT_MUSIC / _ESPRIT; bits: the internal precision; counted: 1 = a source count per item.
+ * bytes_out[0..2], bytes per item, 0 = the record does not exist: coefficient record (doubles whatever bits is),
+ * signal-subspace record, status word.  Returns DOA_OK, DOA_ERR_UNSUPPORTED for a combination no entry runs (bytes_out all
+ * 0), or DOA_ERR_INVALID_ARG. */
+DOA_HIP_API int doa_hip_gridfree_plan_debug(int estimator, int num_ant_ele, int bits, int counted, long long bytes_out[3]);
+
 /* Which kernels a shape launches, and with which grids (gr-doa_amd/csrc/launch_routes.hpp: cov_route, evd_route, scan_route): no
  * handle, no device; cu_count is the device's compute-unit count as the launchers would pass it.  stage 0 = K1 (covariance), 1 =
  * K2+K3 (eigen stage), 2 = K4 (scan of a uniform linear array).  shape, n_shape values, 0 / 1 where a flag:
