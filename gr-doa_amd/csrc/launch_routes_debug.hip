@@ -65,7 +65,8 @@ int evd_route_text(const int *v, std::string &t)
     std::string k;
     switch (r.kernel) {
     case doa::EvdKernel::OneLane:
-        k = fmt("music_evd_kernel<%d,%s,%s>", s.N, T, s.mode == doa::EvdMode::Group ? "EvdGroup" : (s.mode == doa::EvdMode::Counts ? "EvdOneCounts" : "EvdOne"));
+        // (the count-per-item and group forms are compiled in double only: music_evd.hip, launch_evd_one_lane)
+        k = fmt("music_evd_kernel<%d,%s,%s>", s.N, s.mode == doa::EvdMode::Fixed ? T : "double", s.mode == doa::EvdMode::Group ? "EvdGroup" : (s.mode == doa::EvdMode::Counts ? "EvdOneCounts" : "EvdOne"));
         break;
     case doa::EvdKernel::Quad: k = fmt("music_evd_quad_kernel<2,%s>", tf(r.PN)); break;
     case doa::EvdKernel::Subspace: k = fmt("music_evd_subspace_kernel<%d,%d,%s>", r.G, s.M, tf(r.PN)); break;

@@ -8,7 +8,8 @@ Two steps, both on a machine with the device:
 
 `run` walks a fixed table of shapes through autocorrelate, MUSIC_lin_array (work_dev, work_dev_counts, debug),
 calibrate_lin_array, esprit_linear_array, rootMUSIC_linear_array, MUSIC_array, music_pipeline (work_dev, work_dev_auto,
-work_dev_batches) and root_pipeline's ESPRIT auto mode, with a marker kernel (a one-element int32 fill) in front of every call,
+work_dev_batches) and root_pipeline's ESPRIT auto mode, and then every recipe of tests/route_census.py (one call and one row,
+labelled "census:<entry>", per kernel instantiation the launch plan can select), with a marker kernel (a one-element int32 fill) in front of every call,
 and writes what it called: per call a label and, for each of the three routed stages the call runs, the shape in the form
 doa_hip_launch_route_debug takes (gr-doa_amd/csrc/launch_routes.hpp).  The shapes are written down here from the arguments of
 the call and from what include/doa_hip.h says the entries do; no route function is asked.  `write` splits the kernel trace at
@@ -238,6 +239,58 @@ def run(calls_path):
             call("music_pipeline.work_dev_batches", stages,
                  lambda: (pipe.work_dev_batches(n, ins, None, specs, mx, am), pipe.synchronize()))
             pipe.close()
+    # ---- the census (tests/route_census.py): every kernel the plan can select, through its recipe; one row per recipe ----
+    def recipe_call(entry, a):
+        """(handle, the call) of a recipe: the entry with the recipe's arguments on the buffers above"""
+        N, n = a["N"], a["n"]
+        if entry == "autocorrelate.work_dev":
+            blk = (doa.autocorrelate_sc16 if a["fmt"] else doa.autocorrelate)(N, a["K"], a["ovl"], a["avg"])
+            return blk, lambda: blk.work_dev(n, streams(N, a["fmt"], a["off"]), outs[0].data_ptr())
+        if entry.startswith("MUSIC_lin_array."):
+            blk = doa.MUSIC_lin_array(0.5, a["M"], N, a["P"])
+            blk.set_internal_precision(a["bits"])
+            if entry.endswith(".debug"):
+                host = cov[N][:n].cpu().numpy()
+                return blk, lambda: blk.debug(host)
+            if entry.endswith(".work_dev_counts"):
+                return blk, lambda: blk.work_dev_counts(n, cov[N].data_ptr(), counts.data_ptr(), spec.data_ptr())
+            return blk, lambda: blk.work_dev(n, cov[N].data_ptr(), spec.data_ptr() + a["off"])
+        if entry == "root_pipeline[esprit].work_dev_auto":
+            blk = doa.root_pipeline(N, a["K"], 0, 0, 0.5, a["M"], max_batch=n)
+            blk.set_estimator("esprit")
+            return blk, lambda: blk.work_dev_auto(n, streams(N, 0, 0), outs[0].data_ptr(), counts.data_ptr(), d_status_ptr=outs[1].data_ptr())
+        if entry == "esprit_linear_array.work_dev":
+            blk = doa.esprit_linear_array(0.5, a["M"], N)
+            return blk, lambda: blk.work_dev(n, cov[N].data_ptr(), outs[0].data_ptr(), outs[1].data_ptr())
+        if entry == "MUSIC_array.work_dev":
+            blk = doa.MUSIC_array(a["M"], np.exp(1j * rng.uniform(0, 6.28, (32, N))))
+            return blk, lambda: blk.work_dev(n, cov[N].data_ptr(), spec.data_ptr())
+        if entry == "calibrate_lin_array.work_dev":
+            blk = doa.calibrate_lin_array(0.5, N, 45.0)
+            blk.set_internal_precision(a["bits"])
+            return blk, lambda: blk.work_dev(n, cov[N].data_ptr(), outs[0].data_ptr())
+        if entry == "music_pipeline.work_dev":
+            blk = doa.music_pipeline(N, a["K"], 0, 0, 0.5, a["M"], a["P"], max_batch=n)
+            blk.set_internal_precision(a["bits"])
+            return blk, lambda: blk.work_dev(n, streams(N, 0, 0), None, spec.data_ptr() if a["store"] else None, outs[0].data_ptr(), outs[1].data_ptr())
+        assert entry == "music_pipeline.work_dev_batches", entry
+        blk = (doa.music_pipeline_sc16 if a["fmt"] else doa.music_pipeline)(N, a["K"], 0, a["avg"], 0.5, a["M"], a["P"], max_batch=n)
+        blk.set_lanes(1)
+        nb, sb = a["nb"], 4 if a["fmt"] else 8
+        ins = [[p + b * n * a["K"] * sb for p in streams(N, a["fmt"], a["off"])] for b in range(nb)]
+        specs = [spec.data_ptr() + b * n * a["P"] * 4 for b in range(nb)] if a["store"] else None
+        mx = [outs[0].data_ptr() + b * n * a["M"] * 4 for b in range(nb)]
+        am = [outs[1].data_ptr() + b * n * a["M"] * 4 for b in range(nb)]
+        return blk, lambda: (blk.work_dev_batches(n, ins, None, specs, mx, am), blk.synchronize())
+
+    sys.path.append(os.path.join(ROOT, "tests"))
+    import route_census
+    for stage, recipes in sorted(route_census.RECIPES.items()):
+        for kernel in sorted(recipes):
+            r = recipes[kernel]
+            blk, fn = recipe_call(r["entry"], r["args"])
+            call("census:" + r["entry"], r["stages"], fn)
+            blk.close()
     marker.fill_(len(calls))
     torch.cuda.synchronize()
     json.dump({"cu_count": cu, "calls": calls}, open(calls_path, "w"))
