@@ -173,6 +173,17 @@ int launch_capon_inverse(int N, int n_items, const void *d_R, double loading, co
 // M peak values / locations (d_max / d_argmax may be NULL) become NaN (the scan kernels write 0.0 dB for a NaN record)
 int launch_capon_invalid_rows(int P, int M, int n_items, const void *d_status, void *d_spec, void *d_max, void *d_argmax,
                               hipStream_t st);
+// IAA (iaa.hip; definition in include/doa_hip.h): the whole estimator of n_items covariance items in one launch, one wave per
+// item.  d_zd: the P double2 phases of a MusicTables.  Its outputs (device pointers; only spec is required):
+struct IaaOut {
+    float *spec = nullptr;      // P floats per item: dB against the row maximum
+    float *power = nullptr;     // P floats per item: mu p_k, in the units of the covariance item
+    int *status = nullptr;      // int32 per item: 0 ok / 1 (both rows NaN)
+    double *p_dbg = nullptr;    // diagnostics: the final p_k in double, P per item
+    double *lag_dbg = nullptr;  // diagnostics: the lags r_l of the last iteration's R, N (re, im) pairs per item
+};
+int launch_iaa(int N, int P, int iterations, double loading, int n_items, const void *d_R, const void *d_zd, const IaaOut &out,
+               hipStream_t st);
 // ---- arbitrary array geometry (array_scan.hip; definition in include/doa_hip.h) -------------------------------------------
 // FULL RECORD of a Hermitian N x N matrix X: N^2 doubles per item, X packed into a real square (column-major index
 // r + c N):   [r + r N] = X[r][r];   for r < c:  [r + c N] = Re X[r][c],  [c + r N] = Im X[r][c].

@@ -19,6 +19,11 @@ the Capon (MVDR) spectrum, which needs no source count and no eigendecomposition
 
     blk = doa.capon_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0)
 
+the iterative adaptive (IAA) power spectrum, for single snapshots, for coherent sources at the full aperture and for source
+powers: a dB row like the others and, on a second port, the power per direction in the units of the covariance item:
+
+    blk = doa.iaa_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0, iterations=10)
+
 one covariance per snapshot and frequency bin, for several narrowband emitters at different frequencies in one band:
 
     blk = doa.channel_covariance(inputs, snapshot_size, overlap_size, fft_len, window="hann")
@@ -64,7 +69,7 @@ Importing fails if gr-doa_amd/lib/libdoa_hip.so has not been built; constructing
 no HIP device is usable.  There is no CPU fallback.
 """
 from ._lib import DoaError, LIB_PATH, last_error  # noqa: F401
-from .blocks import (autocorrelate, channel_covariance, wideband_music, wideband_bin_spacing, focus_covariance, rss_focusing_matrices, coarray_covariance, coarray_lags, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, rootMUSIC_linear_array,  # noqa: F401
+from .blocks import (autocorrelate, channel_covariance, wideband_music, wideband_bin_spacing, focus_covariance, rss_focusing_matrices, coarray_covariance, coarray_lags, antenna_correction, phase_correct_hier, read_phase_config, calibrate_lin_array, MUSIC_lin_array, find_local_max, source_count, spatial_smooth, capon_lin_array, iaa_lin_array, rootMUSIC_linear_array,  # noqa: F401
                      esprit_linear_array,
                      MUSIC_array, capon_array, planar_steering_table, uca_positions, planar_steering_grid, find_local_max_2d, array_grid_debug,
                      music_pipeline, root_pipeline, root_music_pipeline, autocorrelate_sc16, music_pipeline_sc16,

@@ -175,6 +175,11 @@ SIGNATURES = {
     "doa_capon_lin_array_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_capon_lin_array_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "doa_capon_lin_array_items_total": (C.c_longlong, [_vp]),
+    "doa_iaa_lin_array_create": (_vp, [C.c_float, C.c_int, C.c_int, C.c_float, C.c_int]),
+    "doa_iaa_lin_array_destroy": (None, [_vp]),
+    "doa_iaa_lin_array_work": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "doa_iaa_lin_array_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "doa_iaa_lin_array_items_total": (C.c_longlong, [_vp]),
     "doa_music_pipeline_set_estimator": (C.c_int, [_vp, C.c_int, C.c_float]),
     "doa_planar_steering_table": (C.c_int, [C.c_int, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp]),
     "doa_MUSIC_array_create": (_vp, [C.c_int, C.c_int, C.c_int, _vp]),
@@ -235,6 +240,7 @@ SIGNATURES = {
     "doa_coarray_covariance_work_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     # include/doa_hip_test.h (diagnostics, profiling, fault injection: the test suite's entry points)
     "doa_capon_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "doa_iaa_lin_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_MUSIC_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_capon_array_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "doa_esprit_linear_array_record_debug": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),

@@ -805,6 +805,54 @@ class capon_lin_array(_ItemBlock):
         return int(lib.doa_capon_lin_array_items_total(self._h))
 
 
+class iaa_lin_array(_ItemBlock):
+    """doa.iaa_lin_array(norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0, iterations=10) — the iterative adaptive
+    (IAA) power spectrum of each covariance item on MUSIC_lin_array's angle grid: no source count, no eigendecomposition, no
+    smoothing; it works on rank-one items (one snapshot) and on coherent sources at the full aperture, and its peak heights
+    are source powers (definition: include/doa_hip.h).  A fixed number of iterations (1..32), so the run time does not
+    depend on the data.  Port 0: the spectrum in dB against the row maximum; port 1 (optional): the power per direction in
+    the units of the item, float32 [n, P]; port 2 (optional): int32 status, 1 = a failed pivot or a non-finite item (both
+    rows NaN).  Not a block of the reference."""
+
+    _destroy = staticmethod(lib.doa_iaa_lin_array_destroy)
+
+    def __init__(self, norm_spacing, inputs, pspectrum_len, diagonal_loading=0.0, iterations=10):
+        super().__init__()
+        self.norm_spacing, self.num_ant_ele = float(norm_spacing), int(inputs)
+        self.pspectrum_len, self.diagonal_loading = int(pspectrum_len), float(diagonal_loading)
+        self.iterations = int(iterations)
+        self._h = check_handle(lib.doa_iaa_lin_array_create(self.norm_spacing, self.num_ant_ele, self.pspectrum_len,
+                                                            self.diagonal_loading, self.iterations), "iaa_lin_array")
+        self.in_sig = [(_C64, self.num_ant_ele ** 2)]
+        self.out_sig = [(_F32, self.pspectrum_len), (_F32, self.pspectrum_len), (_I32, 1)]
+
+    def work(self, noutput_items, input_items, output_items) -> int:
+        """output_items = [spectrum float32 [n, P]], [spectrum, power float32 [n, P]] or [spectrum, power, status int32 [n]];
+        power may be None."""
+        n = int(noutput_items)
+        return check(lib.doa_iaa_lin_array_work(self._h, n, self._items_in(input_items[0], _C64, n, self.num_ant_ele ** 2),
+                                                self._items_out(output_items[0], _F32, n, self.pspectrum_len),
+                                                self._opt_out(output_items, 1, _F32, n, self.pspectrum_len),
+                                                self._opt_out(output_items, 2, _I32, n, 1)))
+
+    def work_dev(self, noutput_items, d_in_ptr, d_out_ptr, d_power_ptr=None, d_status_ptr=None, stream=None) -> int:
+        return check(lib.doa_iaa_lin_array_work_dev(self._h, int(noutput_items), _dev_ptr(d_in_ptr), _dev_ptr(d_out_ptr),
+                                                    _opt_ptr(d_power_ptr), _opt_ptr(d_status_ptr), _stream_ptr(stream)))
+
+    def debug(self, R_items: np.ndarray):
+        """(p [n, P] float64: the final p_k before the scaling by mu, lags [n, N] complex128: r_l of the last iteration's R)
+        for the tests."""
+        a = np.ascontiguousarray(R_items, dtype=_C64).reshape(-1, self.num_ant_ele ** 2)
+        n = a.shape[0]
+        p = np.empty((n, self.pspectrum_len), dtype=np.float64)
+        lags = np.empty((n, self.num_ant_ele), dtype=np.complex128)
+        check(lib.doa_iaa_lin_array_debug(self._h, n, _vp(a), _vp(p), _vp(lags)))
+        return p, lags
+
+    def nout_items_total(self) -> int:
+        return int(lib.doa_iaa_lin_array_items_total(self._h))
+
+
 def _steering(table) -> np.ndarray:
     """[P, N] complex128, C-contiguous (the layout doa_MUSIC_array_create / doa_capon_array_create read)."""
     a = np.ascontiguousarray(table, dtype=np.complex128)

@@ -535,6 +535,53 @@ DOA_HIP_API long long doa_capon_lin_array_items_total(const doa_capon_lin_array_
 DOA_HIP_API int doa_music_pipeline_set_estimator(doa_music_pipeline_t *h, int estimator, float diagonal_loading);
 
 /* ---------------------------------------------------------------------------------------------
+ * iaa_lin_array — the iterative adaptive (IAA: Yardibi, Li, Stoica et al., 2010) power spectrum of a uniform linear array:
+ *   a power per direction, in the units of the covariance item, on the angle grid of MUSIC_lin_array.  It needs no source
+ *   count, no eigendecomposition and no smoothing; it works on rank-one items (one snapshot), separates coherent sources at
+ *   the full aperture, and its peak heights ARE the source powers.  A fixed number of iterations, so its time does not depend
+ *   on the data.  Not a block of the reference.
+ * The definition, one for every entry (tests/iaa_ref.py restates it in numpy):
+ *   input item   as capon_lin_array reads it: column-major N x N gr_complex, ONLY THE UPPER TRIANGLE, of the diagonal the
+ *                real part; H = the Hermitian matrix these define.  All arithmetic is in double.  a_k = the steering vector
+ *                of direction k of MUSIC_lin_array's grid (its float-accumulated theta included), k = 0 .. pspectrum_len - 1.
+ *     mu   = (sum_i H[i,i]) / N ;  Hn = H / mu
+ *     p_k  = Re(a_k^H Hn a_k) / N^2                                    the start: the Bartlett spectrum
+ *     repeat L = iterations times (never data dependent):
+ *       R   = sum_k p_k a_k a_k^H + delta I                            delta = (double) diagonal_loading, relative as in Capon
+ *       W   = R^-1                                                     via Cholesky R = L L^H, W = L^-H L^-1
+ *       B   = W Hn W
+ *       g_k = Re(a_k^H W a_k) ;  n_k = max(Re(a_k^H B a_k), 0)
+ *       p_k = n_k / g_k^2
+ *     spectrum row = 10 log10(p / max p), formed as MUSIC_lin_array forms its row from out = p: out rounded to float, a
+ *                    float quotient, 0 dB exactly at the largest rounded value; p_k = 0 gives -inf
+ *     power row    = (float)(mu p_k)                                   the optional second port
+ *   (the kernel multiplies by 1 / mu formed once; an item multiplied by a power of two gives the same spectrum bits and
+ *   a power row multiplied by exactly that factor.  For a uniform linear array R is Hermitian Toeplitz, fixed by the N lags
+ *   r_l = sum_k p_k w_k^l, w_k = a_k[n+1] / a_k[n], and the kernel builds it from them.)
+ *   status per item (int32): 0 ok; 1: mu > 0 does not hold, a Cholesky pivot of any iteration fails
+ *     s_j > DOA_CAPON_PIVOT_MIN * R[j,j], or any quantity is not finite.  A status-1 item gets all-NaN rows on both ports; the
+ *     other items of the call are not affected.
+ * Internal precision 64 only: a handle created while the process default is 32 returns DOA_ERR_UNSUPPORTED from its work
+ * entries.  create validates before the device is touched: 2 <= num_ant_ele <= DOA_MAX_ANT_ELE, 0 < norm_spacing <= 0.5,
+ * 1 <= pspectrum_len <= DOA_IAA_MAX_PSPECTRUM_LEN, diagonal_loading finite and >= 0, 1 <= iterations <=
+ * DOA_IAA_MAX_ITERATIONS (DOA_IAA_DEFAULT_ITERATIONS is what the Python block and the GRC descriptor default to).
+ * power_out / d_power_out (pspectrum_len floats per item) and status_out / d_status_out (one int32 per item) may be NULL.
+ * --------------------------------------------------------------------------------------------- */
+#define DOA_IAA_MAX_PSPECTRUM_LEN 4096
+#define DOA_IAA_MAX_ITERATIONS 32
+#define DOA_IAA_DEFAULT_ITERATIONS 10
+typedef struct doa_iaa_lin_array doa_iaa_lin_array_t;
+
+DOA_HIP_API doa_iaa_lin_array_t *doa_iaa_lin_array_create(float norm_spacing, int num_ant_ele, int pspectrum_len,
+                                                          float diagonal_loading, int iterations);
+DOA_HIP_API void doa_iaa_lin_array_destroy(doa_iaa_lin_array_t *h);
+DOA_HIP_API int doa_iaa_lin_array_work(doa_iaa_lin_array_t *h, int noutput_items, const void *cov_items, void *spectrum_out,
+                                       void *power_out, void *status_out);
+DOA_HIP_API int doa_iaa_lin_array_work_dev(doa_iaa_lin_array_t *h, int noutput_items, const void *d_cov_items,
+                                           void *d_spectrum_out, void *d_power_out, void *d_status_out, void *hip_stream);
+DOA_HIP_API long long doa_iaa_lin_array_items_total(const doa_iaa_lin_array_t *h);
+
+/* ---------------------------------------------------------------------------------------------
  * Arbitrary array geometry: MUSIC_array and capon_array — the two spectra for an array given by a STEERING TABLE instead of
  *   a uniform linear array: a uniform circular array, any planar layout, or a measured (calibrated) manifold of a linear one.
  *   Every other estimator of this library assumes a_n = z^n and hands its scan the 2N-1 diagonal sums of the projector, which

@@ -55,6 +55,12 @@ DOA_HIP_API int doa_rootMUSIC_linear_array_select_counts_debug(doa_rootMUSIC_lin
 DOA_HIP_API int doa_capon_lin_array_debug(doa_capon_lin_array_t *h, int noutput_items, const void *cov_items,
                                           void *inverse_out, void *null_spectrum_out);
 
+/* Diagnostics of iaa_lin_array (host buffers, synchronous): per item the final p_k in double (power_out: pspectrum_len doubles,
+ * before the scaling by mu) and the lags r_l of the last iteration's R (lags_out: num_ant_ele (re, im) pairs of doubles); both
+ * NaN for a status-1 item.  Either output pointer may be NULL. */
+DOA_HIP_API int doa_iaa_lin_array_debug(doa_iaa_lin_array_t *h, int noutput_items, const void *cov_items, void *power_out,
+                                        void *lags_out);
+
 /* Diagnostics of MUSIC_array and capon_array (host buffers, synchronous): per item the matrix X the scan read (projector_out /
  * inverse_out: N x N complex128, column-major, unpacked from the double full record; NaN for a status-1 Capon item) and
  * the un-normalised null spectrum Q_i = Re(a_i^H X a_i) (null_spectrum_out: pspectrum_len floats).  Either output pointer may
